@@ -1,6 +1,6 @@
 """Headline benchmark: training frames/s of the var_sep hot path on MI355X (contract in the task statement).
 
-    python bench.py --gpus N --steps K --warmup W [--config waveeq] [--precision bf16|fp16|fp32]
+    python bench.py --gpus N --steps K --warmup W [--config waveeq] [--precision bf16|fp16|fp32] [--dump-outputs DIR] [--full]
 
 One step = ae_loss + zero_order_loss + get_forecast + forecast MSE + t-regulariser, backward, gradient all-reduce
 (N > 1) and the Adam update, on one seeded synthetic batch per rank that is resident in HBM before timing starts.
@@ -12,12 +12,20 @@ Ranks: under `torch.distributed.run` (RANK / WORLD_SIZE in the environment) this
 rank 0 prints the JSON line.  VARSEP_BENCH_SHARE_GPU=1 puts every rank on cuda:0 and exchanges gradients over gloo (the
 one-GPU test of the N > 1 path, tests/test_safety_gpu.py::test_bench_spawns_its_own_ranks).
 
-Timing: W warm-up steps, then `--repeats` (default 5) timed regions of EXACTLY K steps each, every region bracketed by
+Timing: W warm-up steps, then `--repeats` timed regions of EXACTLY K steps each, every region bracketed by
 barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; the reported ms_per_step is the median region
-(all of them are listed in `ms_per_step_all`).
+(all of them are listed in `ms_per_step_all`).  A plain run times ONE region (K timed steps in all) and does nothing else: no profiler
+passes, no instrumented eager steps, no further workloads, no CPU baseline.  `--full` (default 5 regions, extended to
+VARSEP_BENCH_MIN_TIMED_S of timed time) adds everything below.
 
-The line also carries `configs`: further BASELINE workloads timed the same way with fewer steps, each with the roofline position of its
-dominant kernel group -- at N = 1 Moving-MNIST DCGAN B=128, TaxiBJ VGG B=100, SST nt_pred 40 B=8 in bf16 and SST in fp16 (the dtype
+`--dump-outputs DIR`: after the timed steps, what the LAST timed step handed its caller is written as DIR/<name>.npy -- loss.npy (the
+total loss the step returns, float64 [1]) and state.npy (the parameters and BatchNorm statistics the step leaves, float32: every
+floating-point entry of the network's state_dict flattened in state_dict order, a fixed seeded sample of DUMP_MAX_ELEMS of them when
+larger); with --eval, forecast.npy (the last get_forecast output, same sampling).  Inputs are seeded: the same arguments give the same
+inputs in every run.
+
+With `--full` the line also carries `configs`: further BASELINE workloads timed the same way with fewer steps, each with the roofline
+position of its dominant kernel group -- at N = 1 Moving-MNIST DCGAN B=128, TaxiBJ VGG B=100, SST nt_pred 40 B=8 in bf16 and SST in fp16 (the dtype
 BASELINE.json configs[4] states); at N > 1 TaxiBJ and SST (configs[3], configs[4]: the two workloads stated at 8 GPUs), data-parallel
 over the same ranks.
 
@@ -29,9 +37,9 @@ around a 4096^3 GEMM).  Fallbacks, in order: the committed table profiles/r<NN>_
 equals profiling.source_sha() (`"replay-committed"`); live HIP events around every launch of three eager steps (`"eager"`, with
 `"stale": true` when a committed table exists but belongs to other sources).  VARSEP_BENCH_LIVE_PROFILE=0 | headline | all (default all).
 
-Output: stdout carries ONE JSON line of < 4 KB (headline, one roofline object, cpu_baseline, one short entry per further workload);
-everything else (all regions, every group's roofline, eager-event figures, traffic sources, prose) goes to `bench_detail.json` next to
-this file and to stderr.
+Output: stdout carries ONE JSON line of < 4 KB (headline; with `--full` also one roofline object, cpu_baseline, one short entry per
+further workload); everything else (all regions, every group's roofline, eager-event figures, traffic sources, prose) goes to
+`bench_detail.json` next to this file and to stderr.
 """
 import argparse
 import json
@@ -69,7 +77,13 @@ def parse():
     p.add_argument('--gpus', type=int, default=1)
     p.add_argument('--steps', type=int, default=20)
     p.add_argument('--warmup', type=int, default=5)
-    p.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps each; the median is reported')
+    p.add_argument('--repeats', type=int, default=None, help='timed regions of --steps steps each; the median is reported (default: 1, '
+                   'with --full 5)')
+    p.add_argument('--full', action='store_true', help='also measure what the headline does not need: profiler passes of the replayed '
+                   'step, per-kernel-group rooflines, the further workloads under "configs", the CPU baseline, at least '
+                   'VARSEP_BENCH_MIN_TIMED_S of timed regions')
+    p.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                   help='write what the last timed step computed as DIR/<name>.npy (loss.npy, state.npy; --eval: forecast.npy)')
     p.add_argument('--config', default='waveeq')
     p.add_argument('--precision', default='bf16', choices=['bf16', 'fp16', 'fp32'])
     p.add_argument('--batch', type=int, default=None, help='per-GPU batch (default: the config\'s)')
@@ -83,9 +97,12 @@ def parse():
                    'them to gpurun_out/graph_stats.json')
     p.add_argument('--cpu_steps', type=int, default=None)
     p.add_argument('--extra_configs', default=None,
-                   help='comma list of further workloads appended under "configs" (default at N=1 with the default workload: '
+                   help='comma list of further workloads appended under "configs" (default with --full at N=1 with the default workload: '
                         + EXTRA_DEFAULT + '; "none" disables)')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def _free_port():
@@ -231,23 +248,59 @@ class ExchangeTimeout(RuntimeError):
     pass
 
 
-def run_workload(name, args, rk, steps, warmup, repeats, batch=None, precision=None):
+DUMP_MAX_ELEMS = 1 << 22           # elements per array written by --dump-outputs: 16 MB of float32 (the arrays of one run stay under 64 MB)
+
+
+def _flat_sample(tensors, seed=1234):
+    """The tensors' elements, flattened and concatenated in order, as float32; above DUMP_MAX_ELEMS a fixed sample of DUMP_MAX_ELEMS of them
+    (sorted positions drawn by numpy.random.default_rng(seed), which leaves the global NumPy stream alone: the same positions in every run
+    of the same workload)."""
+    sizes = [t.numel() for t in tensors]
+    total = sum(sizes)
+    if total <= DUMP_MAX_ELEMS:
+        return np.concatenate([t.detach().reshape(-1).float().cpu().numpy() for t in tensors] or [np.zeros(0, np.float32)])
+    pos = np.sort(np.random.default_rng(seed).integers(0, total, size=DUMP_MAX_ELEMS))
+    out, off = [], 0
+    for t, n in zip(tensors, sizes):
+        lo, hi = np.searchsorted(pos, [off, off + n])
+        if hi > lo:
+            idx = torch.from_numpy(pos[lo:hi] - off).to(t.device)
+            out.append(t.detach().reshape(-1).index_select(0, idx).float().cpu().numpy())
+        off += n
+    return np.concatenate(out)
+
+
+def dump_training_outputs(dump_dir, rk, net, opt, sync, loss):
+    """--dump-outputs of a training workload, right after the last timed step: the total loss that step returned (loss.npy) and the state
+    it left (state.npy: every floating-point entry of the network's state_dict -- parameters, BatchNorm statistics -- in state_dict order)."""
+    if sync is not None and getattr(sync, 'masters_dirty', False):
+        sync.sync_masters(opt)               # sharded optimizer: every rank's slice of the fp32 masters (a collective: every rank is here)
+    if rk.rank != 0:
+        return
+    torch.cuda.synchronize()
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, 'loss.npy'), np.array([float(loss.item())], dtype=np.float64))
+    np.save(os.path.join(dump_dir, 'state.npy'), _flat_sample([v for v in net.state_dict().values() if v.is_floating_point()]))
+
+
+def run_workload(name, args, rk, steps, warmup, repeats, batch=None, precision=None, dump_dir=None):
     """`_run_workload`; if the integrator's inter-workgroup exchange reports a time-out while it runs in its XCD-local form (a slab's ring of
     workgroups is assumed to share an XCD, csrc/vs_rollout.hip), the workload is measured again with the placement-independent agent-scope
     exchange instead of failing the run (every rank takes the same decision: the flag is all-reduced)."""
     try:
-        return _run_workload(name, args, rk, steps, warmup, repeats, batch=batch, precision=precision)
+        return _run_workload(name, args, rk, steps, warmup, repeats, batch=batch, precision=precision, dump_dir=dump_dir)
     except ExchangeTimeout as e:
         if os.environ.get('VS_ROLLOUT_XCD_LOCAL', '1') == '0':
             raise
         if rk.rank == 0:
             print('bench.py: %s -- measuring again with VS_ROLLOUT_XCD_LOCAL=0' % e, file=sys.stderr)
         os.environ['VS_ROLLOUT_XCD_LOCAL'] = '0'
-        return _run_workload(name, args, rk, steps, warmup, repeats, batch=batch, precision=precision)
+        return _run_workload(name, args, rk, steps, warmup, repeats, batch=batch, precision=precision, dump_dir=dump_dir)
 
 
-def _run_workload(name, args, rk, steps, warmup, repeats, batch=None, precision=None):
-    """Build the workload `name`, warm up, time `repeats` regions of `steps` steps; returns timings + per-kernel event profile."""
+def _run_workload(name, args, rk, steps, warmup, repeats, batch=None, precision=None, dump_dir=None):
+    """Build the workload `name`, warm up, time `repeats` regions of `steps` steps; returns timings + (--full) per-kernel event profile.
+    `dump_dir`: write what the last timed step computed there (dump_training_outputs)."""
     precision = precision or args.precision
     from spatiotemporal_variable_separation_amd import functional as VF, ops
     from spatiotemporal_variable_separation_amd.configs import BASELINE_CONFIGS
@@ -340,7 +393,7 @@ def _run_workload(name, args, rk, steps, warmup, repeats, batch=None, precision=
         timed_step = step
     for _ in range(warmup):
         timed_step()
-    events_on = os.environ.get('VARSEP_BENCH_NO_EVENTS') is None
+    events_on = args.full and os.environ.get('VARSEP_BENCH_NO_EVENTS') is None
     n_inst = 3                                # instrumented eager steps after a graph-replay timed region
     ops.profile_reset(enable=False)
     regions = []
@@ -369,6 +422,8 @@ def _run_workload(name, args, rk, steps, warmup, repeats, batch=None, precision=
         rk.barrier()
         regions.append(rk.max_over_ranks(time.perf_counter() - t0))
         ops._PROF['on'] = False
+    if dump_dir is not None:
+        dump_training_outputs(dump_dir, rk, net, opt, sync, loss)
     sampled = len([i for i in range(steps) if i % 4 == 3 or steps < 8])
     if graphed is not None and events_on:
         # per-kernel durations cannot be taken inside a graph replay (events are not recordable there): the same step is
@@ -429,6 +484,10 @@ def run_eval(name, args, rk):
                 out = net.get_forecast(cond, n)[0]
             rk.barrier()
             regions.append(rk.max_over_ranks(time.perf_counter() - t0))
+    if args.dump_outputs and rk.rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        f = _flat_sample([out])
+        np.save(os.path.join(args.dump_outputs, 'forecast.npy'), f.reshape(tuple(out.shape)) if f.size == out.numel() else f)
     ms = statistics.median(regions) / args.steps * 1e3
     frames = rk.world * cfg['batch'] * n
     return {'metric': 'inference frames/sec (eval-mode get_forecast, frames emitted)', 'value': round(frames / (ms * 1e-3), 1), 'unit': 'frames/s',
@@ -613,8 +672,9 @@ def compact_line(full, limit=4000):
                                 'vs_baseline', 'dtype', 'data') if k in full}
     cfg = full.get('config', {})
     out['config'] = {k: cfg[k] for k in ('workload', 'global_batch', 'parallelism', 'grad_allreduce', 'launch', 'final_loss') if k in cfg}
-    rf = full.get('roofline')
-    out['roofline'] = None if rf is None else {k: rf[k] for k in _ROOF_KEYS if k in rf}
+    if 'roofline' in full:                   # (--full)
+        rf = full['roofline']
+        out['roofline'] = None if rf is None else {k: rf[k] for k in _ROOF_KEYS if k in rf}
     if full.get('graph'):
         out['graph'] = full['graph']
     cb = full.get('cpu_baseline')
@@ -670,7 +730,7 @@ def main():
     force_dist = os.environ.get('VARSEP_BENCH_FORCE_DIST') == '1'
     extra = args.extra_configs
     if extra is None:
-        if args.config == 'waveeq' and args.batch is None and args.precision == 'bf16':
+        if args.full and args.config == 'waveeq' and args.batch is None and args.precision == 'bf16':
             extra = EXTRA_DEFAULT if (world == 1 and not force_dist) else EXTRA_DEFAULT_DIST
         else:
             extra = 'none'
@@ -679,7 +739,7 @@ def main():
     # per-kernel clock of the replayed step, measured in this run: child passes under rocprofv3 BEFORE this process touches the GPU
     live = {}
     mode = os.environ.get('VARSEP_BENCH_LIVE_PROFILE', 'all')
-    if (mode != '0' and world == 1 and not force_dist and not args.eval_mode and not args.no_graph and args.batch is None
+    if (args.full and mode != '0' and world == 1 and not force_dist and not args.eval_mode and not args.no_graph and args.batch is None
             and os.environ.get('VARSEP_BENCH_NO_EVENTS') is None):
         t_start = time.time()
         todo = [(args.config, args.precision, args.steps, args.warmup)]
@@ -703,7 +763,7 @@ def main():
             os.write(result_fd, (json.dumps(line) + '\n').encode())
         rk.close()
         return
-    res = run_workload(args.config, args, rk, args.steps, args.warmup, args.repeats, batch=args.batch)
+    res = run_workload(args.config, args, rk, args.steps, args.warmup, args.repeats, batch=args.batch, dump_dir=args.dump_outputs)
 
     # further workloads under "configs".  Every rank runs them (they contain the same barriers / all-reduces); rank 0 reports.
     configs = None
@@ -740,7 +800,6 @@ def main():
         return
     cfg, ms = res['cfg'], res['ms']
     frames = rk.world * cfg['batch'] * cfg['nt_pred']
-    roof, others = rooflines(res, args.config, args.precision, live=live.get((args.config, args.precision)))
     launch = 'hipGraph replay' if res['use_graph'] else 'eager'
     out = {
         'metric': 'training frames/sec (seq x nt_pred)', 'value': round(frames / (ms * 1e-3), 1), 'unit': 'frames/s',
@@ -752,11 +811,12 @@ def main():
                    'grad_allreduce': allreduce_text(rk, res), 'optimizer': res['optimizer'], 'launch': launch,
                    'timing': 'median of %d regions of %d steps' % (len(res['ms_all']), args.steps),
                    'final_loss': round(res['loss'], 5)},
-        'roofline': roof, 'roofline_others': others,
         # nodes / kernel nodes / dependency edges / roots of the recorded step (train.GraphedStep.graph_stats): what one replay costs the host
         'graph': res.get('graph'),
     }
-    if out.get('graph') is None:
+    if args.full:
+        out['roofline'], out['roofline_others'] = rooflines(res, args.config, args.precision, live=live.get((args.config, args.precision)))
+    if out.get('graph') is None and args.full:
         tab, src, fresh = _latest_profile(args.config, args.precision, 'graph')
         if tab is not None and fresh:
             out['graph'] = dict({k: tab[k] for k in ('nodes', 'kernel_nodes', 'edges', 'roots') if k in tab}, source=src)
@@ -775,7 +835,7 @@ def main():
     if live:
         out['live_profile'] = {'%s/%s' % k: {kk: v[kk] for kk in ('steps', 'seconds', 'profiled_ms_per_step', 'unassigned_us_per_step')}
                                for k, v in live.items()}
-    if rk.world == 1 and not args.no_cpu_baseline:
+    if args.full and rk.world == 1 and not args.no_cpu_baseline:
         steps = args.cpu_steps or (5 if args.config in ('waveeq', 'mnist_b16') else 2)
         out['cpu_baseline'] = cpu_baseline(cfg, steps)
     from spatiotemporal_variable_separation_amd.profiling import source_sha

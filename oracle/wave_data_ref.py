@@ -93,10 +93,11 @@ class sorted_listdir:
 
 
 def fixture_dir():
+    """A directory of this process alone, directly under the temporary directory (a shared parent would belong to whichever user
+    created it first); user and process id are spelt in letters: the path holds no digit."""
     import tempfile
     tmp = tempfile.gettempdir()
     if re.findall(r'\d', tmp):
         tmp = '/tmp'
-    base = os.path.join(tmp, 'varsep_wave_fixture')
-    suffix = ''.join(chr(ord('a') + (os.getpid() // 26 ** k) % 26) for k in range(6))
-    return os.path.join(base, suffix)
+    suffix = ''.join(chr(ord('a') + (n // 26 ** k) % 26) for n in (os.getuid(), os.getpid()) for k in range(6))
+    return os.path.join(tmp, 'varsep_wave_fixture_' + suffix)

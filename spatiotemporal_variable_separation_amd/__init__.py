@@ -8,16 +8,18 @@ import os as _os
 
 __version__ = '0.3.0'
 
-_QUEUE_KNOBS = ('GPU_MAX_HW_QUEUES', 'DEBUG_HIP_FORCE_GRAPH_QUEUES')
+_QUEUE_KNOBS = ('GPU_MAX_HW_QUEUES',)
 
 
 def configure_single_gpu_queues(force=False):
     """HIP runtime knobs for SINGLE-GPU training processes; call before the first HIP call of the process (main.py and bench.py do, right
     at start-up -- importing the package does NOT touch the environment).  A recorded training step forks into the integrator's stream and
-    up to three gradient streams beside the main chain; with the runtime's defaults (4 hardware queues, 4 graph streams) independent
-    branches of a replayed hipGraph are mapped onto the same queue and run one after the other (WaveEq step, same box: 1.68 -> 1.58 ms
-    with 8 / 8).  Data-parallel ranks keep the defaults: with 8 hardware queues the graph A -> RCCL all-reduce -> graph B step ran at
-    4.1 ms instead of 2.2 ms -- so nothing is set when WORLD_SIZE > 1 or VARSEP_BENCH_FORCE_DIST=1, and a launcher that starts
+    up to three gradient streams beside the main chain; with the runtime's default of 4 hardware queues independent branches of a replayed
+    hipGraph can share a queue and run one after the other, so 8 are asked for.  How the runtime schedules a replayed graph is left at its
+    defaults: a graph-queue count above the hardware-queue count crashed the runtime at the first replay of a step with three lanes
+    whenever the hardware queues were pinned to 4 from outside.  Data-parallel ranks keep the defaults: with 8 hardware queues the
+    graph A -> RCCL all-reduce -> graph B step ran at 4.1 ms instead of 2.2 ms -- so nothing is set when WORLD_SIZE > 1 or
+    VARSEP_BENCH_FORCE_DIST=1, and a launcher that starts
     data-parallel ranks from a process that called this must drop the variables listed in VARSEP_PACKAGE_SET from the children's
     environment (bench.spawn_ranks does).  Explicit settings in the environment win.  Returns the names it set."""
     import sys

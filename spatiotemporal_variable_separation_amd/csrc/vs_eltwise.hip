@@ -201,6 +201,59 @@ __global__ __launch_bounds__(256) void colsum_multi_kernel(ColsumJobs J) {
     }
 }
 
+// Jobs taller than one row block (the integrator's bias gradients: (steps - 1) * B rows): one workgroup per 32-column strip of a job walks
+// ALL of its rows -- 4 lanes x 8 consecutive columns, 64 row groups -- and the row groups meet in LDS in a fixed order.  Every column sum
+// has one writer, so it does not depend on the order in which workgroups finish (partial sums of row blocks added with float atomics do:
+// two runs of the same step differed in the last bits of these gradients).
+constexpr int CSR_COLS = 32;
+__global__ __launch_bounds__(256) void colsum_multi_rows_kernel(ColsumJobs J) {
+    __shared__ float part[64][CSR_COLS + 1];
+    int j = 0;
+    while (j + 1 < J.nj && (int)blockIdx.x >= J.blk_off[j + 1]) ++j;
+    const int64_t M = J.M[j], N = J.N[j], ldx = J.ld[j];
+    const int c8 = threadIdx.x & 3, g = threadIdx.x >> 2;
+    const int64_t n0 = (int64_t)(blockIdx.x - J.blk_off[j]) * CSR_COLS, n = n0 + 8 * c8;
+    const void* X = J.x[j];
+    const int xd = J.dt[j];
+    float s[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = 0.f;
+    const bool vec = n + 8 <= N && ldx % 8 == 0 && (uintptr_t)X % 16 == 0;
+    if (vec && vs_is16(xd)) {
+        const unsigned short* p = (const unsigned short*)X + n;
+#pragma unroll 4
+        for (int64_t r = g; r < M; r += 64) {
+            const u32x4 v = *reinterpret_cast<const u32x4*>(p + r * ldx);
+            const unsigned short* h = reinterpret_cast<const unsigned short*>(&v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += vs_h2f(h[e], xd);
+        }
+    } else if (vec && xd == VS_F32) {
+        const float* p = (const float*)X + n;
+#pragma unroll 4
+        for (int64_t r = g; r < M; r += 64) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(p + r * ldx), b = *reinterpret_cast<const f32x4*>(p + r * ldx + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { s[e] += a[e]; s[4 + e] += b[e]; }
+        }
+    } else if (n < N) {
+        for (int64_t r = g; r < M; r += 64)
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (n + e < N) s[e] += vs_ld(X, xd, r * ldx + n + e);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[g][8 * c8 + e] = s[e];
+    __syncthreads();
+    const int col = threadIdx.x;
+    if (col < CSR_COLS && n0 + col < N) {
+        float t = 0.f;
+        for (int q = 0; q < 64; ++q) t += part[q][col];
+        if (J.direct) J.out[j][n0 + col] = t;
+        else atomicAdd(J.out[j] + n0 + col, t);          // the one contribution to this element in this launch
+    }
+}
+
 // ---- fused frame losses: sum of squared errors of every decoded frame against its target frame ------------------------------
 // frames [B, G, D] fp32 (G frames per sample: the auto-encoding reconstruction followed by the n forecasts), full [B, T, D]
 // fp32 (all observed frames), idx[g] = index of the frame of `full` that frame g is compared with (device array, so the
@@ -916,19 +969,22 @@ extern "C" int vs_colsum_multi(int n_jobs, const void* const* X, const int* x_dt
     ColsumJobs J;
     J.nj = n_jobs;
     int64_t max_m = 0;
-    J.blk_off[0] = 0;
     for (int j = 0; j < n_jobs; ++j) {
         VS_CHECK_ARG(X[j] && out[j] && M[j] > 0 && N[j] > 0 && ldx[j] >= N[j], "vs_colsum_multi: bad job %d", j);
         J.x[j] = X[j]; J.dt[j] = x_dtype[j]; J.ld[j] = ldx[j]; J.M[j] = M[j]; J.N[j] = N[j]; J.out[j] = out[j];
-        J.blk_off[j + 1] = J.blk_off[j] + (int)vs_cdiv(N[j], CSM_COLS);
         if (M[j] > max_m) max_m = M[j];
     }
-    dim3 grid((unsigned)J.blk_off[n_jobs], (unsigned)vs_cdiv(max_m, CS_ROWS));
-    // Every job within ONE row block (the encoders' bias gradients: 256 rows) and the outputs tiling exactly the area this call is asked to
-    // clear: each column sum has one writer, so it is stored instead of added and the clearing launch is not issued (one kernel boundary
-    // less on the critical path of the WaveEq step's tail).
+    // within one row block: the row-block kernel (one block row); taller: the whole-column kernel (colsum_multi_rows_kernel).  Either way
+    // every column sum has exactly one writer.
+    const bool tall = max_m > CS_ROWS;
+    const int cols_per_blk = tall ? CSR_COLS : CSM_COLS;
+    J.blk_off[0] = 0;
+    for (int j = 0; j < n_jobs; ++j) J.blk_off[j + 1] = J.blk_off[j] + (int)vs_cdiv(N[j], cols_per_blk);
+    dim3 grid((unsigned)J.blk_off[n_jobs], 1u);
+    // The outputs tiling exactly the area this call is asked to clear: each column sum is stored instead of added and the clearing
+    // launch is not issued (one kernel boundary less on the critical path of the WaveEq step's tail).
     J.direct = 0;
-    if (zero_base && zero_count > 0 && grid.y == 1) {
+    if (zero_base && zero_count > 0) {
         int64_t cols = 0;
         bool inside = true;
         for (int j = 0; j < n_jobs; ++j) {
@@ -941,7 +997,8 @@ extern "C" int vs_colsum_multi(int n_jobs, const void* const* X, const int* x_dt
         if (vs_zero_async(zero_base, (size_t)zero_count * sizeof(float), (hipStream_t)stream) != hipSuccess)
             return vs_fail(VS_ERR_LAUNCH, "vs_colsum_multi: memset failed");
     }
-    hipLaunchKernelGGL(colsum_multi_kernel, grid, dim3(256), 0, (hipStream_t)stream, J);
+    if (tall) hipLaunchKernelGGL(colsum_multi_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, J);
+    else hipLaunchKernelGGL(colsum_multi_kernel, grid, dim3(256), 0, (hipStream_t)stream, J);
     VS_CHECK_LAUNCH("vs_colsum_multi");
     return VS_OK;
 }

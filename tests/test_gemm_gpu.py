@@ -233,6 +233,30 @@ def test_colsum_multi_shapes_and_dtypes():
         assert torch.allclose(o.double(), r, rtol=1e-5, atol=1e-3 * x.shape[0] ** 0.5 * 1e-2), (x.shape, (o.double() - r).abs().max().item())
 
 
+def test_colsum_multi_is_bitwise_repeatable():
+    """Jobs taller than one row block (the integrator's bias gradients: (steps - 1) * B rows) give the same bits on every launch, into
+    fresh vectors, into a cleared flat buffer and added to zeroed caller vectors: no sum depends on the order workgroups finish in."""
+    from spatiotemporal_variable_separation_amd import ops
+    from oracle.detdata import det_uniform
+    jobs = [(det_uniform((3072, n), 50 + i) - 0.5).to(dt).cuda()
+            for i, (n, dt) in enumerate([(512, torch.float32), (512, torch.bfloat16), (32, torch.float32), (520, torch.float32), (33, torch.bfloat16)])]
+    first = [o.clone() for o in ops.colsum_multi(jobs)]
+    for o, x in zip(first, jobs):
+        assert torch.allclose(o.double(), x.double().sum(0), rtol=1e-5, atol=1e-4)
+    for i in range(12):
+        if i % 3 == 0:
+            outs = ops.colsum_multi(jobs)
+        elif i % 3 == 1:
+            flat, views = ops.colsum_alloc(jobs)
+            flat.fill_(float('nan'))                              # cleared (or overwritten) by the launch itself
+            outs = ops.colsum_multi(jobs, outs=views, zero_flat=flat)
+        else:
+            outs = [torch.zeros_like(o) for o in first]
+            ops.colsum_multi(jobs, outs=outs)
+        for a, b in zip(outs, first):
+            assert torch.equal(a, b), (i, (a - b).abs().max().item())
+
+
 @pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('dims', [(3, 512, 32, 3072, 1, 1), (3, 512, 512, 3072, 1, 1), (2, 32, 512, 96, 1, 1), (4, 100, 72, 264, 0, 0),
                                   (5, 64, 40, 128, 0, 1)])

@@ -132,7 +132,7 @@ def test_bench_line_is_short_and_parses():
     import json
     spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
     bench = importlib.util.module_from_spec(spec)
-    saved = {k: os.environ.get(k) for k in ('GPU_MAX_HW_QUEUES', 'DEBUG_HIP_FORCE_GRAPH_QUEUES', 'VARSEP_PACKAGE_SET')}
+    saved = {k: os.environ.get(k) for k in ('GPU_MAX_HW_QUEUES', 'VARSEP_PACKAGE_SET')}
     try:
         spec.loader.exec_module(bench)
     finally:

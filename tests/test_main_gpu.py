@@ -42,7 +42,7 @@ def test_main_runs_the_step_bench_times(tmp_path):
     import re
     import shutil
     import torch
-    d = '/tmp/varsep_wave_fullsize/' + ''.join(chr(ord('a') + (os.getpid() // 26 ** k) % 26) for k in range(6))
+    d = '/tmp/varsep_wave_fullsize_' + ''.join(chr(ord('a') + (n // 26 ** k) % 26) for n in (os.getuid(), os.getpid()) for k in range(6))
     shutil.rmtree(d, ignore_errors=True)
     os.makedirs(os.path.join(d, 'data'))
     try:
@@ -62,7 +62,7 @@ def test_main_runs_the_step_bench_times(tmp_path):
         fps = [float(m) for m in re.findall(r'\| (\d+) frames/s \(hipGraph\)', r.stdout)]
         assert len(fps) >= 4, r.stdout[-2000:]
         main_ms = 128 * 20 / max(fps[1:]) * 1e3          # (the first interval contains the recording)
-        b = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', 'waveeq', '--no_cpu_baseline', '--extra_configs', 'none'],
+        b = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--config', 'waveeq', '--no_cpu_baseline', '--extra_configs', 'none'],
                            cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
         assert b.returncode == 0, b.stderr[-4000:]
         bench_ms = json.loads(b.stdout.strip().splitlines()[-1])['ms_per_step']
@@ -70,3 +70,20 @@ def test_main_runs_the_step_bench_times(tmp_path):
         assert main_ms <= 1.15 * bench_ms, (main_ms, bench_ms, fps)
     finally:
         shutil.rmtree(d, ignore_errors=True)
+
+
+def test_bench_dumps_the_same_outputs_every_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: two runs with the same arguments see the same inputs and write the same arrays, bit for bit (the loss the
+    last timed step returned and the state it left), so that two builds can be compared output for output."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = tmp_path / ('run%d' % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2', '--dump-outputs', str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-4000:]
+        runs.append({n: np.load(d / n) for n in ('loss.npy', 'state.npy')})
+    for n, a in runs[0].items():
+        b = runs[1][n]
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), '%s: %d of %d values differ between two runs' % (n, int((a != b).sum()), a.size)

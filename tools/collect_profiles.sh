@@ -41,5 +41,5 @@ for w in $wl; do
 done
 rm -rf $out/f $out/w
 # bench lines last: they pick up the replay / traffic tables once those are copied into profiles/ (run again after copying)
-python3 bench.py > $out/${tag}_bench_default.json 2> $out/bench_default.err
+python3 bench.py --full > $out/${tag}_bench_default.json 2> $out/bench_default.err
 ls -la $out

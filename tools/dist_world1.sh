@@ -7,7 +7,7 @@ wl=${@:-waveeq taxibj sst}
 line() { python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$1', '$2', d['ms_per_step'], 'ms', d['config']['grad_allreduce'])"; }
 for w in $wl; do
   for r in 1 2; do
-    python3 bench.py --config $w --extra_configs none --no_cpu_baseline --steps 10 2>/dev/null | line plain $w
-    VARSEP_BENCH_FORCE_DIST=1 python3 bench.py --config $w --extra_configs none --no_cpu_baseline --steps 10 2>/dev/null | line "N>1 path at world size 1 (RCCL)" $w
+    python3 bench.py --full --config $w --extra_configs none --no_cpu_baseline --steps 10 2>/dev/null | line plain $w
+    VARSEP_BENCH_FORCE_DIST=1 python3 bench.py --full --config $w --extra_configs none --no_cpu_baseline --steps 10 2>/dev/null | line "N>1 path at world size 1 (RCCL)" $w
   done
 done
