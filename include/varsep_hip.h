@@ -333,6 +333,25 @@ int vs_frame_metrics(const float* pred, const float* target, int64_t planes, int
 int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
                           int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream);
 
+/* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
+ * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
+ * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's
+ * top-left corner per frame (the (sx, sy) of the test file's `latents`); desc [n_videos, 1 + num_digits] int32 = (sequence, digit index of
+ * object 0 .. num_digits-1).  out [n_videos, seq_len, 1, frame, frame] (fp32 or a 16-bit type): sum of the digits, min(., 255) / 255, the
+ * arithmetic of vs_moving_mnist_batch.  A sequence / digit index out of range or a digit not wholly inside the frame is not drawn and sets
+ * *bad = 1 (bad may be NULL); the launch never reads or writes out of bounds.                                                          */
+int vs_moving_mnist_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions, int n_seq,
+                          int num_digits, const int32_t* desc, int n_videos, int seq_len, int frame_size, void* out, int out_dtype,
+                          int32_t* bad, void* stream);
+/* vs_frame_metrics of one prediction against n_targets candidates: pred [batch, planes_per_sample, H, W] fp32, targets [batch, n_targets,
+ * planes_per_sample, H, W] fp32 -> mse / ssim [batch, n_targets, planes_per_sample] (either may be NULL).  Same window, constants and
+ * operation order as vs_frame_metrics; each prediction plane is staged in LDS once for all its targets.  Planes up to ~80 x 80.      */
+int vs_frame_metrics_multi(const float* pred, const float* targets, int64_t batch, int n_targets, int64_t planes_per_sample, int H, int W,
+                           float max_val, float k1, float k2, float sigma, float* mse, float* ssim, void* stream);
+/* x [n, channels, hw] (fp32 or a 16-bit type, widened to fp32) -> out [n, hw, channels] uint8 = (uint8)(x * 255.f): one fp32 multiply,
+ * truncation toward zero (torch's `x.mul(255).byte()` for x in [0, 1]); values outside [0, 255] after the multiply saturate, NaN -> 0. */
+int vs_frames_to_u8_nhwc(const void* x, int x_dtype, int64_t n, int channels, int64_t hw, uint8_t* out, void* stream);
+
 /* Decoder input of the auto-encoding pair and of every rollout step in one launch (mlp_encdec.py:43-48 mixing applied at
  * model.py:74-83): z [B, 1+n, Cz] = mix(s [B, Cs], [t_rand [B, Ct] ; t_codes [B, n, Ct]]), mixing 0 = concat (Cz = Cs + Ct),
  * 1 = mul (Cz = Cs = Ct); out fp32, out_bf16 (may be NULL) the same values rounded for the decoder's first bf16 GEMM.

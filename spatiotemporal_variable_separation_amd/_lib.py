@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(_HERE, 'libvarsep_hip.so')
 SOURCES = ['vs_gemm.hip', 'vs_eltwise.hip', 'vs_conv.hip', 'vs_rollout.hip', 'vs_norm.hip', 'vs_optim.hip', 'vs_data.hip', 'vs_conv_tap.hip', 'vs_metrics.hip', 'vs_conv_img.hip', 'vs_conv_k4s2.hip',
-           'vs_conv_thin.hip', 'vs_conv_band2.hip', 'vs_conv_wgrad2.hip']
+           'vs_conv_thin.hip', 'vs_conv_band2.hip', 'vs_conv_wgrad2.hip', 'vs_eval.hip']
 
 F32, BF16, F16 = 0, 1, 2
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -162,6 +162,9 @@ SIGNATURES = {
     'vs_conv2d_dgrad': (_i32, [_i32, _vp, _vp, _vp, _i32] + [_i32] * 9 + [_vp, _sz, _vp]),
     'vs_conv2d_wgrad': (_i32, [_i32, _vp, _vp, _vp] + [_i32] * 9 + [_vp, _sz, _vp]),
     'vs_frame_metrics': (_i32, [_vp, _vp, _i64, _i32, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
+    'vs_moving_mnist_place': (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    'vs_frame_metrics_multi': (_i32, [_vp, _vp, _i64, _i32, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    'vs_frames_to_u8_nhwc': (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp]),
     'vs_conv3_img16_supported': (_i32, [_i32] * 6),
     'vs_conv3_img16_splits': (_i32, [_i32] * 3),
     'vs_conv3_img16_packed_elems': (_sz, [_i32, _i32]),

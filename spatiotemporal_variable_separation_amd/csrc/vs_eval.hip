@@ -1,0 +1,215 @@
+// vs_eval.hip -- the device side of the evaluation scripts (reference: test/mnist/test.py, test/mnist/test_disentanglement.py).
+//
+//   * vs_moving_mnist_place: the content-swap videos of `SwapDataset.__getitem__` (test_disentanglement.py:66-86).  Digits are added at
+//     the test file's stored trajectory positions (no bouncing to replay), clipped at 255 and divided by 255 -- the arithmetic of
+//     moving_mnist_kernel (vs_data.hip), so the frames are bit-identical to NumPy's `x[...] += img; x[x > 255] = 255; x / 255`.  One
+//     launch renders a whole batch of B x (1 + n!) videos; the host only builds the [V, 1 + nd] descriptor table.
+//   * vs_frame_metrics_multi: per-plane MSE and mean SSIM of one prediction against P candidate targets (the best-of-permutations
+//     scoring of test_disentanglement.py:153-161).  The window, constants and operation order are those of frame_metrics_kernel
+//     (vs_metrics.hip); the prediction plane and its two row-filtered maps stay in LDS across all P targets.
+//   * vs_frames_to_u8_nhwc: `x.mul(255).byte().permute(0, 1, 3, 4, 2)` of every saved sample, on the device, so that only uint8 bytes
+//     cross PCIe.
+#include "vs_common.h"
+
+namespace {
+
+constexpr int PL_MAXD = 8;           // digits per video
+constexpr int MM_WIN = 11;           // SSIM window (vs_metrics.hip)
+
+struct MmWindow { float g[MM_WIN]; };
+
+// grid (T, V): one workgroup per frame.  pos [Tp][n_seq][nd][2] = (row, column) of each object's top-left corner; desc [V][1 + nd] =
+// (sequence, digit of object 0 .. nd-1).  A sequence or digit index out of range, or a digit that would not lie inside the frame, is
+// not drawn and raises *bad (if given): nothing is read or written out of bounds.
+__global__ __launch_bounds__(256) void place_kernel(const unsigned char* __restrict__ digits, int64_t n_digits, int dh, int dw,
+                                                    const int* __restrict__ pos, int n_seq, int nd, const int* __restrict__ desc, int T, int F,
+                                                    void* out, int od, int* bad) {
+    __shared__ int sp[PL_MAXD][3];       // digit index, row offset, column offset (digit index -1: not drawn)
+    const int t = blockIdx.x, v = blockIdx.y;
+    if ((int)threadIdx.x < nd) {
+        const int d = threadIdx.x;
+        const int* q = desc + (int64_t)v * (1 + nd);
+        const int seq = q[0], dig = q[1 + d];
+        int ok = seq >= 0 && seq < n_seq && dig >= 0 && (int64_t)dig < n_digits;
+        int sx = 0, sy = 0;
+        if (ok) {
+            const int* p = pos + (((int64_t)t * n_seq + seq) * nd + d) * 2;
+            sx = p[0]; sy = p[1];
+            ok = sx >= 0 && sy >= 0 && sx + dh <= F && sy + dw <= F;
+        }
+        if (!ok && bad) *bad = 1;
+        sp[d][0] = ok ? dig : -1; sp[d][1] = sx; sp[d][2] = sy;
+    }
+    __syncthreads();
+    const int64_t base = ((int64_t)v * T + t) * F * F;
+    for (int i = threadIdx.x; i < F * F; i += 256) {
+        const int r = i / F, c = i - r * F;
+        float acc = 0.f;
+        for (int d = 0; d < nd; ++d) {
+            const int rr = r - sp[d][1], cc = c - sp[d][2];
+            if (sp[d][0] >= 0 && rr >= 0 && rr < dh && cc >= 0 && cc < dw) acc += (float)digits[((int64_t)sp[d][0] * dh + rr) * dw + cc];
+        }
+        acc = acc > 255.f ? 255.f : acc;
+        vs_st(out, od, base + i, acc / 255.f);
+    }
+}
+
+// one workgroup per prediction plane; loops over the P targets of that plane.  LDS: the prediction [H][W], one target [H][W], the
+// prediction's two row-filtered maps (mu, E[x^2]) [2][H][OW] and the target's three (mu, E[y^2], E[xy]) [3][H][OW] -- the footprint of
+// frame_metrics_kernel.  pred [planes] with planes = B * TC; targets [B][P][TC][H][W]; outputs [B][P][TC].
+__global__ __launch_bounds__(256) void frame_metrics_multi_kernel(const float* pred, const float* targets, int P, int64_t tc, int H, int W,
+                                                                  MmWindow win, float c1, float c2, float* mse, float* ssim) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int64_t plane = blockIdx.x;
+    const int64_t b = plane / tc, k = plane - b * tc;
+    const int hw = H * W, OW = W - MM_WIN + 1, OH = H - MM_WIN + 1, nh = H * OW, no = OH * OW;
+    float* sx = smem;                      // [H][W]
+    float* sy = smem + hw;                 // [H][W]
+    float* hx = smem + 2 * hw;             // [2][H][OW]: mu_x, E[x^2]
+    float* hy = hx + 2 * nh;               // [3][H][OW]: mu_y, E[y^2], E[xy]
+    __shared__ float red[2][4];
+    const float* px = pred + plane * hw;
+    for (int i = threadIdx.x; i < hw; i += 256) sx[i] = px[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < nh; i += 256) {
+        const int r = i / OW, c = i - r * OW;
+        float m1 = 0.f, q1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < MM_WIN; ++j) {
+            const float a = sx[r * W + c + j], g = win.g[j];
+            m1 += g * a; q1 += g * (a * a);
+        }
+        hx[i] = m1; hx[nh + i] = q1;
+    }
+    for (int p = 0; p < P; ++p) {
+        const int64_t o = (b * P + p) * tc + k;
+        const float* py = targets + o * hw;
+        float se = 0.f;
+        for (int i = threadIdx.x; i < hw; i += 256) {
+            const float a = sx[i], bb = py[i];
+            sy[i] = bb;
+            const float d = a - bb;
+            se += d * d;
+        }
+        __syncthreads();                   // sy complete (and, for p = 0, hx); the previous target's readers of hy / red are done
+        for (int i = threadIdx.x; i < nh; i += 256) {
+            const int r = i / OW, c = i - r * OW;
+            float m2 = 0.f, q2 = 0.f, q12 = 0.f;
+#pragma unroll
+            for (int j = 0; j < MM_WIN; ++j) {
+                const float a = sx[r * W + c + j], bb = sy[r * W + c + j], g = win.g[j];
+                m2 += g * bb; q2 += g * (bb * bb); q12 += g * (a * bb);
+            }
+            hy[i] = m2; hy[nh + i] = q2; hy[2 * nh + i] = q12;
+        }
+        __syncthreads();
+        float acc = 0.f;
+        for (int i = threadIdx.x; i < no; i += 256) {
+            const int r = i / OW, c = i - r * OW;
+            float m1 = 0.f, m2 = 0.f, q1 = 0.f, q2 = 0.f, q12 = 0.f;
+#pragma unroll
+            for (int j = 0; j < MM_WIN; ++j) {
+                const int kk = (r + j) * OW + c;
+                const float g = win.g[j];
+                m1 += g * hx[kk]; m2 += g * hy[kk]; q1 += g * hx[nh + kk]; q2 += g * hy[nh + kk]; q12 += g * hy[2 * nh + kk];
+            }
+            const float mu1_sq = m1 * m1, mu2_sq = m2 * m2, mu12 = m1 * m2;
+            const float v1 = 2.f * (q12 - mu12) + c2, v2 = (q1 - mu1_sq) + (q2 - mu2_sq) + c2;
+            acc += ((2.f * mu12 + c1) * v1) / ((mu1_sq + mu2_sq + c1) * v2);
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) { se += __shfl_down(se, s, 64); acc += __shfl_down(acc, s, 64); }
+        if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = se; red[1][threadIdx.x >> 6] = acc; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (mse) mse[o] = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (float)hw;
+            if (ssim) ssim[o] = no > 0 ? (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / (float)no : 0.f;
+        }
+        // the next target's first barrier orders these reads of red before its writes
+    }
+}
+
+__device__ __forceinline__ unsigned int to_u8(float x) {
+    const float y = __fmul_rn(x, 255.f);             // one rounded multiply, never contracted
+    if (!(y > 0.f)) return 0u;                       // negatives, -0 and NaN
+    if (y >= 255.f) return 255u;
+    return (unsigned int)y;                          // truncation toward zero, as static_cast<uint8_t>
+}
+
+// x [N][C][HW] -> out [N][HW][C]; every thread writes four consecutive output bytes (one 32-bit store when n_out % 4 == 0)
+__global__ __launch_bounds__(256) void to_u8_nhwc_kernel(const void* x, int xd, int64_t N, int C, int64_t HW, unsigned char* out) {
+    const int64_t n_out = N * C * HW, n4 = (n_out + 3) / 4;
+    const int64_t chw = (int64_t)C * HW;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
+        unsigned int packed = 0u;
+        const int64_t o0 = q * 4;
+        const int cnt = n_out - o0 < 4 ? (int)(n_out - o0) : 4;
+        for (int e = 0; e < cnt; ++e) {
+            const int64_t o = o0 + e;
+            const int64_t n = o / chw, rem = o - n * chw;
+            const int64_t pix = rem / C, c = rem - pix * C;
+            packed |= to_u8(vs_ld(x, xd, n * chw + c * HW + pix)) << (8 * e);
+        }
+        if (cnt == 4 && (n_out & 3) == 0) {
+            reinterpret_cast<unsigned int*>(out)[q] = packed;
+        } else {
+            for (int e = 0; e < cnt; ++e) out[o0 + e] = (unsigned char)(packed >> (8 * e));
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int vs_moving_mnist_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions, int n_seq,
+                                     int num_digits, const int32_t* desc, int n_videos, int seq_len, int frame_size, void* out, int out_dtype,
+                                     int32_t* bad, void* stream) {
+    VS_CHECK_ARG(digits && positions && desc && out && n_digits_total > 0 && digit_h > 0 && digit_w > 0 && n_seq > 0 && n_videos > 0 && seq_len > 0,
+                 "vs_moving_mnist_place: bad argument");
+    VS_CHECK_ARG(n_videos < 65536 && seq_len < (1 << 30), "vs_moving_mnist_place: at most 65535 videos per launch");
+    VS_CHECK_ARG(num_digits >= 1 && num_digits <= PL_MAXD, "vs_moving_mnist_place: 1..%d digits per video", PL_MAXD);
+    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "vs_moving_mnist_place: the digit does not fit the frame");
+    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "vs_moving_mnist_place: bad out_dtype");
+    hipLaunchKernelGGL(place_kernel, dim3((unsigned)seq_len, (unsigned)n_videos), dim3(256), 0, (hipStream_t)stream, digits, n_digits_total, digit_h,
+                       digit_w, positions, n_seq, num_digits, desc, seq_len, frame_size, out, out_dtype, (int*)bad);
+    VS_CHECK_LAUNCH("vs_moving_mnist_place");
+    return VS_OK;
+}
+
+extern "C" int vs_frame_metrics_multi(const float* pred, const float* targets, int64_t batch, int n_targets, int64_t planes_per_sample, int H, int W,
+                                      float max_val, float k1, float k2, float sigma, float* mse, float* ssim, void* stream) {
+    VS_CHECK_ARG(pred && targets && batch > 0 && n_targets > 0 && planes_per_sample > 0 && batch * planes_per_sample < (1ll << 31) && H >= MM_WIN &&
+                     W >= MM_WIN && (mse || ssim),
+                 "vs_frame_metrics_multi: bad argument");
+    const size_t lds = ((size_t)2 * H * W + (size_t)5 * H * (W - MM_WIN + 1)) * sizeof(float);
+    if (lds > 150 * 1024)
+        return vs_fail(VS_ERR_UNSUPPORTED, "vs_frame_metrics_multi: planes of %d x %d do not fit the LDS (<= 64 x 64 .. 80 x 80)", H, W);
+    MmWindow win;                                    // the window of vs_frame_metrics
+    double sum = 0.0, e[MM_WIN];
+    for (int j = 0; j < MM_WIN; ++j) {
+        const double x = (double)j - (MM_WIN - 1) / 2.0;
+        e[j] = exp(-x * x / (2.0 * (double)sigma * (double)sigma));
+        sum += e[j];
+    }
+    for (int j = 0; j < MM_WIN; ++j) win.g[j] = (float)(e[j] / sum);
+    const float c1 = (k1 * max_val) * (k1 * max_val), c2 = (k2 * max_val) * (k2 * max_val);
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)frame_metrics_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
+            return vs_fail(VS_ERR_LAUNCH, "vs_frame_metrics_multi: cannot raise the dynamic LDS limit");
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(frame_metrics_multi_kernel, dim3((unsigned)(batch * planes_per_sample)), dim3(256), lds, (hipStream_t)stream, pred, targets,
+                       n_targets, planes_per_sample, H, W, win, c1, c2, mse, ssim);
+    VS_CHECK_LAUNCH("vs_frame_metrics_multi");
+    return VS_OK;
+}
+
+extern "C" int vs_frames_to_u8_nhwc(const void* x, int x_dtype, int64_t n, int channels, int64_t hw, uint8_t* out, void* stream) {
+    VS_CHECK_ARG(x && out && n > 0 && channels > 0 && hw > 0, "vs_frames_to_u8_nhwc: bad argument");
+    VS_CHECK_ARG(vs_dtype_ok(x_dtype), "vs_frames_to_u8_nhwc: bad x_dtype");
+    const int64_t n4 = (n * channels * hw + 3) / 4;
+    const unsigned blocks = (unsigned)(vs_cdiv(n4, 256) < 2048 ? vs_cdiv(n4, 256) : 2048);
+    hipLaunchKernelGGL(to_u8_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, x_dtype, n, channels, hw, out);
+    VS_CHECK_LAUNCH("vs_frames_to_u8_nhwc");
+    return VS_OK;
+}

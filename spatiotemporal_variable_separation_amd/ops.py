@@ -2101,3 +2101,62 @@ def frame_metrics(pred, target, max_val=1.0, k1=0.01, k2=0.03, sigma=1.5, want_s
     check(_lib.load_library().vs_frame_metrics(p.data_ptr(), t.data_ptr(), p.shape[0], H, W, float(max_val), float(k1), float(k2), float(sigma),
                                                mse.data_ptr(), _ptr(ssim), stream_ptr()), 'vs_frame_metrics')
     return mse.view(lead), (ssim.view(lead) if want_ssim else None)
+
+
+def frame_metrics_multi(pred, targets, max_val=1.0, k1=0.01, k2=0.03, sigma=1.5, want_mse=True, want_ssim=True):
+    """pred [B, ..., H, W] fp32 against targets [B, P, ..., H, W] fp32: per-plane (mse, mean SSIM) of shape [B, P, ...]
+    (vs_frame_metrics_multi; vs_frame_metrics against each of the P targets, with the prediction staged once)."""
+    require_cuda(pred, targets)
+    if targets.dim() != pred.dim() + 1 or targets.shape[0] != pred.shape[0] or targets.shape[2:] != pred.shape[1:] or pred.dim() < 3:
+        raise _lib.VarsepHipError('frame_metrics_multi: targets must be [B, P] + pred.shape[1:] (got %s and %s)'
+                                  % (tuple(pred.shape), tuple(targets.shape)))
+    B, P, H, W = pred.shape[0], targets.shape[1], pred.shape[-2], pred.shape[-1]
+    lead = tuple(pred.shape[1:-2])
+    per = 1
+    for d in lead:
+        per *= d
+    p = pred.float().contiguous()
+    t = targets.float().contiguous()
+    mse = torch.empty((B, P) + lead, dtype=torch.float32, device=p.device) if want_mse else None
+    ssim = torch.empty((B, P) + lead, dtype=torch.float32, device=p.device) if want_ssim else None
+    check(_lib.load_library().vs_frame_metrics_multi(p.data_ptr(), t.data_ptr(), B, P, per, H, W, float(max_val), float(k1), float(k2), float(sigma),
+                                                     _ptr(mse), _ptr(ssim), stream_ptr()), 'vs_frame_metrics_multi')
+    return mse, ssim
+
+
+def moving_mnist_place(digits, positions, desc, seq_len, frame_size, out_dtype=torch.float32, validate=True):
+    """Videos [V, seq_len, 1, F, F] with the digits `desc[v, 1 + i]` at `positions[t, desc[v, 0], i]` (vs_moving_mnist_place).
+    digits uint8 [N, h, w], positions int32 [T >= seq_len, n_seq, nd, 2], desc int32 [V, 1 + nd], all on the device.
+    validate=True reads back the launch's error word (a host sync) and raises VarsepHipError for an index out of range or a digit that
+    would be cut at the frame border; validate=False keeps the call free of host syncs (the caller has checked the table)."""
+    require_cuda(digits, positions, desc)
+    if digits.dtype != torch.uint8 or digits.dim() != 3 or positions.dtype != torch.int32 or positions.dim() != 4 or positions.shape[3] != 2 \
+            or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 1 + positions.shape[2] or positions.shape[0] < seq_len:
+        raise _lib.VarsepHipError('moving_mnist_place: digits uint8 [N, h, w], positions int32 [T >= seq_len, n_seq, nd, 2], '
+                                  'desc int32 [V, 1 + nd] expected')
+    digits, positions, desc = digits.contiguous(), positions.contiguous(), desc.contiguous()
+    V, nd = desc.shape[0], positions.shape[2]
+    out = torch.empty((V, seq_len, 1, frame_size, frame_size), dtype=out_dtype, device=digits.device)
+    bad = torch.zeros((1,), dtype=torch.int32, device=digits.device) if validate else None
+    check(_lib.load_library().vs_moving_mnist_place(digits.data_ptr(), digits.shape[0], digits.shape[1], digits.shape[2], positions.data_ptr(),
+                                                    positions.shape[1], nd, desc.data_ptr(), V, seq_len, frame_size, out.data_ptr(),
+                                                    dtype_code(out), _ptr(bad), stream_ptr()), 'vs_moving_mnist_place')
+    if validate and int(bad.item()):
+        raise _lib.VarsepHipError('moving_mnist_place: a sequence / digit index is out of range or a digit does not lie inside the '
+                                  '%d x %d frame' % (frame_size, frame_size))
+    return out
+
+
+def frames_to_u8_nhwc(x):
+    """[B, T, C, H, W] fp32 / 16-bit -> uint8 [B, T, H, W, C] on the device: (uint8)(x * 255.f), i.e. `x.mul(255).byte().permute(0, 1, 3, 4, 2)`
+    bit for bit for x in [0, 1]; out-of-range values saturate to 0 / 255 (NaN -> 0) where torch's cast is undefined (vs_frames_to_u8_nhwc)."""
+    require_cuda(x)
+    if x.dim() != 5:
+        raise _lib.VarsepHipError('frames_to_u8_nhwc: [B, T, C, H, W] expected (got %s)' % (tuple(x.shape),))
+    B, T, C, H, W = x.shape
+    x = x.contiguous()
+    out = torch.empty((B, T, H, W, C), dtype=torch.uint8, device=x.device)
+    if out.numel():
+        check(_lib.load_library().vs_frames_to_u8_nhwc(x.data_ptr(), dtype_code(x), B * T, C, H * W, out.data_ptr(), stream_ptr()),
+              'vs_frames_to_u8_nhwc')
+    return out

@@ -1,0 +1,113 @@
+"""Moving-MNIST evaluation (reference: test/mnist/test.py:50-188, same flags and output files):
+
+    python -m spatiotemporal_variable_separation_amd.test.mnist.test --xp_dir X --data_dir D --nt_pred 95 --device 0
+
+Forecasts the test set (MSE / PSNR / SSIM per sample, printed as the reference's `Results:` block) and a content swap: the S code of
+each test video drives a forecast from a freshly generated training video.  The test set lives in HBM, the swap videos are rendered by
+the device generator from the global NumPy stream in the reference's order, the metrics run on the device (vs_frame_metrics) and every
+saved array is converted to uint8 on the device (vs_frames_to_u8_nhwc).  There is no CPU mode: --device is required.
+"""
+import os
+
+import numpy as np
+import torch
+
+from ...data.moving_mnist import MovingMNIST
+from ...utils.helper import load_json
+from ...utils.metrics import frame_metrics
+from ..utils import add_precision_flag, base_parser, load_model, print_results, seed_all, setup_device, to_host_u8
+
+
+def load_dataset(args, train=False, device='cuda'):
+    return MovingMNIST.make_dataset(args.data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, train,
+                                    device=device)
+
+
+def test_batches(test_dataset, batch_size):
+    """`DataLoader(test_dataset, batch_size)` over the HBM-resident test videos: (cond, target) slices of each batch.  The frames are
+    divided by a device scalar: a true division like the reference's host `/ 255` (a Python-number divisor would become a multiplication
+    by the reciprocal on the GPU)."""
+    data = test_dataset.data
+    d255 = torch.tensor(255., dtype=data.dtype, device=data.device)
+    nt_cond, seq_len = test_dataset.nt_cond, test_dataset.seq_len
+    for start in range(0, data.shape[0], batch_size):
+        v = data[start:start + batch_size]
+        yield v[:, :nt_cond].div(d255), v[:, nt_cond:seq_len].div(d255)
+
+
+def main(args):
+    device = setup_device(args)
+    seed_all(args.test_seed)
+    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
+    xp_config.device = device
+    xp_config.data_dir = args.data_dir
+    xp_config.xp_dir = args.xp_dir
+    xp_config.nt_pred = args.nt_pred
+
+    print('Loading data...')
+    test_dataset = load_dataset(xp_config, train=False, device=device)
+    train_dataset = load_dataset(xp_config, train=True, device=device)
+    nc = 1
+    size = 64
+
+    print('Loading model...')
+    sep_net = load_model(xp_config, args.epoch)
+
+    print('Generating samples...')
+    torch.set_grad_enabled(False)
+    nt_test = xp_config.nt_cond + args.nt_pred
+    predictions, content_swap, cond_swap, target_swap, cond, gt = [], [], [], [], [], []
+    results = {'mse': [], 'psnr': [], 'ssim': []}
+    for x_cond, x_target in test_batches(test_dataset, args.batch_size):
+        bsz = len(x_cond)
+        cond.append(to_host_u8(x_cond))
+        gt.append(to_host_u8(x_target))
+
+        # Prediction
+        x_pred, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
+        x_pred = x_pred[:, xp_config.nt_cond:]
+
+        # Content swap.  The reference's sequential DataLoader over the training set yields a full batch even when the test batch is
+        # ragged; the batch is drawn whole (same NumPy draws) and sliced.  With skip connections the reference hands the already unpacked
+        # `s_code` back as init_s_code (model.py:57-62); that is kept as it is.
+        x_swap_cond, x_swap_target = train_dataset.batch(args.batch_size)
+        x_swap_cond = x_swap_cond[:bsz]
+        x_swap_target = x_swap_target[:bsz]
+        cond_swap.append(to_host_u8(x_swap_cond))
+        target_swap.append(to_host_u8(x_swap_target))
+        x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
+        # reference quirk: `xp_config.dt` is not in params.json and DotDict reads a missing key as None, so this slice keeps all
+        # nt_cond + nt_pred frames
+        x_swap_pred = x_swap_pred[:, xp_config.dt:]
+        content_swap.append(to_host_u8(x_swap_pred))
+
+        # Pixelwise quantitative eval
+        x_target = x_target.reshape(-1, args.nt_pred, nc, size, size)
+        metrics_batch = frame_metrics(x_pred.float().contiguous(), x_target)
+        predictions.append(to_host_u8(x_pred))
+        for name in results:
+            results[name].append(metrics_batch[name].cpu())
+
+    results = print_results(results)
+
+    np.savez_compressed(os.path.join(args.xp_dir, 'results.npz'), **results)
+    np.savez_compressed(os.path.join(args.xp_dir, 'predictions.npz'), predictions=torch.cat(predictions).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'gt.npz'), gt=torch.cat(gt).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'cond.npz'), cond=torch.cat(cond).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap.npz'), content_swap=torch.cat(content_swap).numpy())
+    # reference quirk: the swap conditioning frames are stored under the key `target_swap`
+    np.savez_compressed(os.path.join(args.xp_dir, 'cond_swap.npz'), target_swap=torch.cat(cond_swap).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'target_swap.npz'), target_swap=torch.cat(target_swap).numpy())
+    return results
+
+
+def build_parser():
+    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST testing)', batch_size=16)
+    p.add_argument('--test_seed', type=int, metavar='SEED', default=1,
+                   help='Manual seed.')
+    add_precision_flag(p)
+    return p
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())
