@@ -616,8 +616,7 @@ inline int64_t cols_pitch(int64_t npix) { return (npix + CTraits<CT>::U - 1) / C
 // when the column matrix pays: enough output channels that the contraction dominates the extra HBM pass
 inline bool cols_worthwhile(int64_t M, int64_t npix, int64_t nq) {
     if (getenv("VS_CONV_COLS_FORCE")) return M > 4 && nq <= 65535;      // test aid: the column-matrix form at any size
-    static const int64_t min_work = getenv("VS_CONV_COLS_MIN") ? atoll(getenv("VS_CONV_COLS_MIN")) : ((int64_t)1 << 20);
-    return M >= 64 && npix * nq >= min_work && nq <= 65535;
+    return M >= 64 && npix * nq >= ((int64_t)1 << 20) && nq <= 65535;
 }
 
 template <int CT>
@@ -627,7 +626,7 @@ int materialise(const TapGather<CT>& gth, void* ws, hipStream_t st, const char* 
     int64_t bx = (units + 255) / 256;
     if (bx > 1024) bx = 1024;
     if constexpr (CT != VS_F32) {
-        if (s1_w4_ok(gth.g, gth.npix, gth.src) && getenv("VS_IM2COL_W4") == nullptr) {
+        if (s1_w4_ok(gth.g, gth.npix, gth.src)) {
             const int64_t maps = gth.npix / 16;
             int64_t bm = (maps + 255) / 256;
             if (bm > 1024) bm = 1024;
@@ -635,7 +634,7 @@ int materialise(const TapGather<CT>& gth, void* ws, hipStream_t st, const char* 
             VS_CHECK_LAUNCH(what);
             return VS_OK;
         }
-        if (k4s2_w8_ok(gth.g, gth.npix, gth.src) && getenv("VS_IM2COL_W4") == nullptr) {
+        if (k4s2_w8_ok(gth.g, gth.npix, gth.src)) {
             const int64_t maps = gth.npix / 16;
             int64_t bm = (maps + 255) / 256;
             if (bm > 1024) bm = 1024;
@@ -736,7 +735,7 @@ int gather_gemm(const void* src, const void* wd, const float* bias, void* out, i
     if (scat != 1 || g.GH != OH || g.GW != OW) {
         e.g_w = g.GW; e.g_hw = g.GH * g.GW; e.o_w = OW; e.sy = scat; e.sx = scat; e.oy = oy; e.ox = ox;
     }
-    if (M <= 2 && s1_fast_ok(b.gather.g, N, src) && getenv("VS_CONV_SMALL") == nullptr) {
+    if (M <= 2 && s1_fast_ok(b.gather.g, N, src)) {
         SmallTaps tp;
         for (int d = 0; d < 3; ++d)
             for (int e2 = 0; e2 < 3; ++e2) tp.idx[d][e2] = -1;
@@ -765,10 +764,9 @@ int gather_gemm(const void* src, const void* wd, const float* bias, void* out, i
         if constexpr (CT != VS_F32) {
             // many 128-wide pixel tiles, >= 96 output channels: the 128x128 LDS-DMA ring tile (weights R, column matrix S, NCHW epilogue
             // with 8-byte / 16-byte stores along the pixels)
-            static const int mid_mode = getenv("VS_CONV_FWD_MID") ? atoi(getenv("VS_CONV_FWD_MID")) : 1;
             const int64_t kt = vs_cdiv(K, BIG_BK), tiles = vs_cdiv((int64_t)M, 128) * vs_cdiv(N, 128);
-            if (mid_mode && e.g_hw == 0 && K % 8 == 0 && N % 8 == 0 && (uintptr_t)wd % 16 == 0 && K < (1ll << 23) && ld < (1ll << 23) &&
-                kt >= 8 && tiles >= 192 && (M >= 96 || mid_mode == 2)) {
+            if (e.g_hw == 0 && K % 8 == 0 && N % 8 == 0 && (uintptr_t)wd % 16 == 0 && K < (1ll << 23) && ld < (1ll << 23) &&
+                kt >= 8 && tiles >= 192 && M >= 96) {
                 int rc2 = mid_launch<CT, LR, LS, true>(wd, K, ws, ld, M, N, K, 1, kt, 5, 1, e, nullptr, st, 0);
                 if (rc2 != VS_OK) return rc2;
                 VS_CHECK_LAUNCH(what);
@@ -907,8 +905,7 @@ int transposed_form(const void* src, const void* wp, const float* bias, void* ou
         return gather_gemm<CT>(src, wp, bias, out, out_dtype, M, g, OH, OW, 1, 0, 0, ws, ws_bytes, st, what);
     }
     if (!phase_ok(kh, kw, s, p)) return vs_fail(VS_ERR_UNSUPPORTED, "%s: transposed geometry k%d s%d p%d is not supported", what, kh, s, p);
-    if (kh == 4 && kw == 4 && p == 1 && M <= 4 && W % 8 == 0 && OH == 2 * H && OW == 2 * W && (uintptr_t)src % 16 == 0 &&
-        getenv("VS_CONVT_SMALL") == nullptr) {
+    if (kh == 4 && kw == 4 && p == 1 && M <= 4 && W % 8 == 0 && OH == 2 * H && OW == 2 * W && (uintptr_t)src % 16 == 0) {
         const int64_t units = (int64_t)B * H * (W / 8);
         int64_t blocks = (units + 255) / 256;
         if (blocks > 16384) blocks = 16384;
@@ -994,13 +991,12 @@ int wgrad_form(const void* r, const void* gsrc, float* dw, int B, int Cr, int PH
             // the 128x128 LDS-DMA ring tile (vs_gemm_mid.h) with dy as a channel-rows operand: planes of a multiple of 32 pixels (a K
             // tile never straddles two images), split-K over the batch x pixel axis into slabs; 2x the register-staged tile on the
             // DCGAN / VGG weight gradients (K = 10^4 .. 10^5, 16-64 output tiles)
-            static const int mid_mode = getenv("VS_CONV_WGRAD_MID") ? atoi(getenv("VS_CONV_WGRAD_MID")) : 1;
             const int64_t kt = K / BIG_BK, tiles = vs_cdiv(M, 128) * vs_cdiv(N, 128);
             // maps of 8 / 16 pixels (hw not a multiple of the K tile): the same kernel on a dense [M][K] copy of R (one small transposing pass)
             const bool via_dense = hw % BIG_BK != 0 && hw % 8 == 0;
             const size_t dense_bytes = via_dense ? (size_t)M * (size_t)K * sizeof(T) : 0;
-            if (mid_mode && (hw % BIG_BK == 0 || via_dense) && K % BIG_BK == 0 && M % 8 == 0 && N % 8 == 0 && (uintptr_t)r % 16 == 0 && hw < (1ll << 23) &&
-                ld < (1ll << 23) && K < (1ll << 23) && kt >= 32 && tiles <= 512 && (M >= 64 || mid_mode == 2)) {
+            if ((hw % BIG_BK == 0 || via_dense) && K % BIG_BK == 0 && M % 8 == 0 && N % 8 == 0 && (uintptr_t)r % 16 == 0 && hw < (1ll << 23) &&
+                ld < (1ll << 23) && K < (1ll << 23) && kt >= 32 && tiles <= 512 && M >= 64) {
                 int splits = 1;
                 if (tiles < 448) {
                     splits = (int)(448 / tiles);

@@ -26,7 +26,6 @@
 // WM = 1: 256 threads, a wave owns 32 output channels x 64 pixels, two workgroups per CU; WM = 2: 512 threads = 2 x 4 waves, 64 output
 // channels x 256 pixels per workgroup (the pixel image is staged once for both channel tiles), one workgroup per CU.
 #include "vs_gemm_glds.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -71,12 +70,8 @@ __device__ __forceinline__ void b2_dma(uint32_t lds_dst, const void* sbase, uint
 template <int CT, int W, int WM, int K4, int KC>
 __global__ __launch_bounds__(256 * WM, 2) void conv3_band2_kernel(const unsigned short* __restrict__ X, const unsigned short* __restrict__ Wp,
                                                                  const float* __restrict__ bias, void* __restrict__ Y, int yd, int B, int Creal, int H, int Cout,
-                                                                 int mgroups, int bands, int ntiles, int chunks_total, int nph, int stagger) {
+                                                                 int mgroups, int bands, int ntiles, int chunks_total, int nph) {
     typedef B2Geo<W, KC> G;
-    // VS_BAND2_STAGGER=k (an experiment, default 0): the second half of the grid -- under round-robin placement the second workgroup of every CU -- starts
-    // k x 1024 cycles late, so that the two co-resident workgroups do not meet at the matrix pipe and at the LDS in lockstep
-    if (stagger > 0 && (int)blockIdx.x >= ((int)gridDim.x >> 1))
-        for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(16);
     constexpr int NTHR = 256 * WM;
     constexpr int NKY = K4 ? 2 : 3, NF = K4 ? 2 : 3, NT = NKY * NF;               // tap rows, tap columns (fragments per group), taps per chunk
     constexpr int NJ = 2;                                                          // 32-pixel column tiles per wave
@@ -480,38 +475,29 @@ int b2_launch(int compute, const void* x, const void* w_packed, const float* bia
     if (ntiles >= (1ll << 31)) return vs_fail(VS_ERR_UNSUPPORTED, "vs_conv3_band (v2): too many tiles");
     // persistent: what the chip holds at once (workgroups per CU by LDS: two where they fit, and never more than 2 waves per SIMD)
     const int per_cu = WM == 2 ? 1 : ((size_t)160 * 1024 / lds >= 2 ? 2 : 1);
-    const char* ge = getenv("VS_BAND2_GRID");                                       // (diagnosis: workgroups per CU, 0 = one workgroup per tile)
-    int64_t slots = (int64_t)cus * (ge && atoi(ge) > 0 ? atoi(ge) : per_cu);
-    if (ge && atoi(ge) == 0) slots = ntiles;
+    const int64_t slots = (int64_t)cus * per_cu;
     const dim3 grid((unsigned)(ntiles < slots ? ntiles : slots));
     const int chunks_total = (int)vs_cdiv(Cin, 64) * 4;                             // the pack holds whole 64-channel phases (zeros beyond Cin)
     const int nph = (int)vs_cdiv(Cin, KC);
-    const char* se = getenv("VS_BAND2_STAGGER");                                    // read per call: A/B runs switch it
-    const int stagger = (se && per_cu == 2) ? atoi(se) : 0;
     if (compute == VS_BF16)
         hipLaunchKernelGGL(kb, grid, dim3(256 * WM), lds, stream, (const unsigned short*)x, (const unsigned short*)w_packed, bias, y, y_dtype, B, Cin, H, Cout,
-                           mgroups, bands, (int)ntiles, chunks_total, nph, stagger);
+                           mgroups, bands, (int)ntiles, chunks_total, nph);
     else
         hipLaunchKernelGGL(kh, grid, dim3(256 * WM), lds, stream, (const unsigned short*)x, (const unsigned short*)w_packed, bias, y, y_dtype, B, Cin, H, Cout,
-                           mgroups, bands, (int)ntiles, chunks_total, nph, stagger);
+                           mgroups, bands, (int)ntiles, chunks_total, nph);
     return VS_OK;
 }
 
 // WM = 2 (512 threads, 64 output channels: the pixel image staged once for both channel tiles) vs WM = 1 (two independent workgroups per
-// CU).  VS_BAND2_WM = 1 / 2 forces a form (read per call: tools/band_bench.py A/B).
+// CU)
 template <int W, int K4>
 int b2_pick(int compute, const void* x, const void* w_packed, const float* bias, void* y, int y_dtype, int B, int Cin, int H, int Cout, hipStream_t stream) {
     constexpr int KC = W == 64 ? 16 : 32;                                           // (64-wide maps: 24 KiB of pixels per 32 channels -- half phases keep two workgroups per CU)
-    const char* fe = getenv("VS_BAND2_WM");
-    const int force = fe ? atoi(fe) : 0;
     // measured (tools/band_bench.py, profiles/r05_band_bench.txt): the 8-wave form wins wherever it still has a tile per CU -- 64-wide maps by
     // 30 %, the decoders' 16 / 32-wide layers by 5-10 % -- and loses on the short launches of the encoders (fewer, heavier workgroups)
     constexpr int IPB = W == 8 ? 4 : (W == 4 ? 16 : 1), RI = W == 8 ? 8 : (W == 4 ? 4 : 256 / W);
     const int64_t tiles2 = (IPB > 1 ? vs_cdiv(B, IPB) : (int64_t)B * (H / RI)) * vs_cdiv(vs_cdiv(Cout, 32), 2);
-    bool two = Cout > 32 && tiles2 >= 256;
-    if (force == 1) two = false;
-    if (force == 2) two = Cout > 32;
-    if (two) return b2_launch<W, 2, K4, 32>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream);
+    if (Cout > 32 && tiles2 >= 256) return b2_launch<W, 2, K4, 32>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream);
     return b2_launch<W, 1, K4, KC>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream);
 }
 

@@ -1267,8 +1267,7 @@ extern "C" int vs_conv3_img16(int compute, const void* x, const void* w_packed, 
             return vs_fail(VS_ERR_LAUNCH, "vs_conv3_img16: cannot raise the dynamic LDS limit");
         attr_set[pair] = true;
     }
-    const char* wse = getenv("VS_IMG16_WIDE_STORE");                              // (read per call: A/B in one process; the LDS image holds >= 32 KiB: cs >= 64)
-    const int wide = !(wse && wse[0] == '0') && lds >= (size_t)32 * 1024;
+    const int wide = lds >= (size_t)32 * 1024;                                    // (the LDS image holds >= 32 KiB: cs >= 64)
     if (compute == VS_BF16)
         hipLaunchKernelGGL(kb, grid, dim3(256), lds, (hipStream_t)stream, (const unsigned short*)x, (const u32x4*)w_packed, slabs, B, Cin, Cout, cs, splits, mtiles, wide);
     else
@@ -1287,8 +1286,7 @@ extern "C" int vs_conv3_img16_bn_supported(int compute, int B, int Cin, int Cout
     if (!vs_conv3_img16_supported(compute, B, Cin, 16, 16, Cout)) return 0;
     const int s = img16_splits(B, Cin, Cout), mtiles = (int)vs_cdiv(Cout, 32);
     if (s != 1 && s != 2 && s != 8) return 0;
-    static const int cus = getenv("VS_IMG_BN_MAX_WGS") ? atoi(getenv("VS_IMG_BN_MAX_WGS")) : 256;       // every workgroup must be resident: one per CU
-    if ((int64_t)B * mtiles * s > cus) return 0;
+    if ((int64_t)B * mtiles * s > 256) return 0;                                   // every workgroup must be resident: one per CU
     if (B > 64 || (int64_t)mtiles * 32 * B * 16 > (int64_t)IMGBN_B_BYTES) return 0;
     return 1;
 }
@@ -1309,7 +1307,6 @@ extern "C" int vs_exchange_epoch_advance(void* ws, void* stream) {
 }
 
 static int imgbn_launch(int compute, int mode, ImgBnArgs& a, void* ws, unsigned call_idx, hipStream_t stream) {
-    static const unsigned spin = getenv("VS_IMG_BN_SPIN") ? (unsigned)atol(getenv("VS_IMG_BN_SPIN")) : 2000000u;
     a.splits = img16_splits(a.B, a.Cin, a.Cout);
     a.cs = a.Cin / a.splits;
     a.mtiles = (int)vs_cdiv(a.Cout, 32);
@@ -1320,7 +1317,7 @@ static int imgbn_launch(int compute, int mode, ImgBnArgs& a, void* ws, unsigned 
     a.xb = (xg64*)(base + IMGBN_B_OFF);
     a.xa = (xg64*)(base + IMGBN_A_OFF);
     a.call_idx = call_idx;
-    a.spin_limit = spin;
+    a.spin_limit = 2000000u;
     // the image (cs channels) or the epilogue's tiles -- partial sums [32][256], two pixel-major tiles of <= [32][264] and the small rows --
     // whichever is larger
     size_t lds = (size_t)a.cs * IMG_CPITCH * 2;
@@ -1459,8 +1456,7 @@ static int launch_band(int compute, const void* x, const void* w_packed, const f
     const int Cpad = (int)vs_cdiv(Cin, 64) * 64;                                    // the kernel walks whole 64-channel phases
     const int mtiles = (int)vs_cdiv(Cout, 32), bands = IPB > 1 ? (int)vs_cdiv(B, IPB) : H / R;
     const dim3 grid((unsigned)((int64_t)(IPB > 1 ? 1 : B) * bands * mtiles));
-    static const int xcd_remap = getenv("VS_BAND_XCD") ? atoi(getenv("VS_BAND_XCD")) : 1;
-    const int remap = xcd_remap && mtiles > 1 && grid.x >= 64;
+    const int remap = mtiles > 1 && grid.x >= 64;
     if (compute == VS_BF16)
         hipLaunchKernelGGL(kb, grid, dim3(256), lds, stream, (const unsigned short*)x, (const u32x4*)w_packed, bias, y, y_dtype, B, Cpad, H, Cout, mtiles, bands,
                            remap, bn_sums, maps_per_group, Cin);
@@ -1474,19 +1470,17 @@ static int launch_band(int compute, const void* x, const void* w_packed, const f
 template <int W>
 static int launch_band_k4_w(int compute, const void* x, const void* w_packed, const float* bias, void* y, int y_dtype, int B, int Cin, int H, int Cout,
                             hipStream_t stream, double* bn_sums = nullptr, int mpg = 1) {
-    static const int pair_mode = getenv("VS_CONV_BAND_PAIR") ? atoi(getenv("VS_CONV_BAND_PAIR")) : 1;
     const size_t lds = 2 * band_buf_bytes<W>();                                  // Cin = 4 K >= 256: always two buffers
-    if (pair_mode && 2 * lds <= 160 * 1024) return launch_band<W, 4, 2, 1>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream, bn_sums, mpg);
+    if (2 * lds <= 160 * 1024) return launch_band<W, 4, 2, 1>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream, bn_sums, mpg);
     return launch_band<W, 8, 1, 1>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream, bn_sums, mpg);
 }
 
 template <int W>
 static int launch_band_w(int compute, const void* x, const void* w_packed, const float* bias, void* y, int y_dtype, int B, int Cin, int H, int Cout,
                          hipStream_t stream, double* bn_sums = nullptr, int mpg = 1) {
-    // two workgroups per CU where 2 x LDS fits (VS_CONV_BAND_PAIR=0: always the deep-prefetch form)
-    static const int pair_mode = getenv("VS_CONV_BAND_PAIR") ? atoi(getenv("VS_CONV_BAND_PAIR")) : 1;
+    // two workgroups per CU where 2 x LDS fits, else the deep-prefetch form
     const size_t lds = (size_t)(Cin > 64 ? 2 : 1) * band_buf_bytes<W>();
-    if (pair_mode && 2 * lds <= 160 * 1024) return launch_band<W, 4, 2>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream, bn_sums, mpg);
+    if (2 * lds <= 160 * 1024) return launch_band<W, 4, 2>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream, bn_sums, mpg);
     return launch_band<W, 12, 1>(compute, x, w_packed, bias, y, y_dtype, B, Cin, H, Cout, stream, bn_sums, mpg);
 }
 
@@ -1590,43 +1584,24 @@ static int wgrad_band_ksplit(int B, int Cin, int H, int W, int Cout, int ctw = 1
     // ONE round of workgroups (a workgroup's LDS fills a CU): every share of the bands costs a slab of the weight's size, written and read
     // again by the finish pass -- with two rounds (512) the slabs of a TaxiBJ step were 3.9 GB of traffic: 9.80 -> 9.37 ms with 256; 128, 192
     // and 384 are slower (idle CUs / a partial second round)
-    static const int target_wgs = getenv("VS_WGRAD_BAND_WGS") ? atoi(getenv("VS_WGRAD_BAND_WGS")) : 256;
-    int64_t ks = vs_cdiv(target_wgs, tiles);
+    int64_t ks = vs_cdiv(256, tiles);
     if (ks > items) ks = items;
     const int64_t slab_bytes = (int64_t)Cout * Cin * 9 * 4;
     while (ks > 1 && ks * (4 / mw) * slab_bytes > ((int64_t)96 << 20)) --ks;    // at most 96 MiB of slabs
     return (int)(ks < 1 ? 1 : ks);
 }
 
-// round 5: the form with both operands staged by LDS-DMA and the column shift taken in registers (csrc/vs_conv_wgrad2.hip); VS_WGRAD_V2=0
-// (read per call: the slab query and the launch must see the same value) restores the round-2 kernel.  The k4 s2 family keeps the round-2 kernel.
+// round 5: the form with both operands staged by LDS-DMA and the column shift taken in registers (csrc/vs_conv_wgrad2.hip) serves the 3 x 3
+// family.  The k4 s2 family keeps the round-2 kernel: a plane's 2 x 2 taps leave four MFMAs per k-step against the same staged tiles, so the
+// round-5 form is bound by the LDS-DMA there and loses to the round-2 kernel, which walks two channel tiles per staged dz tile.
 int vs_wgrad2_slabs(int B, int Cin, int H, int W, int Cout);
 int vs_wgrad2_go(int compute, int npieces, const void* const* x, const void* const* dz, int maps_per_piece, float* slabs, int B, int Cin, int H, int W, int Cout,
-                 int k4, hipStream_t stream);
-static inline bool wgrad2_enabled() {
-    const char* e = getenv("VS_WGRAD_V2");
-    return !(e && e[0] == '0');
-}
-// the k4 s2 family: built and correct (tools/band_bench.py k4 --check), but a plane's 2 x 2 taps leave four MFMAs per k-step against the same
-// staged tiles -- the launch is bound by the LDS-DMA (52 KiB per 1 150 cycles) and loses to the round-2 kernel, which walks two channel tiles
-// per staged dz tile: 256 -> 349 us, 192 -> 263 us on the Moving-MNIST decoder layers, the step 6.11 -> 6.32 ms.  Opt-in: VS_WGRAD_V2_K4=1.
-static inline bool wgrad2_k4_enabled() {
-    const char* e = getenv("VS_WGRAD_V2_K4");
-    return wgrad2_enabled() && e && e[0] == '1';
-}
+                 hipStream_t stream);
 
-extern "C" int vs_conv3_wgrad_band_slabs(int B, int Cin, int H, int W, int Cout) {
-    if (wgrad2_enabled()) return vs_wgrad2_slabs(B, Cin, H, W, Cout);
-    return (4 / wgrad_band_mw(Cout)) * wgrad_band_ksplit(B, Cin, H, W, Cout);
-}
+extern "C" int vs_conv3_wgrad_band_slabs(int B, int Cin, int H, int W, int Cout) { return vs_wgrad2_slabs(B, Cin, H, W, Cout); }
 
-// K4 form: two 32-channel tiles of a plane per workgroup against one staged dz tile.  Four (VS_WGRAD_K4_CTW4=1, where a plane holds a multiple of
-// 128 channels) is built and measured SLOWER: half as many tiles means twice the batch shares to fill the chip, i.e. twice the slabs, and the
-// fourth stage of an item no longer hides its loads -- Moving-MNIST 6.45 (two) vs 6.71 ms (four).
-static int wgrad_k4_ctw(int Cin) {
-    static const int allow4 = getenv("VS_WGRAD_K4_CTW4") ? atoi(getenv("VS_WGRAD_K4_CTW4")) : 0;
-    return (allow4 && (Cin >> 2) % 128 == 0) ? 4 : 2;
-}
+// K4 form of the round-2 kernel: two 32-channel tiles of a plane per workgroup against one staged dz tile
+constexpr int WGRAD_K4_CTW = 2;
 
 template <int W, int MW, int K4, int CTW>
 static void launch_wgrad_band_ctw(int compute, const WgradPieces& pieces, float* slabs, int B, int Cin, int H, int Cout, int ksplit, hipStream_t stream) {
@@ -1649,12 +1624,7 @@ static void launch_wgrad_band_ctw(int compute, const WgradPieces& pieces, float*
 
 template <int W, int MW, int K4 = 0>
 static void launch_wgrad_band(int compute, const WgradPieces& pieces, float* slabs, int B, int Cin, int H, int Cout, int ksplit, hipStream_t stream) {
-    if constexpr (K4) {
-        if (wgrad_k4_ctw(Cin) == 4) launch_wgrad_band_ctw<W, MW, K4, 4>(compute, pieces, slabs, B, Cin, H, Cout, ksplit, stream);
-        else launch_wgrad_band_ctw<W, MW, K4, 2>(compute, pieces, slabs, B, Cin, H, Cout, ksplit, stream);
-    } else {
-        launch_wgrad_band_ctw<W, MW, K4, 1>(compute, pieces, slabs, B, Cin, H, Cout, ksplit, stream);
-    }
+    launch_wgrad_band_ctw<W, MW, K4, K4 ? WGRAD_K4_CTW : 1>(compute, pieces, slabs, B, Cin, H, Cout, ksplit, stream);
 }
 
 template <int W, int K4 = 0>
@@ -1667,7 +1637,7 @@ static void launch_wgrad_band_w(int compute, const WgradPieces& pieces, float* s
 
 template <int K4 = 0>
 static int wgrad_band_go(int compute, const WgradPieces& pieces, float* slabs, int B, int Cin, int H, int W, int Cout, hipStream_t stream) {
-    const int ks = wgrad_band_ksplit(B, Cin, H, W, Cout, K4 ? wgrad_k4_ctw(Cin) : 1);
+    const int ks = wgrad_band_ksplit(B, Cin, H, W, Cout, K4 ? WGRAD_K4_CTW : 1);
     if (W == 64) launch_wgrad_band_w<64, K4>(compute, pieces, slabs, B, Cin, H, Cout, ks, stream);
     else if (W == 32) launch_wgrad_band_w<32, K4>(compute, pieces, slabs, B, Cin, H, Cout, ks, stream);
     else if (W == 16) launch_wgrad_band_w<16, K4>(compute, pieces, slabs, B, Cin, H, Cout, ks, stream);
@@ -1681,17 +1651,10 @@ extern "C" int vs_conv3_wgrad_band(int compute, const void* x, const void* dz, f
     VS_CHECK_ARG(x && dz && slabs, "vs_conv3_wgrad_band: bad argument");
     VS_CHECK_ARG(vs_conv3_wgrad_band_supported(compute, B, Cin, H, W, Cout), "vs_conv3_wgrad_band: unsupported geometry (query vs_conv3_wgrad_band_supported)");
     VS_CHECK_ARG(((uintptr_t)x | (uintptr_t)dz | (uintptr_t)slabs) % 16 == 0, "vs_conv3_wgrad_band: operands must be 16-byte aligned");
-    if (wgrad2_enabled()) {
-        const int rc = vs_wgrad2_go(compute, 1, &x, &dz, B, slabs, B, Cin, H, W, Cout, 0, (hipStream_t)stream);
-        if (rc != VS_OK) return rc;
-        VS_CHECK_LAUNCH("vs_conv3_wgrad_band (v2)");
-        return VS_OK;
-    }
-    WgradPieces pieces = {};
-    pieces.x[0] = (const unsigned short*)x;
-    pieces.dz[0] = (const unsigned short*)dz;
-    pieces.maps_per_piece = B;
-    return wgrad_band_go<0>(compute, pieces, slabs, B, Cin, H, W, Cout, (hipStream_t)stream);
+    const int rc = vs_wgrad2_go(compute, 1, &x, &dz, B, slabs, B, Cin, H, W, Cout, (hipStream_t)stream);
+    if (rc != VS_OK) return rc;
+    VS_CHECK_LAUNCH("vs_conv3_wgrad_band (v2)");
+    return VS_OK;
 }
 
 // ---- k4 s2 p1 on parity planes (csrc/vs_conv_k4s2.hip): planes [B][4 K][H][W] ----------------------------------------------------------
@@ -1731,20 +1694,13 @@ extern "C" int vs_conv_k4s2_band(int compute, const void* planes, const void* w_
 
 // slabs vs_conv_k4s2_wgrad_band writes (the skip form shares the batch among fewer, heavier workgroups than vs_conv3_wgrad_band on the same planes)
 extern "C" int vs_conv_k4s2_wgrad_band_slabs(int B, int K, int H, int W, int M) {
-    if (wgrad2_k4_enabled() && vs_conv_k4s2_skip_form(K)) return vs_wgrad2_slabs(B, 4 * K, H, W, M);
-    return (4 / wgrad_band_mw(M)) * wgrad_band_ksplit(B, 4 * K, H, W, M, vs_conv_k4s2_skip_form(K) ? wgrad_k4_ctw(4 * K) : 1);
+    return (4 / wgrad_band_mw(M)) * wgrad_band_ksplit(B, 4 * K, H, W, M, vs_conv_k4s2_skip_form(K) ? WGRAD_K4_CTW : 1);
 }
 
 extern "C" int vs_conv_k4s2_wgrad_band(int compute, const void* planes, const void* small, float* slabs, int B, int K, int H, int W, int M, void* stream) {
     VS_CHECK_ARG(planes && small && slabs, "vs_conv_k4s2_wgrad_band: bad argument");
     VS_CHECK_ARG(vs_conv3_wgrad_band_supported(compute, B, 4 * K, H, W, M), "vs_conv_k4s2_wgrad_band: unsupported geometry");
     VS_CHECK_ARG(((uintptr_t)planes | (uintptr_t)small | (uintptr_t)slabs) % 16 == 0, "vs_conv_k4s2_wgrad_band: operands must be 16-byte aligned");
-    if (wgrad2_k4_enabled() && vs_conv_k4s2_skip_form(K)) {
-        const int rc = vs_wgrad2_go(compute, 1, &planes, &small, B, slabs, B, 4 * K, H, W, M, 1, (hipStream_t)stream);
-        if (rc != VS_OK) return rc;
-        VS_CHECK_LAUNCH("vs_conv_k4s2_wgrad_band (v2)");
-        return VS_OK;
-    }
     WgradPieces pieces = {};
     pieces.x[0] = (const unsigned short*)planes;
     pieces.dz[0] = (const unsigned short*)small;
@@ -1762,24 +1718,13 @@ extern "C" int vs_conv3_wgrad_band_pieces(int compute, int npieces, const void* 
     VS_CHECK_ARG(vs_conv3_wgrad_band_supported(compute, B, Cin, H, W, Cout), "vs_conv3_wgrad_band_pieces: unsupported geometry");
     VS_CHECK_ARG(W != 8 || npieces == 1 || maps_per_piece % 4 == 0, "vs_conv3_wgrad_band_pieces: 8 x 8 maps go four at a time: maps_per_piece must be a multiple of 4");
     VS_CHECK_ARG(W != 4 || npieces == 1 || maps_per_piece % 16 == 0, "vs_conv3_wgrad_band_pieces: 4 x 4 maps go sixteen at a time: maps_per_piece must be a multiple of 16");
-    if (wgrad2_enabled()) {
-        for (int i = 0; i < npieces; ++i)
-            VS_CHECK_ARG(x[i] && dz[i] && ((uintptr_t)x[i] | (uintptr_t)dz[i]) % 16 == 0, "vs_conv3_wgrad_band_pieces: every piece must be a 16-byte aligned tensor");
-        VS_CHECK_ARG((uintptr_t)slabs % 16 == 0, "vs_conv3_wgrad_band_pieces: slabs must be 16-byte aligned");
-        const int rc = vs_wgrad2_go(compute, npieces, x, dz, maps_per_piece, slabs, B, Cin, H, W, Cout, 0, (hipStream_t)stream);
-        if (rc != VS_OK) return rc;
-        VS_CHECK_LAUNCH("vs_conv3_wgrad_band_pieces (v2)");
-        return VS_OK;
-    }
-    WgradPieces pieces = {};
-    for (int i = 0; i < npieces; ++i) {
+    for (int i = 0; i < npieces; ++i)
         VS_CHECK_ARG(x[i] && dz[i] && ((uintptr_t)x[i] | (uintptr_t)dz[i]) % 16 == 0, "vs_conv3_wgrad_band_pieces: every piece must be a 16-byte aligned tensor");
-        pieces.x[i] = (const unsigned short*)x[i];
-        pieces.dz[i] = (const unsigned short*)dz[i];
-    }
-    pieces.maps_per_piece = maps_per_piece;
     VS_CHECK_ARG((uintptr_t)slabs % 16 == 0, "vs_conv3_wgrad_band_pieces: slabs must be 16-byte aligned");
-    return wgrad_band_go<0>(compute, pieces, slabs, B, Cin, H, W, Cout, (hipStream_t)stream);
+    const int rc = vs_wgrad2_go(compute, npieces, x, dz, maps_per_piece, slabs, B, Cin, H, W, Cout, (hipStream_t)stream);
+    if (rc != VS_OK) return rc;
+    VS_CHECK_LAUNCH("vs_conv3_wgrad_band_pieces (v2)");
+    return VS_OK;
 }
 
 // partial[g][i] = sum over the slabs g * per .. g * per + per - 1 (per = ceil(nslabs / groups)) of slabs[s][i], i < total (a multiple of 4):

@@ -127,7 +127,7 @@ __device__ __forceinline__ void tap_bn_accumulate(double* sums, float s1, float 
 
 template <int CT>
 __global__ __launch_bounds__(512) void convt_k4s2_tap_kernel(const unsigned short* X, const unsigned short* At, const float* bias, unsigned short* Y,
-                                                             double* sums, int B, int Cin, int H, int W, int Cout, int Bg, int tiles_m, int diag, int y_f32) {
+                                                             double* sums, int B, int Cin, int H, int W, int Cout, int Bg, int tiles_m, int y_f32) {
     extern __shared__ __attribute__((aligned(16))) char smem[];      // ring: 4 x [A0 | A1 | B0 | B1] x 8 KiB; then the fp32 staging area
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = wave >> 2, wc = wave & 3;
@@ -137,11 +137,7 @@ __global__ __launch_bounds__(512) void convt_k4s2_tap_kernel(const unsigned shor
     const int tm = (int)(tile % (unsigned)tiles_m);
     const int64_t n0 = (int64_t)(tile / (unsigned)tiles_m) * 256;
     f32x16 acc[4][2];
-    tap_k_loop<CT>(acc, At + (int64_t)tm * 256 * (diag & 2 ? 32 : Cin), X, diag & 2 ? 32 : Cin, HW, npix, n0, smem);
-    if (diag & 4) {                                               // timing diagnostics: no epilogue at all
-        if (acc[0][0][0] == 123.f) Y[0] = 1;
-        return;
-    }
+    tap_k_loop<CT>(acc, At + (int64_t)tm * 256 * Cin, X, Cin, HW, npix, n0, smem);
 
     // ---- epilogue: col2im through LDS.  Staging image Gs[tap 16][channel 8][pixel 256] fp32 = 128 KiB, two passes ------------
     float* Gs = reinterpret_cast<float*>(smem);
@@ -171,60 +167,58 @@ __global__ __launch_bounds__(512) void convt_k4s2_tap_kernel(const unsigned shor
         // w of the pass (two items per lane): the BatchNorm partial sums stay in registers over both items and are reduced once
         // per wave and pass.  (First version: items dealt round-robin, a 64-lane fp64 shuffle reduction per item and 16
         // conditional scalar LDS reads per tap row: 575 of the 814 us of the 128 -> 64 @16x16 layer.)
-        if (!(diag & 1)) {
-            const int ch = wave;
-            const int m = tm * TAP_MB + 8 * pass + ch;
-            const float bv = (bias && m < Cout) ? bias[m] : 0.f;
-            float s1 = 0.f, s2 = 0.f;
+        const int ch = wave;
+        const int m = tm * TAP_MB + 8 * pass + ch;
+        const float bv = (bias && m < Cout) ? bias[m] : 0.f;
+        float s1 = 0.f, s2 = 0.f;
 #pragma unroll 1
-            for (int rep = 0; rep < 2; ++rep) {
-                const int rem = rep * 64 + lane;                 // H = W in {4, 8, 16}: every divisor below is a power of two
-                const int s = rem >> lg_ips, r2 = rem & (items_per_sample - 1);
-                const int oy = r2 >> lg_ipr, ox0 = (r2 & (ipr - 1)) * 8, x0 = ox0 >> 1;
-                const int64_t b = n0 / HW + s;
-                float z[8];
+        for (int rep = 0; rep < 2; ++rep) {
+            const int rem = rep * 64 + lane;                 // H = W in {4, 8, 16}: every divisor below is a power of two
+            const int s = rem >> lg_ips, r2 = rem & (items_per_sample - 1);
+            const int oy = r2 >> lg_ipr, ox0 = (r2 & (ipr - 1)) * 8, x0 = ox0 >> 1;
+            const int64_t b = n0 / HW + s;
+            float z[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) z[e] = bv;
-                // rows: oy even <- (ky 1, y = oy/2), (ky 3, y = oy/2 - 1); oy odd <- (ky 0, y = (oy+1)/2), (ky 2, y = (oy-1)/2)
+            for (int e = 0; e < 8; ++e) z[e] = bv;
+            // rows: oy even <- (ky 1, y = oy/2), (ky 3, y = oy/2 - 1); oy odd <- (ky 0, y = (oy+1)/2), (ky 2, y = (oy-1)/2)
 #pragma unroll
-                for (int jy = 0; jy < 2; ++jy) {
-                    const int ky = (oy & 1) ? 2 * jy : 1 + 2 * jy;
-                    const int y = (oy + 1 - ky) >> 1;
-                    if (y < 0 || y >= H) continue;
-                    const float* g = Gs + ((ky * 4) * 8 + ch) * 256 + s * HW + y * W + x0;      // + kx * 8 * 256 per tap column
-                    // even outputs ox0 + 2q <- (kx 1, x = x0 + q), (kx 3, x = x0 + q - 1); odd ox0 + 2q + 1 <- (kx 0, x0 + q + 1), (kx 2, x0 + q):
-                    // four aligned 16-byte reads at x0 and the two neighbours across the item's ends
-                    const f32x4 k0 = *reinterpret_cast<const f32x4*>(g), k1 = *reinterpret_cast<const f32x4*>(g + 2048);
-                    const f32x4 k2 = *reinterpret_cast<const f32x4*>(g + 2 * 2048), k3 = *reinterpret_cast<const f32x4*>(g + 3 * 2048);
-                    const float left = x0 > 0 ? g[3 * 2048 - 1] : 0.f, right = x0 + 4 < W ? g[4] : 0.f;
-                    z[0] += k1[0] + left;   z[1] += k2[0] + k0[1];
-                    z[2] += k1[1] + k3[0];  z[3] += k2[1] + k0[2];
-                    z[4] += k1[2] + k3[1];  z[5] += k2[2] + k0[3];
-                    z[6] += k1[3] + k3[2];  z[7] += k2[3] + right;
-                }
-                if (m < Cout && b < B) {
-                    if (y_f32) {
-                        // fp32 output (vs_convt_k4s2_tap_fwd_f32: the fp32 parity mode assembles an fp32 convolution from bf16 pieces, ops._tap_split)
-                        float* yo = reinterpret_cast<float*>(Y) + (b * Cout + m) * OHW + oy * OW + ox0;
-                        *reinterpret_cast<f32x4*>(yo) = f32x4{z[0], z[1], z[2], z[3]};
-                        *reinterpret_cast<f32x4*>(yo + 4) = f32x4{z[4], z[5], z[6], z[7]};
+            for (int jy = 0; jy < 2; ++jy) {
+                const int ky = (oy & 1) ? 2 * jy : 1 + 2 * jy;
+                const int y = (oy + 1 - ky) >> 1;
+                if (y < 0 || y >= H) continue;
+                const float* g = Gs + ((ky * 4) * 8 + ch) * 256 + s * HW + y * W + x0;      // + kx * 8 * 256 per tap column
+                // even outputs ox0 + 2q <- (kx 1, x = x0 + q), (kx 3, x = x0 + q - 1); odd ox0 + 2q + 1 <- (kx 0, x0 + q + 1), (kx 2, x0 + q):
+                // four aligned 16-byte reads at x0 and the two neighbours across the item's ends
+                const f32x4 k0 = *reinterpret_cast<const f32x4*>(g), k1 = *reinterpret_cast<const f32x4*>(g + 2048);
+                const f32x4 k2 = *reinterpret_cast<const f32x4*>(g + 2 * 2048), k3 = *reinterpret_cast<const f32x4*>(g + 3 * 2048);
+                const float left = x0 > 0 ? g[3 * 2048 - 1] : 0.f, right = x0 + 4 < W ? g[4] : 0.f;
+                z[0] += k1[0] + left;   z[1] += k2[0] + k0[1];
+                z[2] += k1[1] + k3[0];  z[3] += k2[1] + k0[2];
+                z[4] += k1[2] + k3[1];  z[5] += k2[2] + k0[3];
+                z[6] += k1[3] + k3[2];  z[7] += k2[3] + right;
+            }
+            if (m < Cout && b < B) {
+                if (y_f32) {
+                    // fp32 output (vs_convt_k4s2_tap_fwd_f32: the fp32 parity mode assembles an fp32 convolution from bf16 pieces, ops._tap_split)
+                    float* yo = reinterpret_cast<float*>(Y) + (b * Cout + m) * OHW + oy * OW + ox0;
+                    *reinterpret_cast<f32x4*>(yo) = f32x4{z[0], z[1], z[2], z[3]};
+                    *reinterpret_cast<f32x4*>(yo + 4) = f32x4{z[4], z[5], z[6], z[7]};
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) { s1 += z[e]; s2 += z[e] * z[e]; }
-                    } else {
-                        u16x8 o;
+                    for (int e = 0; e < 8; ++e) { s1 += z[e]; s2 += z[e] * z[e]; }
+                } else {
+                    u16x8 o;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            o[e] = vs_f2h(z[e], CT);
-                            const float zr = vs_h2f(o[e], CT);                       // statistics of the STORED values, like vs_bn_stats
-                            s1 += zr; s2 += zr * zr;
-                        }
-                        *reinterpret_cast<u16x8*>(Y + (b * Cout + m) * OHW + oy * OW + ox0) = o;
+                    for (int e = 0; e < 8; ++e) {
+                        o[e] = vs_f2h(z[e], CT);
+                        const float zr = vs_h2f(o[e], CT);                       // statistics of the STORED values, like vs_bn_stats
+                        s1 += zr; s2 += zr * zr;
                     }
+                    *reinterpret_cast<u16x8*>(Y + (b * Cout + m) * OHW + oy * OW + ox0) = o;
                 }
             }
-            // the tile's samples belong to ONE call group (Bg % S == 0 is checked on the host)
-            if (sums) tap_bn_accumulate(sums, s1, s2, lane, m < Cout && n0 / HW < B, ((n0 / HW) / Bg) * Cout + m);
         }
+        // the tile's samples belong to ONE call group (Bg % S == 0 is checked on the host)
+        if (sums) tap_bn_accumulate(sums, s1, s2, lane, m < Cout && n0 / HW < B, ((n0 / HW) / Bg) * Cout + m);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                            // staging area free for the next pass
     }
@@ -546,14 +540,12 @@ int convt_tap_go(int compute, const void* x, const void* w_tap, const float* bia
         attr_set = true;
     }
     dim3 grid((unsigned)(tiles_px * tiles_m));
-    const char* denv = getenv("VS_TAP_DIAG");                     // timing diagnostics only (wrong results)
-    const int diag = denv ? atoi(denv) : 0;
     if (compute == VS_BF16)
         hipLaunchKernelGGL(kb, grid, dim3(512), BIG_STAGES * BIG_TILE_BYTES, (hipStream_t)stream, (const unsigned short*)x, (const unsigned short*)w_tap, bias,
-                           (unsigned short*)y, bn_sums, B, Cin, H, W, Cout, B / groups, tiles_m, diag, y_f32);
+                           (unsigned short*)y, bn_sums, B, Cin, H, W, Cout, B / groups, tiles_m, y_f32);
     else
         hipLaunchKernelGGL(kh, grid, dim3(512), BIG_STAGES * BIG_TILE_BYTES, (hipStream_t)stream, (const unsigned short*)x, (const unsigned short*)w_tap, bias,
-                           (unsigned short*)y, bn_sums, B, Cin, H, W, Cout, B / groups, tiles_m, diag, y_f32);
+                           (unsigned short*)y, bn_sums, B, Cin, H, W, Cout, B / groups, tiles_m, y_f32);
     VS_CHECK_LAUNCH("vs_convt_k4s2_tap_fwd");
     return VS_OK;
 }

@@ -17,7 +17,6 @@
 //   * a workgroup is eight waves = 2 output-channel sub-tiles (64 m) x 4 quarters of the band's sixteen k-steps, 32 input channels; the four
 //     partial sums of a sub-tile meet in LDS at the very end: ONE slab [tap][m][c] per workgroup share (vs_conv3_wgrad_band_finish adds them).
 #include "vs_gemm_glds.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -52,13 +51,11 @@ __device__ __forceinline__ void wg2_dma(uint32_t lds_dst, const void* sbase, uin
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory", "m0");
 }
 
-// K4 = 1: the k4 s2 p1 family on parity planes (csrc/vs_conv_k4s2.hip): Cin = 4 K plane channels, K a multiple of 32, so the 32 channels of a workgroup
-// lie in ONE plane, which sees 2 x 2 of the 3 x 3 taps: four MFMAs per k-step, four slab positions written (vs_conv_k4s2_wgrad_finish reads no others)
-template <int CT, int W, int K4>
-__global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, float* __restrict__ slabs, int B, int Cin, int H, int Cout, int ctiles, int ksplit, int lds_neighbours) {
+template <int CT, int W>
+__global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, float* __restrict__ slabs, int B, int Cin, int H, int Cout, int ctiles, int ksplit) {
     typedef Wg2Geo<W> G;
     constexpr int ROWB = W * 2;
-    constexpr int NKY = K4 ? 2 : 3, NT = K4 ? 4 : 9;
+    constexpr int NT = 9;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];         // [2][x tile | dz tile]
     int id = blockIdx.x;
     const int ks = id % ksplit;
@@ -157,9 +154,6 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
         }
     };
 
-    // K4: first tap row / column this plane sees (odd planes: {0, 1}, even planes: {1, 2}); wave-uniform
-    const int plane = K4 ? (ct * 32) / (Cin >> 2) : 0;
-    const int ky_lo = K4 ? ((plane >> 1) ? 0 : 1) : 0, kx_lo = K4 ? ((plane & 1) ? 0 : 1) : 0;
     f32x16 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -189,8 +183,7 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
             }
             const u32x4 af = *reinterpret_cast<const u32x4*>(zs + (msub * 32 + rl) * (G::ZPP * 16) + (p0 + 8 * h) * 2);
 #pragma unroll
-            for (int kyi = 0; kyi < NKY; ++kyi) {
-                const int ky = ky_lo + kyi;
+            for (int ky = 0; ky < 3; ++ky) {
                 u32x4 own;
                 unsigned lft = 0, rgt = 0;                                        // dwords holding the pixel before / after the lane's eight
                 if constexpr (G::HALO) {
@@ -200,26 +193,20 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
                     if (yimg < 0 || yimg >= H) continue;                          // a row outside the image contributes nothing
                     const unsigned char* src = xs + rl * (G::PPCP * 16) + ((row + ky) * W + q) * 2;
                     own = *reinterpret_cast<const u32x4*>(src);
-                    // The sixteen pixels of a k-step are split over the two lane halves (h): the pixel AFTER the lower half's eight is the upper half's
-                    // first, the pixel BEFORE the upper half's eight is the lower half's last -- one v_permlane32_swap instead of two LDS reads.  What
-                    // is left for LDS is the pixel outside the sixteen (one ds_read_b32 per lane; none at W = 16, where a k-step is a whole row): the
-                    // channel pitch is a multiple of 16 bytes, so a 4-byte read of 32 channels is 4-way bank-conflicted whatever the pad, and round 5's
-                    // counters had these reads at 46-52 % of the kernel's LDS cycles (profiles/r05_*_mfma_util.md).
-                    if (lds_neighbours) {                                        // VS_WGRAD2_NB=1: the round-5 form (both neighbours from LDS), kept for A/B runs
+                    // The column neighbours of a lane's eight pixels.  W > 16: one ds_read_b32 each side (the channel pitch is a multiple of 16 bytes,
+                    // so a 4-byte read of 32 channels is 4-way bank-conflicted whatever the pad: round 5's counters had these reads at 46-52 % of the
+                    // kernel's LDS cycles, profiles/r05_*_mfma_util.md).  W = 16: a k-step is a whole row split over the two lane halves (h), so the
+                    // pixel AFTER the lower half's eight is the upper half's first and the pixel BEFORE the upper half's eight is the lower half's
+                    // last -- one v_permlane32_swap and no LDS read (4-9 % faster there; at W = 32 / 64 the swap still needs one conflicted read
+                    // plus selects and loses 2-5 %: profiles/HISTORY.md).
+                    if constexpr (W > 16) {
                         const unsigned lv = *reinterpret_cast<const unsigned*>(src - (q > 0 ? 4 : 0)), rv = *reinterpret_cast<const unsigned*>(src + (q + 8 < W ? 16 : 0));
                         lft = q > 0 ? lv : 0u;
                         rgt = q + 8 < W ? rv : 0u;
                     } else {
                         const auto sw = __builtin_amdgcn_permlane32_swap(own[0], own[3], false, false);
-                        unsigned outer = 0u;
-                        if constexpr (W > 16) {
-                            // (unconditional load, the select on the address and on the value: a conditional load makes the compiler wait for each one)
-                            const bool need = h ? (q + 8 < W) : (q > 0);
-                            const unsigned ov = *reinterpret_cast<const unsigned*>(src + (need ? (h ? 16 : -4) : 0));
-                            outer = need ? ov : 0u;
-                        }
-                        lft = h ? sw[0] : outer;                                 // upper half: the lower half's last dword (its HIGH half is the pixel before)
-                        rgt = h ? outer : sw[1];                                 // lower half: the upper half's first dword (its LOW half is the pixel after)
+                        lft = h ? sw[0] : 0u;                                    // upper half: the lower half's last dword (its HIGH half is the pixel before)
+                        rgt = h ? 0u : sw[1];                                    // lower half: the upper half's first dword (its LOW half is the pixel after)
                     }
                 } else if constexpr (W == 8) {
                     // a lane's eight pixels are one whole row of an 8 x 8 map: no column neighbours; the tap row may leave the map (per lane half)
@@ -254,19 +241,9 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
                     fr[0] = m01; fr[1] = m12; fr[2] = m23;
                     fr[3] = __builtin_amdgcn_alignbyte(rgt, own[3], 2);            // (.. pixel 7 : pixel after): rgt's LOW half
                 }
-                if constexpr (K4) {
-                    if (kx_lo == 0) {                                              // column taps {0, 1}: x[col - 1], x[col]
-                        acc[kyi * 2 + 0] = mfma16_32<CT>(af, fl, acc[kyi * 2 + 0]);
-                        acc[kyi * 2 + 1] = mfma16_32<CT>(af, own, acc[kyi * 2 + 1]);
-                    } else {                                                       // column taps {1, 2}: x[col], x[col + 1]
-                        acc[kyi * 2 + 0] = mfma16_32<CT>(af, own, acc[kyi * 2 + 0]);
-                        acc[kyi * 2 + 1] = mfma16_32<CT>(af, fr, acc[kyi * 2 + 1]);
-                    }
-                } else {
-                    acc[ky * 3 + 0] = mfma16_32<CT>(af, fl, acc[ky * 3 + 0]);
-                    acc[ky * 3 + 1] = mfma16_32<CT>(af, own, acc[ky * 3 + 1]);
-                    acc[ky * 3 + 2] = mfma16_32<CT>(af, fr, acc[ky * 3 + 2]);
-                }
+                acc[ky * 3 + 0] = mfma16_32<CT>(af, fl, acc[ky * 3 + 0]);
+                acc[ky * 3 + 1] = mfma16_32<CT>(af, own, acc[ky * 3 + 1]);
+                acc[ky * 3 + 2] = mfma16_32<CT>(af, fr, acc[ky * 3 + 2]);
             }
         }
         // the next item has landed (this wave's share; behind the barrier everybody's) and nobody reads this stage any more
@@ -281,7 +258,6 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
     const int c = ct * 32 + rl;
 #pragma unroll
     for (int tp = 0; tp < NT; ++tp) {
-        const int t3 = K4 ? (ky_lo + (tp >> 1)) * 3 + kx_lo + (tp & 1) : tp;        // slab position [tap of the 3 x 3 form][m][c]
         if (kpart != 0) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) red[(wave * 16 + v) * 64 + lane] = acc[tp][v];
@@ -295,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
 #pragma unroll
                 for (int k = 1; k < 4; ++k) s += red[((k * 2 + msub) * 16 + v) * 64 + lane];          // fixed order: reproducible
                 const int m = mt * 64 + msub * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
-                if (m < Cout && c < Cin) out[((int64_t)t3 * Cout + m) * Cin + c] = s;
+                if (m < Cout && c < Cin) out[((int64_t)tp * Cout + m) * Cin + c] = s;
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -306,10 +282,9 @@ __global__ __launch_bounds__(512, 2) void wgrad2_band_kernel(Wg2Pieces pieces, f
 int wg2_ksplit(int B, int Cin, int H, int W, int Cout) {
     const int64_t tiles = vs_cdiv(Cout, 64) * vs_cdiv(Cin, 32);
     const int64_t items = W == 8 ? vs_cdiv(B, 4) : (W == 4 ? vs_cdiv(B, 16) : (int64_t)B * (H / (256 / W)));
-    static const int target_wgs = getenv("VS_WGRAD2_WGS") ? atoi(getenv("VS_WGRAD2_WGS")) : 256;      // one workgroup of eight waves per CU
     // ONE round of workgroups: a workgroup's two stages fill a CU, so the 257th workgroup waits for a whole share of the bands to finish
     // (260 -> 256 channels: 36 tiles x 8 shares = 288 workgroups ran 1.8 x as long as 36 x 7 = 252)
-    int64_t ks = target_wgs / tiles;
+    int64_t ks = 256 / tiles;                                                    // one workgroup of eight waves per CU
     if (ks < 1) ks = 1;
     if (ks > items) ks = items;
     const int64_t slab_bytes = (int64_t)Cout * Cin * 9 * 4;
@@ -317,13 +292,13 @@ int wg2_ksplit(int B, int Cin, int H, int W, int Cout) {
     return (int)(ks < 1 ? 1 : ks);
 }
 
-template <int W, int K4>
+template <int W>
 int wg2_launch(int compute, const Wg2Pieces& pieces, float* slabs, int B, int Cin, int H, int Cout, hipStream_t stream) {
     typedef Wg2Geo<W> G;
     constexpr size_t lds = (size_t)2 * G::STAGE;
     static_assert(lds <= 160 * 1024 && lds >= 32 * 1024, "two stages fit the CU; the final reduction needs 32 KiB");
-    auto kb = wgrad2_band_kernel<VS_BF16, W, K4>;
-    auto kh = wgrad2_band_kernel<VS_F16, W, K4>;
+    auto kb = wgrad2_band_kernel<VS_BF16, W>;
+    auto kh = wgrad2_band_kernel<VS_F16, W>;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
@@ -334,15 +309,10 @@ int wg2_launch(int compute, const Wg2Pieces& pieces, float* slabs, int B, int Ci
     const int ks = wg2_ksplit(B, Cin, H, W, Cout);
     const int mtiles = (int)vs_cdiv(Cout, 64), ctiles = (int)vs_cdiv(Cin, 32);
     const dim3 grid((unsigned)((int64_t)mtiles * ctiles * ks));
-    // the column neighbours of a lane's eight pixels: from LDS (1) or from the other lane half by v_permlane32_swap (0).  Same-box A/B of
-    // round 6 (tools/band_bench.py wgrad, VS_BAND_BENCH_VARIANTS="VS_WGRAD2_NB=0,1"): the swap form wins 4-9 % at W = 16 (no LDS read left:
-    // 88.7 vs 93.3, 123.5 vs 135.3, 107.6 vs 113.7 us) and loses 2-5 % at W = 32 / 64 (one conflicted read still needed + the selects).
-    const char* env = getenv("VS_WGRAD2_NB");                     // read per call: A/B runs switch it
-    const int nb = env ? atoi(env) : (W > 16 ? 1 : 0);
     if (compute == VS_BF16)
-        hipLaunchKernelGGL(kb, grid, dim3(512), lds, stream, pieces, slabs, B, Cin, H, Cout, ctiles, ks, nb);
+        hipLaunchKernelGGL(kb, grid, dim3(512), lds, stream, pieces, slabs, B, Cin, H, Cout, ctiles, ks);
     else
-        hipLaunchKernelGGL(kh, grid, dim3(512), lds, stream, pieces, slabs, B, Cin, H, Cout, ctiles, ks, nb);
+        hipLaunchKernelGGL(kh, grid, dim3(512), lds, stream, pieces, slabs, B, Cin, H, Cout, ctiles, ks);
     return VS_OK;
 }
 
@@ -352,9 +322,8 @@ int wg2_launch(int compute, const Wg2Pieces& pieces, float* slabs, int B, int Ci
 int vs_wgrad2_slabs(int B, int Cin, int H, int W, int Cout) { return wg2_ksplit(B, Cin, H, W, Cout); }
 
 // x / dz: up to 64 equal pieces of `maps_per_piece` maps each (vs_conv3_wgrad_band_pieces); slabs [vs_wgrad2_slabs][9][Cout][Cin] fp32
-// k4 != 0: x = parity planes [B][Cin = 4 K][H][W] (K a multiple of 32), dz = the small map; slabs as above (four of nine positions written)
 int vs_wgrad2_go(int compute, int npieces, const void* const* x, const void* const* dz, int maps_per_piece, float* slabs, int B, int Cin, int H, int W, int Cout,
-                 int k4, hipStream_t stream) {
+                 hipStream_t stream) {
     if (npieces < 1 || npieces > WG2_MAX_PIECES) return vs_fail(VS_ERR_UNSUPPORTED, "vs_conv3_wgrad_band (v2): %d pieces", npieces);
     Wg2Pieces p = {};
     for (int i = 0; i < npieces; ++i) {
@@ -363,7 +332,7 @@ int vs_wgrad2_go(int compute, int npieces, const void* const* x, const void* con
     }
     p.maps_per_piece = maps_per_piece;
 #define VS_WG2_CASE(WV) \
-    case WV: return k4 ? wg2_launch<WV, 1>(compute, p, slabs, B, Cin, H, Cout, stream) : wg2_launch<WV, 0>(compute, p, slabs, B, Cin, H, Cout, stream);
+    case WV: return wg2_launch<WV>(compute, p, slabs, B, Cin, H, Cout, stream);
     switch (W) {
         VS_WG2_CASE(64)
         VS_WG2_CASE(32)

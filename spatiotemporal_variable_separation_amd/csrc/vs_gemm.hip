@@ -41,10 +41,9 @@ int launch(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, in
     const int batch = epi.splits_per_batch > 0 ? plan.batch : 1;
     dim3 grid((unsigned)vs_cdiv(N, BN), (unsigned)vs_cdiv(M, BM), (unsigned)(plan.splits * batch));
     // XCD runs (Epi::xcd_runs) from 64 workgroups upwards: PMC on the WaveEq decoder layers (3328 x 1200 x 1200, 988 tiles of 64 x 64) showed
-    // 77 MB fetched per launch for 11 MB of operands -- each of the eight L2s pulled the whole of A and B.  VS_GEMM_XCD=0: the plain map.
-    static const int xcd_mode = getenv("VS_GEMM_XCD") ? atoi(getenv("VS_GEMM_XCD")) : 1;
+    // 77 MB fetched per launch for 11 MB of operands -- each of the eight L2s pulled the whole of A and B.
     Epi e = epi;
-    e.xcd_runs = xcd_mode && (int64_t)grid.x * grid.y * grid.z >= 64;
+    e.xcd_runs = (int64_t)grid.x * grid.y * grid.z >= 64;
     hipLaunchKernelGGL((gemm_kernel<CT, Dense<CT, LA>, Dense<CT, LB>, BM, BN, BK>), grid, dim3(256), smem, stream, a, b, M, N,
                        K, (int)plan.k_tiles_per_split, e, slabs);
     VS_CHECK_LAUNCH("vs_gemm");
@@ -114,11 +113,8 @@ int launch_p8(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M,
             attr_set = true;
         }
         dim3 grid((unsigned)(pp.tiles_m * pp.tiles_n), 1, (unsigned)(pp.splits * batch));
-        static const int plain = getenv("VS_GEMM_P8_QUICK") && atoi(getenv("VS_GEMM_P8_QUICK")) == 0;
-        Epi e = epi;
-        e.p8_plain = plain;
         hipLaunchKernelGGL(kfn, grid, dim3(512), lds, stream, (const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, N, K, (int)pp.k_tiles_per_split,
-                           pp.tiles_n, e, slabs);
+                           pp.tiles_n, epi, slabs);
         VS_CHECK_LAUNCH("vs_gemm (staggered 256-row tile)");
         return VS_OK;
     }
@@ -366,8 +362,6 @@ extern "C" int vs_gemm_adam(int compute, int64_t M, int64_t N, int64_t K, const 
     Epi epi{param, N, VS_F32, alpha, nullptr, VS_ACT_NONE, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     epi.adam_m = exp_avg; epi.adam_v = exp_avg_sq; epi.adam_shadow = (unsigned short*)shadow; epi.adam_shadow_dtype = shadow_dtype;
     epi.adam_step = step; epi.adam_skipped = skipped; epi.adam_guard = vs_g_exchange_guard;
-    static const int adam_pipe = getenv("VS_ADAM_PIPE") ? atoi(getenv("VS_ADAM_PIPE")) : 1;      // 0: one row piece at a time; 1: four ahead; 3: + non-temporal state
-    epi.adam_pipe = adam_pipe;
     epi.adam_lr = lr; epi.adam_beta1 = beta1; epi.adam_beta2 = beta2; epi.adam_eps = (float)eps;
     MidPlan mp{true, 1, vs_cdiv(K, BIG_BK), (int)vs_cdiv(M, 128), (int)vs_cdiv(N, 128), 5};
     if ((int64_t)mp.tiles_m * mp.tiles_n > 0x7fffffffll) return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_adam: too many tiles");
@@ -467,7 +461,7 @@ extern "C" int vs_gemm(int compute, int64_t M, int64_t N, int64_t K, const void*
     VS_CHECK_ARG(!mask || ldmask >= N, "vs_gemm: ldmask too small");
     VS_CHECK_ARG(act >= VS_ACT_NONE && act <= VS_ACT_ELU, "vs_gemm: bad activation");
     Epi epi{C, ldc, c_dtype, alpha, bias, act, mask, ldmask, mask_dtype, mask_act, accumulate, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    Plan plan = make_plan(compute, M, N, K, 1, layout_a == LR && layout_b == LR);
+    Plan plan = make_plan(compute, M, N, K);
     const P8Plan pp = p8_plan_for(compute, M, N, K, 1, A, lda, layout_a, B, ldb, layout_b, 0, 0);
     BigPlan bp = big_plan_for(compute, M, N, K, 1, A, lda, layout_a, B, ldb, layout_b, 0, 0);
     if (pp.use) bp.use = false;

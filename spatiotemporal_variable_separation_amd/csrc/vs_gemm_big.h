@@ -472,7 +472,7 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(const unsigned short* Ap,
 // ~26 us of a 63 us launch at 3328 x 4096 x 1200 are launch, ring fill and the 54 MB of fp32 output), and enough work that the
 // 256-wide tile is not mostly padding.  VS_GEMM_BIG=0 disables, =2 takes it whenever the operands allow (tests; split-K off).
 // k_tiles_per_split counts K tiles of BIG_BK.  Measured (MI355X, bf16, random operands): 3328 x 4096 x 1200 63 us (128x64 tile:
-// 76 us), 4096^3 158 us = 870 TFLOP/s (128x128 LDS-DMA tile: 184 us).  Timing-only variants of the loop (VS_BIG_DIAG): without
+// 76 us), 4096^3 158 us = 870 TFLOP/s (128x128 LDS-DMA tile: 184 us).  Timing-only variants of the loop: without
 // the MFMAs and fragment reads the DMA ring alone runs at 0.57 us per 32 KiB tile (57 GB/s per CU), without real DMA traffic
 // the multiply alone at 0.74 us per tile (MFMA-issue bound at the clock the chip holds under load), both together at 1.03 us.
 struct BigPlan { bool use; int splits; int64_t k_tiles_per_split; int tiles_m, tiles_n; };

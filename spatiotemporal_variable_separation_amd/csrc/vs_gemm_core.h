@@ -58,8 +58,6 @@ struct Epi {
     const float* fl_full; const int* fl_tdev; int fl_ae_shift, fl_first, fl_G, fl_T;
     const float* fl_up; float fl_l_ae, fl_l_pred, fl_inv_ae, fl_inv_pred;        // k = *fl_up * l * 2 * (1 / count), in this order
     void* fl_dz; int fl_dz_dtype; float* fl_partials;
-    int adam_pipe;                       // fused optimizer: state of four row pieces requested ahead (VS_ADAM_PIPE=0: one piece at a time)
-    int p8_plain;                        // VS_GEMM_P8_QUICK=0 (measurements): interior tiles of the staggered tile take the general stores too
 };
 
 // XCD-aware, bijective block -> tile index (blocks b and b + 8 share an XCD under round-robin dispatch: speed only)
@@ -342,12 +340,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(OpA A, OpB B, int64_t M, int6
         tile_commit<CT, OpA::layout, BM, BK>(sA, ra);
         tile_commit<CT, OpB::layout, BN, BK>(sB, rb);
         __syncthreads();
-#ifndef VS_DIAG_NO_GLOBAL
         if (kt + 1 < kt_end) {       // prefetch next tile into registers; lands while the MFMAs below run
             tile_fetch<CT, OpA, BM, BK>(A, sta, m0, (kt + 1) * BK, ra);
             tile_fetch<CT, OpB, BN, BK>(B, stb, n0, (kt + 1) * BK, rb);
         }
-#endif
         if constexpr (CT != VS_F32) {
 #pragma unroll
             for (int kk = 0; kk < BK; kk += 16) {
@@ -361,13 +357,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(OpA A, OpB B, int64_t M, int6
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-#ifdef VS_DIAG_NO_MFMA
-                        acc[i][j][0] += (float)fa[i][0] + (float)fb[j][0];          // keeps the LDS reads alive, no matrix work (diagnostic)
-#else
-                        acc[i][j] = mfma16_32<CT>(fa[i], fb[j], acc[i][j]);
-#endif
-                    }
+                    for (int j = 0; j < TN; ++j) acc[i][j] = mfma16_32<CT>(fa[i], fb[j], acc[i][j]);
             }
         } else {
             // parity mode: two-level summation.  Each K tile (16 products) is accumulated in a fresh MFMA chain and then
@@ -475,7 +465,7 @@ struct Plan { int bm, bn, splits; int64_t k_tiles_per_split; int batch = 1; };
 
 template <int CT> constexpr int bk_of() { return CT != VS_F32 ? 64 : 16; }
 
-Plan make_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch = 1, bool forward_layout = false) {
+Plan make_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch = 1) {
     const int bk = compute != VS_F32 ? 64 : 16;
     Plan p;
     // Tile choice (measured on the config-2 shapes, tools/gemm_bench.py): the kernel keeps ~3 workgroups (12 waves) per CU
@@ -487,12 +477,8 @@ Plan make_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch = 1, 
     // 128x64 only from ~2.3 tiles per CU upwards.  Below that the step is faster with 64x64 tiles although the isolated kernel is
     // not (WaveEq B=128, whole recorded step: 1.51 -> 1.43 ms; 3328x1200 outputs are 494 tiles of 128x64 but 988 of 64x64, and
     // the 256x1200 encoder outputs 38 against 76): the launches overlap with the gradient branches, where more and lighter
-    // workgroups fill the CUs the neighbours leave.  VS_GEMM_T64_BELOW moves the threshold (0 = the round-1 rule).
-    static const int64_t t64_below_any = getenv("VS_GEMM_T64_BELOW") ? atoll(getenv("VS_GEMM_T64_BELOW")) : 600;
-    // R x R operands = a Linear layer's FORWARD launch: nothing runs beside the decoder's forward chain (the gradient branches that made the
-    // light tiles win exist in backward only), so the threshold may differ there (VS_GEMM_T64_BELOW_RR)
-    static const int64_t t64_below_rr = getenv("VS_GEMM_T64_BELOW_RR") ? atoll(getenv("VS_GEMM_T64_BELOW_RR")) : t64_below_any;
-    const int64_t t64_below = forward_layout ? t64_below_rr : t64_below_any;
+    // workgroups fill the CUs the neighbours leave.
+    constexpr int64_t t64_below = 600;
     if (const char* f = getenv("VS_GEMM_TILE")) {                       // debugging aid: force a tile ("128x128", "128x64", "64x64")
         p.bm = atoi(f); const char* x = strchr(f, 'x'); p.bn = x ? atoi(x + 1) : p.bm;
     } else if (K <= 512 && t128 >= 256) { p.bm = 64; p.bn = 64; }      // short K: prologue/epilogue bound, many small tiles win

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
         // flight instead of 3 (one piece at a time ran the 640 MB launches of the WaveEq encoders at 3.3 TB/s: latency x bytes in flight).
         // (whole tiles only -- no per-row branch: a branch around a request makes the compiler wait for EVERY outstanding load, vmcnt(0),
         // at the next use, which serialises the groups again)
-        if (epi.adam_pipe && m0 + 128 <= M && nn + 3 < N && ((epi.ldc | nn) & 3) == 0 &&
+        if (m0 + 128 <= M && nn + 3 < N && ((epi.ldc | nn) & 3) == 0 &&
             (((uintptr_t)epi.C | (uintptr_t)epi.adam_m | (uintptr_t)epi.adam_v) & 15) == 0 && (!epi.adam_shadow || ((uintptr_t)epi.adam_shadow & 7) == 0)) {
             constexpr int G = 4;
             f32x4 p[2][G], mm[2][G], vv[2][G];
@@ -245,11 +245,8 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
             const float* __restrict__ Mp = epi.adam_m + idx0;
             const float* __restrict__ Vp = epi.adam_v + idx0;
             const int sdt = epi.adam_shadow_dtype;
-            // adam_pipe & 2: the fp32 master and the two moments are touched once per step -- non-temporal loads and stores (they do not displace
-            // what the step re-reads from the L2s / the Infinity Cache); the 16-bit copy, read by the next forward pass, keeps the default policy
-            const bool nt = (epi.adam_pipe & 2) != 0;
-            auto ld4 = [&](const float* q) { return nt ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)) : *reinterpret_cast<const f32x4*>(q); };
-            auto st4 = [&](float* q, const f32x4& v) { if (nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(q)); else *reinterpret_cast<f32x4*>(q) = v; };
+            auto ld4 = [&](const float* q) { return *reinterpret_cast<const f32x4*>(q); };
+            auto st4 = [&](float* q, const f32x4& v) { *reinterpret_cast<f32x4*>(q) = v; };
 #pragma unroll
             for (int t = 0; t < G; ++t) {
                 p[0][t] = ld4(Pp + t * rstep);
@@ -341,10 +338,9 @@ int mid_launch(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M
         const int tiles_m = (int)vs_cdiv(M, 128), tiles_n = (int)vs_cdiv(N, 128);
         dim3 grid((unsigned)(tiles_m * tiles_n), 1, (unsigned)(splits * batch));
         // several splits: the XCD runs go over (split, tile) -- the 256 x 1200 x 20480 encoder layer (20 tiles x 22 splits) fetched 147 MB for
-        // 60 MB of operands with the splits of one K chunk spread over all eight L2s.  VS_GEMM_XCD=0: runs over the tiles of each split only.
-        static const int xcd_mode = getenv("VS_GEMM_XCD") ? atoi(getenv("VS_GEMM_XCD")) : 1;
+        // 60 MB of operands with the splits of one K chunk spread over all eight L2s.
         Epi e_runs = epi;
-        e_runs.xcd_runs = xcd_mode && grid.z > 1;
+        e_runs.xcd_runs = grid.z > 1;
         const Epi& epi_l = e_runs;
         auto go = [&](auto kfn, int st_, bool& attr_set) -> int {
             const int lds = st_ * MID_TILE_BYTES;

@@ -379,7 +379,7 @@ __global__ __launch_bounds__(512, MI == 4 ? 2 : 4) void gemm_p8_kernel(const uns
         // elements, ~36 us of a 64 us launch at 3328 x 4096 x 1200 by the stamps of tools/probes/p8_bench.hip), one rolling window of DEPTH
         // target requests that is refilled as it is consumed (the hardware counter waits are the compiler's, exact in straight-line code), and
         // the four stores of a row back to back (a full 128-byte line of the gradient).  Same arithmetic, same order of the partial sums.
-        const bool quick = !epi.p8_plain && (m0 + BM <= M) && (n0 + BN <= N) && epi.act == (LOSS == 2 ? VS_ACT_SIGMOID : VS_ACT_NONE) && epi.fl_dz_dtype == CT;
+        const bool quick = (m0 + BM <= M) && (n0 + BN <= N) && epi.act == (LOSS == 2 ? VS_ACT_SIGMOID : VS_ACT_NONE) && epi.fl_dz_dtype == CT;
         auto loss_quick = [&]() {
             constexpr int ACT = LOSS == 2 ? VS_ACT_SIGMOID : VS_ACT_NONE;
             constexpr int RQ = 2 * NI, ROWS = 2 * MI, Q = ROWS * RQ, DEPTH = P8_LOSS_DEPTH < Q ? P8_LOSS_DEPTH : Q;
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(512, MI == 4 ? 2 : 4) void gemm_p8_kernel(const uns
         // at 3328 x 4096 x 1200, stamps of tools/probes/p8_bench.hip).  Here the mask bits come through a rolling window of DEPTH requests, the
         // test `mask > 0` is made on the 16 bits themselves (positive, non-zero, not a NaN: what the float comparison says) and the stores of a
         // row follow each other (full 128-byte lines).
-        const bool quick = !epi.p8_plain && fast && !slab_base && (m0 + BM <= M) && (n0 + BN <= N) && epi.c_dtype == CT && (epi.act == VS_ACT_NONE || epi.act == VS_ACT_RELU) &&
+        const bool quick = fast && !slab_base && (m0 + BM <= M) && (n0 + BN <= N) && epi.c_dtype == CT && (epi.act == VS_ACT_NONE || epi.act == VS_ACT_RELU) &&
                            (!epi.mask || epi.mask_dtype == VS_BF16 || epi.mask_dtype == VS_F16);
         if (quick) {
             auto store_quick = [&](auto actc) {
@@ -655,23 +655,14 @@ inline P8Plan make_p8_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t
     }
     // One tile row, long K (the encoders' first layer, 256 x 1200 x 20480: the weight matrix is streamed once, HBM-bound): 256 x 128 tiles, K split
     // over ~one round of CUs into fp32 slabs (reduced by splitk_reduce_kernel).  Measured against the 128 x 128 ring tile (20 tiles x 22 splits):
-    // alone, cold operands 43.5 -> 38.1 us; replayed WaveEq step, two interleaved pairs 1.2414 / 1.2337 -> 1.2114 / 1.2079 ms.  VS_GEMM_P8_SPLIT=0: off.
+    // alone, cold operands 43.5 -> 38.1 us; replayed WaveEq step, two interleaved pairs 1.2414 / 1.2337 -> 1.2114 / 1.2079 ms.
     {
-        const char* env_sp = getenv("VS_GEMM_P8_SPLIT");
-        // VS_GEMM_P8_SPLIT_NI=2: 256 x 256 tiles (the activation panel is read by half as many tile columns, twice the splits and slab bytes)
-        const char* env_sni = getenv("VS_GEMM_P8_SPLIT_NI");
-        const int sni = env_sni && atoi(env_sni) == 2 ? 2 : 1;
-        const int64_t kt = p.k_tiles_per_split, tn = vs_cdiv(N, 128 * sni);
-        if (!(env_sp && atoi(env_sp) == 0) && M > 128 && M <= 256 && N >= 512 && kt >= 64 && tn * batch <= 64 && (double)N / (tn * 128.0 * sni) >= 0.85) {
-            // VS_GEMM_P8_SPLIT_MI=2: 128 x 128 tiles (100 registers per lane, two workgroups per CU: a workgroup fits beside a workgroup of the integrator's
-            // forward kernel, under which E_s's first layer runs in the WaveEq step)
-            const char* env_smi = getenv("VS_GEMM_P8_SPLIT_MI");
-            const int tm = env_smi && atoi(env_smi) == 2 ? 2 : 1;
-            int64_t splits = 250 / (tn * tm * batch);
+        const int64_t kt = p.k_tiles_per_split, tn = vs_cdiv(N, 128);
+        if (M > 128 && M <= 256 && N >= 512 && kt >= 64 && tn * batch <= 64 && (double)N / (tn * 128.0) >= 0.85) {
+            int64_t splits = 250 / (tn * batch);
             if (splits > kt / 8) splits = kt / 8;
             if (splits >= 2) {
-                p.ni = sni;
-                if (tm == 2 && sni == 1) { p.mi = 2; p.tiles_m = (int)vs_cdiv(M, 128); }
+                p.ni = 1;
                 p.tiles_n = (int)tn;
                 p.k_tiles_per_split = vs_cdiv(kt, splits);
                 p.splits = (int)vs_cdiv(kt, p.k_tiles_per_split);

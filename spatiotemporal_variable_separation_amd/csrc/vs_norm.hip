@@ -1325,8 +1325,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_v8_kernel(const unsigned shor
 
 // the 16-byte forms apply: one 16-bit type throughout, small-map rows of whole pieces, 16-byte aligned tensors
 inline bool v8_ok(int d0, int d1, int Wsmall, const void* p0, const void* p1, const void* p2 = nullptr) {
-    static const int mode = getenv("VS_POOL_V8") ? atoi(getenv("VS_POOL_V8")) : 1;
-    return mode && vs_is16(d0) && d0 == d1 && Wsmall % 8 == 0 && ((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) % 16 == 0;
+    return vs_is16(d0) && d0 == d1 && Wsmall % 8 == 0 && ((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) % 16 == 0;
 }
 
 inline unsigned ew_grid(int64_t total) {
@@ -1375,9 +1374,8 @@ extern "C" int vs_bn_stats_ub(const void* x, int x_dtype, int B, int C, int64_t 
 
 // 1 when vs_bn_train_fwd_small serves the tensor: one call group, slabs of <= 8192 elements, 16-byte vectors
 extern "C" int vs_bn_train_fwd_small_supported(int x_dtype, int B, int C, int64_t HW) {
-    static const int small_mode = getenv("VS_BN_SMALL") ? atoi(getenv("VS_BN_SMALL")) : 1;
     const int w = x_dtype == VS_F32 ? 4 : 8;
-    return small_mode && vs_dtype_ok(x_dtype) && B > 0 && C >= 32 && HW > 0 && HW % 8 == 0 && (int64_t)B * HW <= 8192 && HW % w == 0;
+    return vs_dtype_ok(x_dtype) && B > 0 && C >= 32 && HW > 0 && HW % 8 == 0 && (int64_t)B * HW <= 8192 && HW % w == 0;
 }
 
 // Training-mode BatchNorm2d forward of ONE reference call on a small tensor in one launch: mean / invstd [C] (kept for backward),
@@ -1391,14 +1389,14 @@ extern "C" int vs_bn_train_fwd_small(const void* x, int x_dtype, void* y, int y_
     if (!vs_bn_train_fwd_small_supported(x_dtype, B, C, HW) || ((uintptr_t)x | (uintptr_t)y) % 16 != 0)
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_bn_train_fwd_small: tensor not served (use vs_bn_stats + vs_bn_act_fwd)");
     const int64_t nvec = (int64_t)B * HW / (x_dtype == VS_F32 ? 4 : 8);
-#define VS_BN_SMALL(NV)                                                                                                                 \
+#define VS_BN_SMALL_CASE(NV)                                                                                                                 \
     hipLaunchKernelGGL(bn_fwd_small_kernel<NV>, dim3(C), dim3(256), 0, (hipStream_t)stream, x, x_dtype, y, y_dtype, gamma, beta, act, mean, invstd, \
                        running_mean, running_var, momentum, eps, B, C, (int)HW)
-    if (nvec <= 256) VS_BN_SMALL(1);
-    else if (nvec <= 512) VS_BN_SMALL(2);
-    else if (nvec <= 1024) VS_BN_SMALL(4);
-    else VS_BN_SMALL(8);
-#undef VS_BN_SMALL
+    if (nvec <= 256) VS_BN_SMALL_CASE(1);
+    else if (nvec <= 512) VS_BN_SMALL_CASE(2);
+    else if (nvec <= 1024) VS_BN_SMALL_CASE(4);
+    else VS_BN_SMALL_CASE(8);
+#undef VS_BN_SMALL_CASE
     VS_CHECK_LAUNCH("vs_bn_train_fwd_small");
     return VS_OK;
 }
@@ -1417,15 +1415,15 @@ extern "C" int vs_bn_train_fwd_small_groups(const void* x, int x_dtype, void* y,
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_bn_train_fwd_small_groups: tensor not served (use vs_bn_stats + vs_bn_act_fwd)");
     const int64_t nvec = (int64_t)Bg * HW / (x_dtype == VS_F32 ? 4 : 8);
     const dim3 grid(C, groups);
-#define VS_BN_SMALL(NV)                                                                                                                 \
+#define VS_BN_SMALL_CASE(NV)                                                                                                                 \
     hipLaunchKernelGGL(bn_fwd_small_kernel<NV>, grid, dim3(256), 0, (hipStream_t)stream, x, x_dtype, y, y_dtype, gamma, beta, act, mean, invstd, \
                        (float*)nullptr, (float*)nullptr, momentum, eps, Bg, C, (int)HW, (const float*)nullptr, 0, (const float*)nullptr, (void*)nullptr,  \
                        (const float*)nullptr, (float*)nullptr, (void*)nullptr, running_mean ? var_scratch : (float*)nullptr)
-    if (nvec <= 256) VS_BN_SMALL(1);
-    else if (nvec <= 512) VS_BN_SMALL(2);
-    else if (nvec <= 1024) VS_BN_SMALL(4);
-    else VS_BN_SMALL(8);
-#undef VS_BN_SMALL
+    if (nvec <= 256) VS_BN_SMALL_CASE(1);
+    else if (nvec <= 512) VS_BN_SMALL_CASE(2);
+    else if (nvec <= 1024) VS_BN_SMALL_CASE(4);
+    else VS_BN_SMALL_CASE(8);
+#undef VS_BN_SMALL_CASE
     VS_CHECK_LAUNCH("vs_bn_train_fwd_small_groups");
     if (running_mean) {
         hipLaunchKernelGGL(bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, var_scratch, groups, C, running_mean,
@@ -1449,23 +1447,22 @@ extern "C" int vs_bn_train_fwd_small_slabs(const float* slabs, int nslabs, const
     if (!vs_bn_train_fwd_small_supported(z_dtype, B, C, HW) || ((uintptr_t)slabs | (uintptr_t)z | (uintptr_t)y) % 16 != 0)
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_bn_train_fwd_small_slabs: tensor not served (vs_slab_sum + vs_bn_stats + vs_bn_act_fwd)");
     const int64_t nvec = (int64_t)B * HW / 8;
-#define VS_BN_SMALL(NV)                                                                                                                 \
+#define VS_BN_SMALL_CASE(NV)                                                                                                                 \
     hipLaunchKernelGGL(bn_fwd_small_kernel<NV>, dim3(C), dim3(256), 0, (hipStream_t)stream, (const void*)nullptr, z_dtype, y, y_dtype, gamma, beta, act, mean, \
                        invstd, running_mean, running_var, momentum, eps, B, C, (int)HW, slabs, nslabs, bias, z, skip, xnew, xnew16)
-    if (nvec <= 256) VS_BN_SMALL(1);
-    else if (nvec <= 512) VS_BN_SMALL(2);
-    else if (nvec <= 1024) VS_BN_SMALL(4);
-    else VS_BN_SMALL(8);
-#undef VS_BN_SMALL
+    if (nvec <= 256) VS_BN_SMALL_CASE(1);
+    else if (nvec <= 512) VS_BN_SMALL_CASE(2);
+    else if (nvec <= 1024) VS_BN_SMALL_CASE(4);
+    else VS_BN_SMALL_CASE(8);
+#undef VS_BN_SMALL_CASE
     VS_CHECK_LAUNCH("vs_bn_train_fwd_small_slabs");
     return VS_OK;
 }
 
 // One (call group, channel) slab of 8 193 .. 131 072 16-bit elements: read once, held in the registers of a 1024-thread workgroup
 extern "C" int vs_bn_train_fwd_slab_supported(int x_dtype, int Bg, int C, int64_t HW) {
-    static const int slab_mode = getenv("VS_BN_SLAB") ? atoi(getenv("VS_BN_SLAB")) : 1;
     const int64_t n = (int64_t)Bg * HW;
-    return slab_mode && vs_is16(x_dtype) && Bg > 0 && C > 0 && HW >= 8 && HW <= 8192 && (HW & (HW - 1)) == 0 && n > 8192 && n <= 131072;
+    return vs_is16(x_dtype) && Bg > 0 && C > 0 && HW >= 8 && HW <= 8192 && (HW & (HW - 1)) == 0 && n > 8192 && n <= 131072;
 }
 
 // Training-mode BatchNorm2d (+ activation) forward of `groups` reference calls stacked along the batch axis, every (call, channel) slab read
@@ -1485,7 +1482,7 @@ extern "C" int vs_bn_train_fwd_slab(const void* x, int x_dtype, void* y, int y_d
     float* rm = groups == 1 ? running_mean : nullptr;
     float* rv = groups == 1 ? running_var : nullptr;
     hipStream_t st = (hipStream_t)stream;
-#define VS_BN_SLAB(NV, AV)                                                                                                              \
+#define VS_BN_SLAB_CASE(NV, AV)                                                                                                              \
     do {                                                                                                                                  \
         if (x_dtype == VS_BF16)                                                                                                           \
             hipLaunchKernelGGL((bn_fwd_slab_kernel<NV, AV, VS_BF16>), grid, dim3(1024), 0, st, (const unsigned short*)x, y, y_dtype, gamma, beta, act, mean, \
@@ -1496,16 +1493,16 @@ extern "C" int vs_bn_train_fwd_slab(const void* x, int x_dtype, void* y, int y_d
     } while (0)
 #define VS_BN_SLAB_NV(AV)                      \
     do {                                       \
-        if (nvec <= 2048) VS_BN_SLAB(2, AV);   \
-        else if (nvec <= 4096) VS_BN_SLAB(4, AV);  \
-        else if (nvec <= 8192) VS_BN_SLAB(8, AV);  \
-        else VS_BN_SLAB(16, AV);               \
+        if (nvec <= 2048) VS_BN_SLAB_CASE(2, AV);   \
+        else if (nvec <= 4096) VS_BN_SLAB_CASE(4, AV);  \
+        else if (nvec <= 8192) VS_BN_SLAB_CASE(8, AV);  \
+        else VS_BN_SLAB_CASE(16, AV);               \
     } while (0)
     if (act == VS_ACT_LEAKY) VS_BN_SLAB_NV(VS_ACT_LEAKY);
     else if (act == VS_ACT_NONE) VS_BN_SLAB_NV(VS_ACT_NONE);
     else VS_BN_SLAB_NV(-1);
 #undef VS_BN_SLAB_NV
-#undef VS_BN_SLAB
+#undef VS_BN_SLAB_CASE
     VS_CHECK_LAUNCH("vs_bn_train_fwd_slab");
     if (ub) {
         hipLaunchKernelGGL(bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, st, mean, var_scratch, groups, C, running_mean, running_var, momentum);
@@ -1583,21 +1580,20 @@ extern "C" int vs_bn_act_bwd_gsum(const void* dy, int dy_dtype, const void* x, i
     }
     {
         // one launch for small slabs (see bn_bwd_small_kernel); enough workgroups to be worth it
-        static const int small_mode = getenv("VS_BN_SMALL") ? atoi(getenv("VS_BN_SMALL")) : 1;
         const int64_t nslab = (int64_t)(B / groups) * HW;
         const int wv = x_dtype == VS_F32 ? 4 : 8;
-        if (small_mode && vec == 1 && x_dtype == dy_dtype && nslab <= 8192 && HW < (1 << 20) &&
+        if (vec == 1 && x_dtype == dy_dtype && nslab <= 8192 && HW < (1 << 20) &&
             ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 16 == 0 && (int64_t)C * groups >= 32) {
             const int64_t nvec = nslab / wv;
             const dim3 grid(C, groups);
-#define VS_BN_SMALL(NV)                                                                                                              \
+#define VS_BN_SMALL_CASE(NV)                                                                                                              \
             hipLaunchKernelGGL(bn_bwd_small_kernel<NV>, grid, dim3(256), 0, (hipStream_t)stream, dy, x, x_dtype, mean, invstd, gamma, beta, act,  \
                                dbeta, dgamma, dx, dx_dtype, B / groups, C, (int)HW, training, gs)
-            if (nvec <= 256) VS_BN_SMALL(1);
-            else if (nvec <= 512) VS_BN_SMALL(2);
-            else if (nvec <= 1024) VS_BN_SMALL(4);
-            else VS_BN_SMALL(8);
-#undef VS_BN_SMALL
+            if (nvec <= 256) VS_BN_SMALL_CASE(1);
+            else if (nvec <= 512) VS_BN_SMALL_CASE(2);
+            else if (nvec <= 1024) VS_BN_SMALL_CASE(4);
+            else VS_BN_SMALL_CASE(8);
+#undef VS_BN_SMALL_CASE
             VS_CHECK_LAUNCH("vs_bn_act_bwd (small slabs)");
             if (dbeta_sum && !gs.out_a) {
                 hipLaunchKernelGGL(group_sum2_kernel, dim3((unsigned)vs_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, dbeta, dgamma, groups, C, dbeta_sum,
@@ -1609,14 +1605,13 @@ extern "C" int vs_bn_act_bwd_gsum(const void* dy, int dy_dtype, const void* x, i
     }
     {
         // slabs of 8 193 .. 65 536 16-bit elements: x and dy resident in the registers of a 1024-thread workgroup, both read ONCE (bn_bwd_slab_kernel)
-        static const int slab_mode = getenv("VS_BN_SLAB") ? atoi(getenv("VS_BN_SLAB")) : 1;
         const int64_t nslab = (int64_t)(B / groups) * HW;
-        if (slab_mode && training && vec == 1 && vs_is16(x_dtype) && x_dtype == dy_dtype && nslab > 8192 && nslab <= 65536 && HW <= 8192 && (HW & (HW - 1)) == 0 &&
+        if (training && vec == 1 && vs_is16(x_dtype) && x_dtype == dy_dtype && nslab > 8192 && nslab <= 65536 && HW <= 8192 && (HW & (HW - 1)) == 0 &&
             ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 16 == 0) {
             const int64_t nvec = nslab / 8;
             const dim3 grid(C, groups);
             hipStream_t st = (hipStream_t)stream;
-#define VS_BN_SLAB(NV, AV)                                                                                                              \
+#define VS_BN_SLAB_CASE(NV, AV)                                                                                                              \
             do {                                                                                                                          \
                 if (x_dtype == VS_BF16)                                                                                                   \
                     hipLaunchKernelGGL((bn_bwd_slab_kernel<NV, AV, VS_BF16>), grid, dim3(1024), 0, st, (const unsigned short*)dy, (const unsigned short*)x, mean, \
@@ -1627,15 +1622,15 @@ extern "C" int vs_bn_act_bwd_gsum(const void* dy, int dy_dtype, const void* x, i
             } while (0)
 #define VS_BN_SLAB_NV(AV)                          \
             do {                                   \
-                if (nvec <= 2048) VS_BN_SLAB(2, AV);   \
-                else if (nvec <= 4096) VS_BN_SLAB(4, AV);  \
-                else VS_BN_SLAB(8, AV);            \
+                if (nvec <= 2048) VS_BN_SLAB_CASE(2, AV);   \
+                else if (nvec <= 4096) VS_BN_SLAB_CASE(4, AV);  \
+                else VS_BN_SLAB_CASE(8, AV);            \
             } while (0)
             if (act == VS_ACT_LEAKY) VS_BN_SLAB_NV(VS_ACT_LEAKY);
             else if (act == VS_ACT_NONE) VS_BN_SLAB_NV(VS_ACT_NONE);
             else VS_BN_SLAB_NV(-1);
 #undef VS_BN_SLAB_NV
-#undef VS_BN_SLAB
+#undef VS_BN_SLAB_CASE
             VS_CHECK_LAUNCH("vs_bn_act_bwd (resident slabs)");
             if (dbeta_sum && !gs.out_a) {
                 hipLaunchKernelGGL(group_sum2_kernel, dim3((unsigned)vs_cdiv(C, 256)), dim3(256), 0, st, dbeta, dgamma, groups, C, dbeta_sum, dgamma_sum);
@@ -1645,31 +1640,30 @@ extern "C" int vs_bn_act_bwd_gsum(const void* dy, int dy_dtype, const void* x, i
         }
     }
     {
-        // slabs of 65 537 .. 131 072 elements: x in registers, dy in LDS + a re-read tail (bn_bwd_slab_lds_kernel).  VS_BN_SLAB=2: not these.
-        static const int slab_mode = getenv("VS_BN_SLAB") ? atoi(getenv("VS_BN_SLAB")) : 1;
+        // slabs of 65 537 .. 131 072 elements: x in registers, dy in LDS + a re-read tail (bn_bwd_slab_lds_kernel)
         const int64_t nslab = (int64_t)(B / groups) * HW;
-        if (slab_mode == 1 && training && vec == 1 && vs_is16(x_dtype) && x_dtype == dy_dtype && nslab > 65536 && nslab <= 131072 && HW <= 8192 &&
+        if (training && vec == 1 && vs_is16(x_dtype) && x_dtype == dy_dtype && nslab > 65536 && nslab <= 131072 && HW <= 8192 &&
             (HW & (HW - 1)) == 0 && ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 16 == 0) {
             const int64_t nvec = nslab / 8;
             const dim3 grid(C, groups);
             hipStream_t st = (hipStream_t)stream;
             int rc;
-#define VS_BN_SLAB(NV, AV)                                                                                                                            \
+#define VS_BN_SLAB_CASE(NV, AV)                                                                                                                            \
             rc = x_dtype == VS_BF16 ? launch_bn_bwd_slab_lds<NV, AV, VS_BF16>(grid, st, dy, x, mean, invstd, gamma, beta, act, dbeta, dgamma, dx, dx_dtype,   \
                                                                               B / groups, C, (int)HW, gs)                                              \
                                     : launch_bn_bwd_slab_lds<NV, AV, VS_F16>(grid, st, dy, x, mean, invstd, gamma, beta, act, dbeta, dgamma, dx, dx_dtype,    \
                                                                              B / groups, C, (int)HW, gs)
 #define VS_BN_SLAB_NV(AV)                              \
             do {                                       \
-                if (nvec <= 12288) VS_BN_SLAB(12, AV); \
-                else if (nvec <= 14336) VS_BN_SLAB(14, AV); \
-                else VS_BN_SLAB(16, AV);               \
+                if (nvec <= 12288) VS_BN_SLAB_CASE(12, AV); \
+                else if (nvec <= 14336) VS_BN_SLAB_CASE(14, AV); \
+                else VS_BN_SLAB_CASE(16, AV);               \
             } while (0)
             if (act == VS_ACT_LEAKY) VS_BN_SLAB_NV(VS_ACT_LEAKY);
             else if (act == VS_ACT_NONE) VS_BN_SLAB_NV(VS_ACT_NONE);
             else VS_BN_SLAB_NV(-1);
 #undef VS_BN_SLAB_NV
-#undef VS_BN_SLAB
+#undef VS_BN_SLAB_CASE
             if (rc != VS_OK) return rc;
             VS_CHECK_LAUNCH("vs_bn_act_bwd (resident slabs, LDS)");
             if (dbeta_sum && !gs.out_a) {
@@ -1702,14 +1696,14 @@ extern "C" int vs_bn_act_bwd_small_ex(const void* dy_a, int dy_a_dtype, const fl
         ((uintptr_t)dy_a | (uintptr_t)dy_b | (uintptr_t)slabs | (uintptr_t)z | (uintptr_t)dx) % 16 != 0)
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_bn_act_bwd_small_ex: tensor not served (vs_bn_act_bwd)");
     const int64_t nvec = (int64_t)B * HW / 8;
-#define VS_BN_SMALL(NV)                                                                                                                  \
+#define VS_BN_SMALL_CASE(NV)                                                                                                                  \
     hipLaunchKernelGGL(bn_bwd_small_ex_kernel<NV>, dim3(C), dim3(256), 0, (hipStream_t)stream, dy_a, dy_a_dtype, dy_b, slabs, nslabs, z, z_dtype, mean, \
                        invstd, gamma, beta, act, dbeta, dgamma, accumulate, dx, dx_dtype, B, C, (int)HW)
-    if (nvec <= 256) VS_BN_SMALL(1);
-    else if (nvec <= 512) VS_BN_SMALL(2);
-    else if (nvec <= 1024) VS_BN_SMALL(4);
-    else VS_BN_SMALL(8);
-#undef VS_BN_SMALL
+    if (nvec <= 256) VS_BN_SMALL_CASE(1);
+    else if (nvec <= 512) VS_BN_SMALL_CASE(2);
+    else if (nvec <= 1024) VS_BN_SMALL_CASE(4);
+    else VS_BN_SMALL_CASE(8);
+#undef VS_BN_SMALL_CASE
     VS_CHECK_LAUNCH("vs_bn_act_bwd_small_ex");
     return VS_OK;
 }

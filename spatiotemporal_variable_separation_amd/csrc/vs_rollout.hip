@@ -48,7 +48,6 @@ struct RollParams {
                                  // reads and clears it -- ops.rollout_exchange_error / train.check_rollout_exchange)
     size_t xtotal;               // workspace bytes (all but the last 16 are zero-filled before every launch)
     unsigned spin_limit;         // rounds a wait may take before it gives up (VS_ROLLOUT_SPIN_LIMIT, default 2^22)
-    int nap;                     // weight-stationary form: s_sleep units (64 clocks) between seeing the producer's input and polling its partials
     unsigned* ebase;             // weight-stationary form: per-slab epoch base words (even; advanced by the slab's last workgroup of every launch)
     int ring_skew;               // weight-stationary form, TEST AID (VS_ROLLOUT_XCD_LOCAL=2): deal the slabs out so that the ring of a slab is
                                  // spread over the XCDs -- the placement the XCD-local exchange must never meet
@@ -853,7 +852,7 @@ __global__ __launch_bounds__(WT) void rollout_ws_kernel(RollParams p, int mask_p
                 if (++spins > p.spin_limit) break;
                 __builtin_amdgcn_s_sleep(1);
             }
-            for (int z = 0; z < p.nap; ++z) __builtin_amdgcn_s_sleep(1);
+            for (int z = 0; z < WS_NAP; ++z) __builtin_amdgcn_s_sleep(1);
             u32x4 v[P + 1];
             const u64* addr[P + 1];
 #pragma unroll
@@ -1039,9 +1038,7 @@ inline bool usable(int compute, int B, int C, int H, int nb) {
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
         cus = n;
     }
-    if ((int64_t)nslabs * nb * P > (int64_t)cus - cus / 8) return false;      // MI355X: 256 CUs -> at most 224 workgroups
-    const char* e = getenv("VS_ROLLOUT_WS");
-    return !(e && e[0] == '0');
+    return (int64_t)nslabs * nb * P <= (int64_t)cus - cus / 8;                // MI355X: 256 CUs -> at most 224 workgroups
 }
 
 int g_xcd_local_allowed = 1;          // vs_mlp_rollout_xcd_local_set: 0 after a failed placement probe (process-wide)
@@ -1078,9 +1075,7 @@ int pick_parts(int compute, int B, int C, int H) {
 
 int launch_ws(int compute, bool fwd, const RollParams& p, int mask_pitch, size_t workspace_bytes, hipStream_t stream) {
     // No fill: the workspace is zero when the caller creates it (the contract of vs_mlp_rollout_workspace_bytes) and every launch tags its
-    // granules above the previous launch's (RollParams::ebase).  VS_ROLLOUT_ZERO=1: clear it anyway (all-zero is always a valid state).
-    static const int zero_mode = getenv("VS_ROLLOUT_ZERO") ? atoi(getenv("VS_ROLLOUT_ZERO")) : 0;
-    if (zero_mode && vs_zero_async(p.xbuf, p.xtotal - 16, stream) != hipSuccess) return vs_fail(VS_ERR_LAUNCH, "vs_mlp_rollout: zero fill failed");
+    // granules above the previous launch's (RollParams::ebase).
     (void)workspace_bytes;
     const int nslabs = (p.B + 15) / 16, P = p.H / 64;
     dim3 grid((unsigned)(nslabs * p.nb * P)), block(wsr::WT);
@@ -1187,7 +1182,6 @@ int setup_exchange(RollParams& p, int compute, void* workspace, size_t workspace
 // weight-stationary form: same decision in both directions (the sign-bit layout differs from the slab form)
 bool setup_ws(RollParams& p, int compute, void* workspace, size_t workspace_bytes, int* mask_pitch) {
     p.spin_limit = spin_limit_from_env();
-    { const char* e = getenv("VS_ROLLOUT_NAP"); p.nap = e ? atoi(e) : WS_NAP; if (p.nap < 0 || p.nap > 64) p.nap = WS_NAP; }
     if (!wsr::usable(compute, p.B, p.C, p.H, p.nb) || p.n < 2) return false;
     if (!workspace || workspace_bytes < wsr::exchange_bytes(p.B, p.H) + wsr::base_words_bytes(p.B) + 16) return false;
     p.xbuf = (u64*)workspace;

@@ -78,7 +78,7 @@ def mark_repeated(weights):
 def _defer_wgrad_ok(w, dz, transposed, stride):
     # (a weight that is used once or twice per step -- encoder / decoder layers -- gains nothing from the batching and would pay a
     # zero-filled buffer and, for calls of different batch sizes, a concatenation)
-    return (_STATE.get('fold_grads') and os.environ.get('VARSEP_DEFER_WGRADS', '1') == '1' and not transposed and stride == 1
+    return (_STATE.get('fold_grads') and not transposed and stride == 1
             and getattr(w, '_vs_repeated', False) and dz.shape[0] * dz.shape[2] * dz.shape[3] <= 16384 and not torch.is_grad_enabled())
 
 
@@ -239,10 +239,10 @@ def compute_dtype():
 #     E_s encoder, its backward overlaps the decoder/encoder weight gradients.
 # Only valid when every parameter receives ONE gradient per step (the batched MLP-family step) and without hook-driven
 # gradient all-reduce; `train._compute_losses_mlp_batched` / `GraphedStep` switch it on, everything else leaves it off.
-_SIDE = {'on': False, 'lanes': [], 'next_lane': 0, 'rollout': None, 'es': None, 'hold': False, 'held': [], 'hold_main': None, 'late': []}
+_SIDE = {'on': False, 'lanes': [], 'next_lane': 0, 'rollout': None, 'hold': False, 'held': [], 'hold_main': None, 'late': []}
 # Deferred gradient work is spread over a few streams ("lanes", one per Linear chain / integrator backward in turn): most of it
 # is GEMMs of 10-50 us that fill a fraction of the chip each, and one stream would run them one after the other.
-N_LANES = max(1, int(os.environ.get('VARSEP_WGRAD_LANES', '3')))
+N_LANES = 3
 
 
 _OWN_STREAMS = []
@@ -280,19 +280,11 @@ def enable_side_streams(flag):
         _SIDE['hold'], _SIDE['held'], _SIDE['late'] = False, [], []
 
 
-def tail_fused_updates():
-    """Default (VARSEP_ADAM_UNDER_FUSED=0 disables; WaveEq step, same box: 1.406-1.415 -> 1.378 ms): a chain's fused first-layer update (the 640 MB weight-gradient + Adam launches of the WaveEq encoders) is
-    issued LAST on its lane, behind the chain's bias sums and a marker event; the optimizer launch for the remaining parameters then waits
-    for the markers only and runs beside the fused updates (disjoint parameters; the step counter is advanced after the full join)."""
-    return os.environ.get('VARSEP_ADAM_UNDER_FUSED', '1') == '1'
-
-
-def tail_split():
-    """VARSEP_TAIL_SPLIT=1 (round 5): see MLPChain.backward -- the last chain's fused first-layer update on lane 0, beside its own small gradients."""
-    return os.environ.get('VARSEP_TAIL_SPLIT', '0') == '1'
-
-
 def _lane_marker(lane):
+    """A chain's fused first-layer update (the 640 MB weight-gradient + Adam launches of the WaveEq encoders) is issued LAST on its lane, behind
+    the chain's bias sums and this marker event; the optimizer launch for the remaining parameters then waits for the markers only and runs
+    beside the fused updates (disjoint parameters; the step counter is advanced after the full join).  WaveEq step, same box: 1.406-1.415
+    -> 1.378 ms."""
     def fn():
         ev = torch.cuda.Event()
         ev.record()
@@ -304,7 +296,7 @@ def _lane_marker(lane):
 def _queued_on_lane(fn, lane):
     """`fn` has just been issued on gradient lane `lane`.  A marker recorded earlier on that lane stands for "everything but the trailing
     fused update of this lane is done" only while nothing else follows it: any other work queued behind it (a later chain when the lanes
-    wrap around, VARSEP_WGRAD_LANES < number of chains) withdraws the marker, and join_side_streams(partial=True) then waits for the
+    wrap around, N_LANES < number of chains) withdraws the marker, and join_side_streams(partial=True) then waits for the
     whole lane."""
     if not (getattr(fn, '_vs_marker', False) or getattr(fn, '_vs_tail', False)):
         (_SIDE.get('markers') or {}).pop(lane, None)
@@ -312,27 +304,6 @@ def _queued_on_lane(fn, lane):
 
 def side_streams_enabled():
     return _SIDE['on']
-
-
-class chain_forward_stream:
-    """While active, MLPChain.forward issues its launches on `stream` (and records what it hands to the caller and keeps for backward on the
-    caller's stream); the autograd node is still created under the caller's stream, so BACKWARD runs where it would have run anyway."""
-
-    def __init__(self, stream):
-        self.stream = stream
-
-    def __enter__(self):
-        self.prev, _SIDE['chain_stream'] = _SIDE.get('chain_stream'), self.stream
-
-    def __exit__(self, *exc):
-        _SIDE['chain_stream'] = self.prev
-
-
-def on_chain_forward_stream():
-    """Context: the stream of the active chain_forward_stream, or nothing."""
-    from contextlib import nullcontext
-    s = _SIDE.get('chain_stream')
-    return torch.cuda.stream(s) if s is not None else nullcontext()
 
 
 def note_main_stream(stream):
@@ -384,23 +355,13 @@ def _record_on(ws, inputs, outs):
             t.record_stream(ws)
 
 
-def _late_mode():
-    """VARSEP_FUSED_AFTER_ROLLOUT: '2' (default) = a held fused first-layer update (E_s's 20480 x 1200 weight-gradient + Adam launch: 640 MB
-    of HBM traffic) waits ON ITS OWN LANE for the integrator's backward kernel to finish and then runs beside E_t's input-gradient chain, which
-    leaves HBM idle (WaveEq step, same box: 1.4505 -> 1.4045 ms); '3' = every held fused update; '1' = on a stream of its own (2.95 ms: a
-    fourth gradient stream collides with the integrator's queue); '0' = released with the other held work under the integrator's kernel."""
-    return os.environ.get('VARSEP_FUSED_AFTER_ROLLOUT', '2')
-
-
-def _late_fused(layer):
-    m = _late_mode()
-    return (m in ('1', '2') and layer == 0) or m == '3'
-
-
 def run_deferred(fn, *inputs, outs=None, lane=0, late=False):
     """Run `fn()` (weight-gradient launches) on a gradient stream behind everything queued so far on the current stream.
     `outs`: the tensors `fn` writes, allocated by the caller -- required for the work to be holdable (hold_deferred); they are
-    returned in place of fn's result."""
+    returned in place of fn's result.  `late`: when held, `fn` additionally waits ON ITS OWN LANE for the event recorded after the
+    integrator's backward kernel (release_deferred(late_after=...)): a held fused first-layer update (E_s's 20480 x 1200 weight-gradient +
+    Adam launch: 640 MB of HBM traffic) then runs beside E_t's input-gradient chain, which leaves HBM idle, instead of beside that
+    latency-bound kernel (WaveEq step, same box: 1.4505 -> 1.4045 ms)."""
     if not _SIDE['on']:
         out = fn()
         return out if outs is None else outs
@@ -435,12 +396,11 @@ def run_late(fn, *inputs, outs, lane=0):
     return outs
 
 
-def defer_call(fn, late=False):
-    """Queue `fn` (launches that consume held gradients, e.g. an optimizer bucket) behind ALL the held work; False if nothing is held.
-    `late`: additionally behind the event recorded after the integrator's backward kernel (release_deferred(late_after=...))."""
+def defer_call(fn):
+    """Queue `fn` (launches that consume held gradients, e.g. an optimizer bucket) behind ALL the held work; False if nothing is held."""
     if not deferred_held():
         return False
-    _SIDE['held'].append((fn, (), (), 'all-late' if late else None, None))
+    _SIDE['held'].append((fn, (), (), None, None))
     return True
 
 
@@ -452,7 +412,8 @@ def _behind_producer(ws, producer, main, behind):
 
 def release_deferred(after=None, late_after=None):
     """Launch everything collected since hold_deferred() on the gradient streams, in order, behind the work queued so far on the
-    stream the hold was declared on (the producer of every input of the held closures) and behind the event `after`."""
+    stream the hold was declared on (the producer of every input of the held closures) and behind the event `after`; work held with
+    `late` also behind the event `late_after` (recorded after the integrator's kernel)."""
     held, _SIDE['held'] = _SIDE['held'], []
     was, _SIDE['hold'] = _SIDE['hold'], False
     if not held:
@@ -461,33 +422,17 @@ def release_deferred(after=None, late_after=None):
     started = set()
     behind = set()                             # (gradient stream, producer stream) pairs already ordered
     for fn, inputs, outs, lane, producer in held:
-        if isinstance(lane, tuple):            # ('late', lane): behind the event `late_after` (recorded after the integrator's kernel)
-            own = _late_mode() == '1'          # '1': a stream of its own; '2': the closure's own lane
-            key = 'late' if own else lane[1]
-            ws = _lane_stream(N_LANES) if own else _lane_stream(lane[1])
-            if key not in started:
-                ws.wait_stream(main)
-                if after is not None and not own:
-                    ws.wait_event(after)
-                started.add(key)
-            _behind_producer(ws, producer, main, behind)
-            if late_after is not None:
-                ws.wait_event(late_after)
-            with torch.cuda.stream(ws):
-                fn()
-            _queued_on_lane(fn, N_LANES if own else lane[1])
-            _record_on(ws, inputs, outs)
-            continue
-        if lane is None or lane == 'all-late':  # consumes everything released so far: lane 0 behind the other lanes
+        late = isinstance(lane, tuple)         # ('late', lane)
+        if late:
+            lane = lane[1]
+        if lane is None:                       # consumes everything released so far: lane 0 behind the other lanes
             ws = _lane_stream(0)
             if 0 not in started:
                 ws.wait_stream(main)
                 started.add(0)
             for l in started:
-                if l != 0 and l != 'late':
+                if l != 0:
                     ws.wait_stream(_lane_stream(l))
-            if lane == 'all-late' and late_after is not None:
-                ws.wait_event(late_after)
         else:
             ws = _lane_stream(lane)
             if lane not in started:
@@ -496,9 +441,11 @@ def release_deferred(after=None, late_after=None):
                     ws.wait_event(after)
                 started.add(lane)
             _behind_producer(ws, producer, main, behind)
+            if late and late_after is not None:
+                ws.wait_event(late_after)
         with torch.cuda.stream(ws):
             fn()
-        _queued_on_lane(fn, 0 if (lane is None or lane == 'all-late') else lane)
+        _queued_on_lane(fn, 0 if lane is None else lane)
         _record_on(ws, inputs, outs)
 
 
@@ -599,7 +546,7 @@ def fused_optimizer(prm):
 
 def side_streams_in_use():
     """Streams that deferred gradient work of the current step may still be running on."""
-    return (list(_SIDE['lanes']) + [_SIDE[k] for k in ('rollout', 'es') if _SIDE[k] is not None]) if _SIDE['on'] else []
+    return (list(_SIDE['lanes']) + ([_SIDE['rollout']] if _SIDE['rollout'] is not None else [])) if _SIDE['on'] else []
 
 
 def finish_join(pending):
@@ -611,15 +558,13 @@ def finish_join(pending):
 
 def join_side_streams(partial=False):
     """Make the current stream wait for all deferred gradient work (call before the optimizer step).  `partial`: on lanes that recorded a
-    marker in front of a trailing fused update (tail_fused_updates) wait for the marker only and return those lanes: the caller runs the
+    marker in front of a trailing fused update (_lane_marker) wait for the marker only and return those lanes: the caller runs the
     optimizer launch for the other parameters and then calls finish_join()."""
     if not _SIDE['on']:
         return []       # nothing was deferred; waiting on a stream outside the running capture would break the capture
     release_deferred()  # (a step without the integrator's backward never reached the release point)
     late, _SIDE['late'] = _SIDE['late'], []
     for fn, inputs, outs, lane, producer in late:
-        if tail_split() and N_LANES > 1:
-            lane = N_LANES - 1                # (lane 0 carries the last chain's 640 MB update: the late gradients would queue behind it)
         ws = _lane_stream(lane)
         ws.wait_stream(producer)
         with torch.cuda.stream(ws):
@@ -637,9 +582,8 @@ def join_side_streams(partial=False):
         else:
             cur.wait_stream(ws)
     _SIDE['markers'] = {}
-    for k in ('rollout', 'es'):
-        if _SIDE[k] is not None:
-            cur.wait_stream(_SIDE[k])
+    if _SIDE['rollout'] is not None:
+        cur.wait_stream(_SIDE['rollout'])
     return pending
 
 
@@ -783,19 +727,6 @@ class MLPChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x_lowp, acts, handoff, *params):
-        fs = _SIDE.get('chain_stream')
-        if fs is not None and fs != torch.cuda.current_stream():
-            caller = torch.cuda.current_stream()
-            _SIDE['chain_stream'] = None
-            try:
-                with torch.cuda.stream(fs):
-                    out = MLPChain.forward(ctx, x, x_lowp, acts, handoff, *params)
-            finally:
-                _SIDE['chain_stream'] = fs
-            for t in (out,) + tuple(ctx.to_save):
-                if isinstance(t, torch.Tensor) and t.is_cuda:
-                    t.record_stream(caller)
-            return out
         require_cuda(x)
         cdt = compute_dtype()
         n_layers = len(params) // 2
@@ -854,19 +785,6 @@ class MLPChain(torch.autograd.Function):
         grads = [None] * (2 * L)
         dx = None
         lane = next_lane()                   # this chain's weight / bias gradients: one gradient stream, in order
-        tail_lane = lane
-        if (lane > 0 and deferred_held() and _late_mode() == '2' and tail_fused_updates() and L > 1 and params[0].requires_grad
-                and grad_output(params[0]) is None and fused_optimizer(params[0]) is not None and cdt != torch.float32
-                and os.environ.get('VARSEP_LATE_TAIL_ALONE', '0') == '1'):
-            # A chain whose fused first-layer update is HELD for the end of the integrator's backward kernel (E_s in the batched MLP step: 640 MB
-            # of HBM traffic that must not run beside that latency-bound kernel) keeps its lane for that update alone; its small weight gradients
-            # and bias sums ride on the previous chain's lane.  In the recording the update then depends on the chain's input gradient and on
-            # the integrator's kernel only -- not on its own small gradients, which sat behind the decoder's weight gradients on a shared
-            # hardware queue and started it ~180 us after the integrator's kernel had finished (timeline of round 6) -- so it runs in the
-            # HBM-idle window beside E_t's input-gradient chain instead of beside E_t's own 640 MB update.  MEASURED AND NOT THE DEFAULT
-            # (VARSEP_LATE_TAIL_ALONE=1 turns it on): 1.2521 / 1.2337 vs 1.2047 / 1.1930 ms -- E_t's input-gradient chain, the critical path
-            # after the integrator, loses more under the update's HBM traffic than the earlier start of the tail gives back.
-            lane = lane - 1
         bias_jobs = []                       # (slot, dz): all bias gradients of the chain in one launch at the end
         tail_job = None
         for l in range(L - 1, -1, -1):
@@ -891,10 +809,10 @@ class MLPChain(torch.autograd.Function):
                         dx = ops.gemm(dz, R, shadow(W, cdt), S, M, K, N, out_dtype=torch.float32)
                     # the weight-gradient GEMM's epilogue IS this weight's optimizer step; nothing is stored, autograd gets nothing
                     job = (lambda dz=dz, h_in=h_in, N=N, K=K, W=W, fused=fused: fused.fused_update(W, dz, S, h_in, S, N, K, M), (dz, h_in))
-                    if l == 0 and _SIDE['on'] and tail_fused_updates():
-                        tail_job = job                   # issued behind the chain's bias sums and a marker (see tail_fused_updates)
+                    if l == 0 and _SIDE['on']:
+                        tail_job = job                   # issued behind the chain's bias sums and a marker (see _lane_marker)
                     else:
-                        run_deferred(job[0], *job[1], outs=(), lane=lane, late=_late_fused(l))
+                        run_deferred(job[0], *job[1], outs=(), lane=lane)
                 elif dst is not None:           # straight into the all-reduce bucket; autograd gets nothing for this parameter
                     # (holdable like the single-GPU path: the destination exists already)
                     run_deferred(lambda dz=dz, h_in=h_in, N=N, K=K, dst=dst: ops.gemm(dz, S, h_in, S, N, K, M, out=dst), dz, h_in,
@@ -926,14 +844,8 @@ class MLPChain(torch.autograd.Function):
             run_deferred(lambda views=views: ops.colsum_multi(dzs, outs=views, zero_flat=flat), *dzs, outs=flat, lane=lane)
         if tail_job is not None:
             tail_job[0]._vs_tail = True
-            tl = tail_lane
-            if tail_split() and tail_lane == N_LANES - 1 and N_LANES > 1 and not deferred_held():
-                # the LAST chain of backward (E_t in the batched MLP step: lane N_LANES - 1): its small weight gradients and bias sums (~90 us of
-                # 10 us launches on `lane`) run BESIDE its 640 MB first-layer update instead of in front of it -- the update goes to lane 0, whose
-                # work (the decoder's weight gradients) is long done; the integrator's late weight gradients move to `lane` (join_side_streams)
-                tl = 0
-            run_deferred(_lane_marker(tl), outs=(), lane=tl)
-            run_deferred(tail_job[0], *tail_job[1], outs=(), lane=tl, late=_late_fused(0))
+            run_deferred(_lane_marker(lane), outs=(), lane=lane)
+            run_deferred(tail_job[0], *tail_job[1], outs=(), lane=lane, late=True)
         return (dx, None, None, None) + tuple(grads)
 
 
@@ -1019,14 +931,11 @@ class MLPRollout(torch.autograd.Function):
         ctx.cdt, ctx.nb, ctx.n_steps, ctx.params = cdt, nb, n_steps, params
         ctx.save_for_backward(xin, h1, h2, m1, m2)
         ctx.mark_non_differentiable(residuals)
-        # VARSEP_ROLLOUT_GRES_FILL=0: no zero tensor for the gradient of the non-differentiable residuals (autograd launches a 1.2 MB fill for it
-        # on the integrator's stream, right in front of the backward kernel).  MEASURED AND NOT THE DEFAULT: without that node the replayed WaveEq
-        # step is 1.282 / 1.283 ms against 1.145 / 1.151 (same box, alternating).  It is not a race between the held weight-gradient GEMMs and
-        # the backward kernel for the CUs: holding the GEMMs back by one to three small launches behind `ready` leaves it at 1.29-1.30 ms.  The
-        # node changes where the runtime places the branches of the recording (the same kind of cliff as a sixth stream or six hardware
-        # queues, profiles/r06_queues.md), so it stays.
-        if os.environ.get('VARSEP_ROLLOUT_GRES_FILL', '1') == '0':
-            ctx.set_materialize_grads(False)
+        # The gradient of the non-differentiable residuals stays materialised (autograd launches a 1.2 MB fill for it on the integrator's stream,
+        # right in front of the backward kernel): without that node the replayed WaveEq step is 1.282 / 1.283 ms against 1.145 / 1.151 (same box,
+        # alternating).  It is not a race between the held weight-gradient GEMMs and the backward kernel for the CUs: holding the GEMMs back by
+        # one to three small launches behind `ready` leaves it at 1.29-1.30 ms.  The node changes where the runtime places the branches of the
+        # recording (the same kind of cliff as a sixth stream or six hardware queues, profiles/r06_queues.md).
         ctx.codes_shape = tuple(t_codes.shape)
         return t_codes, residuals
 
@@ -1050,7 +959,7 @@ class MLPRollout(torch.autograd.Function):
             ready.record()
         dx0, dr, dh2, dh1 = ops.mlp_rollout_bwd(g_codes, wts, h1, h2, m1, m2, n_steps)
         done = None
-        if ready is not None and (_late_mode() in ('1', '2', '3') or os.environ.get('VARSEP_ADAM_EARLY_BUCKET') == '2'):
+        if ready is not None:
             done = torch.cuda.Event()
             done.record()
         release_deferred(after=ready, late_after=done)
@@ -1081,7 +990,7 @@ class MLPRollout(torch.autograd.Function):
                 # the start of the step: the three batched launches write [blocks, ., .] IN the bucket, the bias sums add into their views --
                 # autograd is handed nothing (no 18 `+=` launches of 4 us each at the end of backward: 86 us of the WaveEq step under a reducer)
                 w1, w2, w3, bias_out = stacked
-                if _SIDE['on'] and os.environ.get('VARSEP_ROLLOUT_WGRAD_LATE', '1') == '1':
+                if _SIDE['on']:
                     run_late(lambda: weight_grads(w1, w2, w3, bias_out, None), dr, dh2, dh1, xin, h1, h2, outs=(w1, w2, w3), lane=next_lane())
                 else:
                     weight_grads(w1, w2, w3, bias_out, None)
@@ -1089,7 +998,7 @@ class MLPRollout(torch.autograd.Function):
             # with gradient destinations registered these gradients still go through autograd's `+=` into the bucket views, which
             # runs on THIS node's stream: compute them here, not on a gradient stream
             grads = weight_grads()
-        elif _SIDE['on'] and os.environ.get('VARSEP_ROLLOUT_WGRAD_LATE', '1') == '1':
+        elif _SIDE['on']:
             # recorded at the END of backward (run_late), into buffers allocated now; autograd is handed views of its own (a tensor
             # somebody else references would be cloned, here before it has been written)
             dev = dx0.device
@@ -1170,14 +1079,6 @@ def packed_k4s2_weight(p, dtype):
     return ent[1]
 
 
-def _conv_lane():
-    """Gradient stream of the next convolution weight gradient (VARSEP_CONV_WGRAD_LANES of them in turn, default 1)."""
-    n = max(1, int(os.environ.get('VARSEP_CONV_WGRAD_LANES', '1')))
-    i = _SIDE.get('conv_lane', 0)
-    _SIDE['conv_lane'] = (i + 1) % n
-    return i
-
-
 def _conv_weight_grad(w, dz, xc, stride, pad, transposed, k4s2=None):
     """Weight gradient of one convolution call for autograd, or None when it was added to / will be batched into the tensor autograd
     already holds.  `k4s2` = (small map, parity planes of the large map): the k4 s2 p1 family on the row-band kernels (ops.conv_k4s2_wgrad)."""
@@ -1194,7 +1095,7 @@ def _conv_weight_grad(w, dz, xc, stride, pad, transposed, k4s2=None):
     if k4s2 is not None:
         if first_w is not None and first_w.dtype == torch.float32 and first_w.shape == w.shape and first_w.is_contiguous():
             if on_lane:
-                run_deferred(lambda a=k4s2[0], b=k4s2[1]: ops.conv_k4s2_wgrad(a, b, w.shape, into=dst), k4s2[0], k4s2[1], outs=dst, lane=_conv_lane())
+                run_deferred(lambda a=k4s2[0], b=k4s2[1]: ops.conv_k4s2_wgrad(a, b, w.shape, into=dst), k4s2[0], k4s2[1], outs=dst, lane=0)
                 _STATE['wgrad_on_lane'] = True
             else:
                 ops.conv_k4s2_wgrad(k4s2[0], k4s2[1], w.shape, into=first_w)
@@ -1219,7 +1120,7 @@ def _conv_weight_grad(w, dz, xc, stride, pad, transposed, k4s2=None):
         slot['pairs'].append((dz, xc))
     elif first_w is not None and first_w.dtype == torch.float32 and first_w.shape == w.shape and first_w.is_contiguous():
         if on_lane:
-            run_deferred(lambda: ops.conv_wgrad(dz, xc, w.shape, stride, pad, transposed, into=dst), dz, xc, outs=dst, lane=_conv_lane())
+            run_deferred(lambda: ops.conv_wgrad(dz, xc, w.shape, stride, pad, transposed, into=dst), dz, xc, outs=dst, lane=0)
             _STATE['wgrad_on_lane'] = True
         else:
             ops.conv_wgrad(dz, xc, w.shape, stride, pad, transposed, into=first_w)
@@ -1259,7 +1160,7 @@ def _fold_param_grads(pairs):
             what.append(g)
             out[i] = None
     if into:
-        if _CONV_GRAD_OUT and torch.cuda.is_current_stream_capturing() and os.environ.get('VARSEP_BATCH_SMALL_ADDS', '1') == '1':
+        if _CONV_GRAD_OUT and torch.cuda.is_current_stream_capturing():
             # recorded step under a reducer: EVERY contribution (the first included) is an add into a bucket view -- 44 multi-tensor launches
             # of ~5 us per TaxiBJ step against 11 without a reducer.  Nothing reads the buckets before the backward call returns (no hooks
             # fire in a recording; train.GraphedStep reduces after the replay), so the adds of the whole pass are issued as ONE multi-tensor
@@ -1339,11 +1240,26 @@ def prepack_conv3_weights(net, dtype=None):
     return len(stale)
 
 
+# Form of the ConvResBlock layers: VARSEP_FUSED_RESBLOCK = '0' (the plain ConvBlock path), '1' (default: convolution and BatchNorm as two launches
+# per layer) or '2' (one launch per layer, partial sums exchanged inside it).  train.recover_exchange withdraws '2' for the rest of the process
+# after its in-launch exchange timed out (module state, like ops.rollout_xcd_local for the integrator: the environment is an input only).
+_RESBLOCK = {'two_launch_only': False}
+
+
+def resblock_two_launch_only(flag=True):
+    _RESBLOCK['two_launch_only'] = bool(flag)
+
+
+def _resblock_mode():
+    mode = os.environ.get('VARSEP_FUSED_RESBLOCK', '1')
+    return '1' if (mode == '2' and _RESBLOCK['two_launch_only']) else mode
+
+
 def conv_res_block_fusable(x, convs, bns, cdt=None):
     """Whether `ConvResBlockFn` serves a ConvResBlock (resnet.py:53-70): three Conv2d k3 s1 p1 + training-mode BatchNorm on a few 16x16
     maps in a 16-bit compute type, identity skip."""
     cdt = cdt or compute_dtype()
-    if os.environ.get('VARSEP_FUSED_RESBLOCK', '1') not in ('1', '2') or cdt == torch.float32 or not x.is_cuda or x.dim() != 4:
+    if _resblock_mode() not in ('1', '2') or cdt == torch.float32 or not x.is_cuda or x.dim() != 4:
         return False
     if x.dtype != torch.float32 or not x.is_contiguous() or len(convs) != 3 or convs[2].out_channels != x.shape[1]:
         return False
@@ -1385,7 +1301,7 @@ class ConvResBlockFn(torch.autograd.Function):
         cdt = compute_dtype()
         h = x16 if (x16 is not None and x16.dtype == cdt and x16.shape == x.shape) else to_compute(x, cdt)
         saved = []
-        one_launch = os.environ.get('VARSEP_FUSED_RESBLOCK', '1') == '2'       # '1' (default): convolution and BatchNorm as two launches per layer
+        one_launch = _resblock_mode() == '2'
         for li in range(3):
             w, b, gm, bt = prm[4 * li:4 * li + 4]
             rmean, rvar, momentum, eps, act = cfg[li]
@@ -1438,7 +1354,7 @@ class ConvResBlockFn(torch.autograd.Function):
         grads = [None] * 12
         dz_up = None                                 # dz of the layer above (li + 1)
         fold = _STATE.get('fold_grads')
-        one_launch = os.environ.get('VARSEP_FUSED_RESBLOCK', '1') == '2'
+        one_launch = _resblock_mode() == '2'
         for li in (2, 1, 0):
             w, b, gm, bt = prm[4 * li:4 * li + 4]
             h, z, mean, invstd = saved[4 * li:4 * li + 4]
@@ -1526,12 +1442,12 @@ def _drop_folded(key):
 
 def _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt):
     """BatchNorm (+ activation) of a convolution output z on the two-launch path: (y, mean, invstd).  Training with tracked running estimates:
-    the fold of the running estimates rides in the apply launch (VS_BN_RUNNING_FUSED=0: the separate bn_running launch)."""
+    the fold of the running estimates rides in the apply launch."""
     if training:
         if ops.bn_slab_supported(z, groups):
             # (a call's channel slab fits one workgroup's registers: statistics and apply from ONE read of z)
             return ops.bn_train_fwd_slab(z, gamma.detach(), beta.detach(), act, out_dt, rmean, rvar, momentum, eps, groups=groups)
-        if rmean is not None and os.environ.get('VS_BN_RUNNING_FUSED', '1') == '1':
+        if rmean is not None:
             mean, invstd, ub = ops.bn_stats_ub(z, eps, groups=groups)
             y = ops.bn_act_fwd(z, mean, invstd, gamma.detach(), beta.detach(), act, out_dt, groups=groups, running=(ub, rmean, rvar, momentum))
             return y, mean, invstd
@@ -1873,9 +1789,9 @@ class CatBcast(torch.autograd.Function):
 
 def cat_bcast(a, x, n, out_dtype=None):
     """cat([a repeated n times along the batch axis, x], dim=1) in `out_dtype` (default: x's); falls back to torch ops where the kernel does not
-    take the tensors (CPU, odd plane sizes) or VARSEP_CAT_BCAST=0."""
+    take the tensors (CPU, odd plane sizes)."""
     out_dtype = out_dtype or x.dtype
-    if (n > 1 and os.environ.get('VARSEP_CAT_BCAST', '1') == '1' and a.is_cuda and a.dim() == 4 and x.dim() == 4
+    if (n > 1 and a.is_cuda and a.dim() == 4 and x.dim() == 4
             and ops.cat_bcast_supported(a.detach().contiguous(), x.detach().contiguous(), n)):
         return CatBcast.apply(a, x, n, out_dtype)
     return torch.cat([a.repeat(n, 1, 1, 1).to(out_dtype), x.to(out_dtype)], dim=1)

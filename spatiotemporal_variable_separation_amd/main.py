@@ -152,8 +152,6 @@ def main(argv=None):
         print('step launch: %s' % ('recorded hipGraph, replayed per batch (--no_hip_graph: eager launches)' if hip_graph else 'eager launches from Python'))
     from .train import make_loss_scaler
     scaler = make_loss_scaler(device) if precision == 'fp16' else None
-    from .train import enable_update_in_backward
-    enable_update_in_backward(optimizer, sep_net, grad_sync, scaler=scaler)
     train(args.xp_dir, train_loader, device, sep_net, optimizer, scheduler, args.apex_amp, False, args.epochs, args.lamb_ae,
           args.lamb_s, args.lamb_t, args.lamb_pred, args.offset, args.nt_cond, args.nt_pred, args.no_s, args.skipco,
           args.chkpt_interval, args.architecture == 'encoderSST', grad_sync=grad_sync, log_interval=args.log_interval,

@@ -1,5 +1,4 @@
 """Model orchestrator (reference: networks/model.py:20-89)."""
-import os
 
 import torch
 import torch.nn as nn
@@ -63,7 +62,7 @@ class SeparableNetwork(nn.Module):
     def _roll(self, t_code, n_forecast):
         """[t_0, ..., t_{n-1}] with t_{k+1} = t_resnet(t_k), and the per-step residual lists."""
         codes, residuals = [t_code], []
-        want_alias = getattr(self.t_resnet, 'supports_alias', False) and os.environ.get('VARSEP_RESBLOCK_ALIAS', '1') == '1'
+        want_alias = getattr(self.t_resnet, 'supports_alias', False)
         while len(codes) < n_forecast:
             if want_alias:
                 # a fused ConvResBlock hands its output out twice: the recurrence goes on with one, the list keeps the other, and the two

@@ -398,7 +398,7 @@ def _probe_rollout_exchange(code, B, C, H, nb, device):
     guard = _GUARD.get(device.index if device.index is not None else torch.cuda.current_device())
     before = int(guard[0].item()) if guard is not None else 0
     saved = os.environ.get('VS_ROLLOUT_SPIN_LIMIT')
-    os.environ['VS_ROLLOUT_SPIN_LIMIT'] = os.environ.get('VARSEP_ROLLOUT_PROBE_SPINS', str(1 << 16))
+    os.environ['VS_ROLLOUT_SPIN_LIMIT'] = str(1 << 16)
     try:
         wa, ba = _ptr_array(weights), _ptr_array(biases)
         check(lib.vs_mlp_rollout_fwd(code, B, C, H, nb, n, x0.data_ptr(), ctypes.cast(wa, ctypes.c_void_p), ctypes.cast(ba, ctypes.c_void_p),
@@ -558,17 +558,13 @@ def _conv_workspace(x_dtype_code, B, Cin, H, W, Cout, k, stride, pad, device):
 
 
 # ---- convolutions with 1..8 channels on the image side (csrc/vs_conv_thin.hip): dispatched from conv_fwd / conv_dgrad / conv_wgrad ----------
-def _thin_plan(op, code, B, Cin, H, W, Cout, OH, OW, k, stride, pad, transposed, wgrad_max_m=None):
+def _thin_plan(op, code, B, Cin, H, W, Cout, OH, OW, k, stride, pad, transposed, wgrad_max_m=8):
     """Whether this convolution call is one of the thin forms; returns (kind, C, Hb, Wb, M, sc, sm, flip) -- the many-channel map's channels and
     size, the thin channel count and how element (c, m, t) of the kernel's weight view is found in the weight tensor -- or None.
-    VS_CONV_THIN=0: never.  The weight gradient takes its thin kernel up to `wgrad_max_m` thin channels (VS_CONV_THIN_WGRAD_MAX_M, default 8 since
-    round 4: no convolution of the BASELINE steps builds a column matrix any more.  With 4 / 5 / 8 thin channels -- the first encoder layers --
-    the column-matrix GEMM was the faster form, 57-72 us against 78-129 us: the VALU form re-reads the map per pair of thin channels; 2
-    restores that choice)."""
-    import os
-    if wgrad_max_m is None:
-        wgrad_max_m = int(os.environ.get('VS_CONV_THIN_WGRAD_MAX_M', '8'))
-    if os.environ.get('VS_CONV_THIN') == '0' or code == F32 or pad != 1 or (k, stride) not in ((3, 1), (4, 2)):
+    The weight gradient takes its thin kernel up to `wgrad_max_m` thin channels (8 since round 4: no convolution of the BASELINE steps builds
+    a column matrix any more.  With 4 / 5 / 8 thin channels -- the first encoder layers -- the column-matrix GEMM was the faster form, 57-72 us
+    against 78-129 us: the VALU form re-reads the map per pair of thin channels)."""
+    if code == F32 or pad != 1 or (k, stride) not in ((3, 1), (4, 2)):
         return None
     k2 = k * k
     plan = None
@@ -641,15 +637,13 @@ def conv_thin_wgrad(big, thin, w_shape, k, stride, sc, sm, flip, into=None, out=
 # ---- ConvTranspose2d on a 1x1 map (the decoders' first_upconv, reference conv.py:258, 295: [B, C, 1, 1] -> [B, Cout, k, k]) IS a dense GEMM with
 # the weight [Cin][Cout k k] as it lies in memory: no column matrix, no scatter ------------------------------------------------------------------
 def _convt_1x1(x_shape, k, stride, pad, transposed):
-    import os
-    return (transposed and x_shape[2] == 1 and x_shape[3] == 1 and pad == 0 and stride == 1 and os.environ.get('VS_CONVT_1X1_GEMM', '1') == '1')
+    return transposed and x_shape[2] == 1 and x_shape[3] == 1 and pad == 0 and stride == 1
 
 
 def _conv_full(x_shape, k, stride, pad, transposed):
     """Conv2d whose window is the whole (unpadded) map -- the encoders' `last_op` (reference conv.py:123, 169: Conv2d(8 nf, nh, 4, 1, 0) on a
     4 x 4 map -> 1 x 1): a Linear layer on the map as it lies in memory, y[b][co] = sum_j x[b][j] w[co][j], j = (ci, ky, kx).  No gather."""
-    import os
-    return (not transposed and pad == 0 and x_shape[2] == k and x_shape[3] == k and os.environ.get('VS_CONV_FULL_GEMM', '1') == '1')
+    return not transposed and pad == 0 and x_shape[2] == k and x_shape[3] == k
 
 
 # ---- fp32 results from the 16-bit row-band kernels (VARSEP_FP32_SPLIT=1) ---------------------------------------------------------------------
@@ -1020,9 +1014,8 @@ def conv_wgrad(dy, x, w_shape, stride, pad, transposed, into=None, out=None):
 def conv_k4s2_supported(big, M):
     """Whether the gather-type operations of a k4 s2 p1 (transposed) convolution on the LARGE map `big` [B, C, H, W] -- Conv2d forward /
     weight gradient (big = the input, M = Cout), ConvTranspose2d input / weight gradient (big = the output gradient, M = Cin) -- run on
-    the parity planes of `big` with the row-band kernels (no column matrix).  VS_CONV_K4S2=0: never."""
-    import os
-    if os.environ.get('VS_CONV_K4S2') == '0' or big.dtype == torch.float32 or big.dim() != 4:
+    the parity planes of `big` with the row-band kernels (no column matrix)."""
+    if big.dtype == torch.float32 or big.dim() != 4:
         return False
     B, C, H, W = big.shape
     lib = _lib.load_library()
@@ -1035,8 +1028,7 @@ def conv_k4s2_supported(big, M):
 def conv_k4s2_gather_supported(big, M):
     """`conv_k4s2_supported` for the GATHER alone (Conv2d forward / ConvTranspose2d input gradient on the parity planes): 8 x 8 maps have 4 x 4
     planes, which the row-band forward kernel serves (sixteen maps per workgroup) but the row-band weight gradient does not."""
-    import os
-    if os.environ.get('VS_CONV_K4S2') == '0' or big.dtype == torch.float32 or big.dim() != 4:
+    if big.dtype == torch.float32 or big.dim() != 4:
         return False
     B, C, H, W = big.shape
     lib = _lib.load_library()
@@ -1115,8 +1107,7 @@ def conv_k4s2_wgrad(small, planes, w_shape, into=None, out=None):
 
 # ---- ConvTranspose2d k4 s2 p1 forward as tap GEMM + col2im epilogue (csrc/vs_conv_tap.hip) -------------------------------------
 def convt_tap_supported(x, Cout, groups):
-    import os
-    if os.environ.get('VS_CONV_TAP') == '0' or x.dtype == torch.float32:
+    if x.dtype == torch.float32:
         return False
     B, Cin, H, W = x.shape
     return bool(_lib.load_library().vs_convt_tap_supported(dtype_code(x), B, Cin, H, W, Cout, groups))
@@ -1153,22 +1144,19 @@ def conv_k3_tap_supported(x, Cout, groups, force=False):
     """Whether Conv2d k3 s1 p1 on `x` takes the tap kernel.  Measured (tools/conv_bench.py): with 9 taps x 28 channels per tile the
     epilogue (shift-sum of nine maps) outweighs the saved column matrix unless the contraction is long -- 512 -> 512 at 16x16
     (the SST integrator): 45 vs 65 us; 128 -> 128 (K = 4 tiles): 489 vs 371 us -- so it is taken for Cin >= 384, Cout >= 256
-    (VS_CONV_TAP=2 or force=True: whenever the geometry is supported; VS_CONV_TAP=0: never)."""
-    import os
-    mode = os.environ.get('VS_CONV_TAP')
-    if mode == '0' or x.dtype == torch.float32:
+    (force=True: whenever the geometry is supported)."""
+    if x.dtype == torch.float32:
         return False
     B, Cin, H, W = x.shape
-    if not (force or mode == '2') and (Cin < 384 or Cout < 256):
+    if not force and (Cin < 384 or Cout < 256):
         return False
     return bool(_lib.load_library().vs_conv_k3_tap_supported(dtype_code(x), B, Cin, H, W, Cout, groups))
 
 
 def conv3_img16_supported(x, Cout):
     """Whether Conv2d k3 s1 p1 on `x` takes the few-images kernel (`conv3_img16`): 16x16 maps, 16-bit, Cin a multiple of 64 and a batch
-    small enough that the per-image tiling pays (the SST integrator: 8 maps).  VS_CONV_IMG=0: never."""
-    import os
-    if os.environ.get('VS_CONV_IMG') == '0' or x.dtype == torch.float32 or x.dim() != 4:
+    small enough that the per-image tiling pays (the SST integrator: 8 maps)."""
+    if x.dtype == torch.float32 or x.dim() != 4:
         return False
     B, Cin, H, W = x.shape
     if B > 32:
@@ -1230,14 +1218,12 @@ def conv3_img16(x, w_packed, Cout, role='fwd'):
 
 def conv3_band_supported(x, Cout):
     """Whether Conv2d k3 s1 p1 on `x` takes the row-band kernel (`conv3_band`: many maps of width 4 / 8 / 16 / 32 / 64, any channel count --
-    a last 64-channel phase is filled with zeros --, no column matrix).  VS_CONV_BAND=0: never.  Below 16 channels on either side the
-    thin-channel kernels (one VALU pass, no 32 x 64-wide MFMA tiles of padding) keep the layer: VS_CONV_BAND_MIN_C."""
-    import os
-    if os.environ.get('VS_CONV_BAND') == '0' or x.dtype == torch.float32 or x.dim() != 4:
+    a last 64-channel phase is filled with zeros --, no column matrix).  Below 16 channels on either side the thin-channel kernels (one VALU
+    pass, no 32 x 64-wide MFMA tiles of padding) keep the layer."""
+    if x.dtype == torch.float32 or x.dim() != 4:
         return False
     B, Cin, H, W = x.shape
-    min_c = int(os.environ.get('VS_CONV_BAND_MIN_C', '16'))
-    if Cin < min_c or Cout < min_c:
+    if Cin < 16 or Cout < 16:
         return False
     return bool(_lib.load_library().vs_conv3_band_supported(dtype_code(x), B, Cin, H, W, Cout))
 
@@ -1439,8 +1425,7 @@ def bn_small_supported(x, groups=1):
     if groups > 1:
         # several calls stacked along the batch axis in one launch (vs_bn_train_fwd_small_groups): measured on the TaxiBJ step and NOT the
         # default -- 8.95 ms with it, 8.93 without (the two-launch path's kernels overlap with their neighbours just as well)
-        import os
-        if os.environ.get('VS_BN_SMALL_GROUPS', '0') != '1' or B % groups != 0:
+        if not bn_small_groups_enabled() or B % groups != 0:
             return False
     return x.is_contiguous() and bool(_lib.load_library().vs_bn_train_fwd_small_supported(dtype_code(x), B // groups, C, x.numel() // (B * C)))
 
@@ -1598,10 +1583,10 @@ def exchange_epoch_advance(device=None):
 
 def conv3_img16_bn_supported(B, Cin, Cout, dtype, act='leaky_relu', out_dtype=None, backward=False):
     """Whether conv3_img16_bn_fwd / _bwd serve a Conv2d k3 s1 p1 (Cin -> Cout) -> BatchNorm -> `act` layer on B maps of 16 x 16 with output type
-    `out_dtype` (forward).  VS_IMG_BN_FUSED=0: never; VS_IMG_BN_SPLITS (default '1'): the input-channel split counts served -- with several
+    `out_dtype` (forward).  VS_IMG_BN_SPLITS (default '1'): the input-channel split counts served -- with several
     splits the partial sums cross the chip inside the launch, which costs what the kernel boundary it replaces costs (measured)."""
     import os
-    if os.environ.get('VS_IMG_BN_FUSED', '1') == '0' or dtype == torch.float32:
+    if dtype == torch.float32:
         return False
     lib = _lib.load_library()
     if not lib.vs_conv3_img16_bn_supported(code_of(dtype), B, Cin, Cout):

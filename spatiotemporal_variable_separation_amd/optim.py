@@ -8,7 +8,6 @@ WaveEq model keep every CU streaming.  The step count lives on the device, so `s
 (train.GraphedStep) without `capturable=True` plumbing.  Only what the reference uses is supported: no weight decay, no
 amsgrad, no maximize; fp32 CUDA parameters (anything else raises: there is no CPU fallback on the product path)."""
 import ctypes
-import os
 
 import torch
 
@@ -93,8 +92,7 @@ class Adam(torch.optim.Optimizer):
         group = self.param_groups[0]
         self._init_group(0, group)
         from . import functional as VF
-        bg = int(os.environ.get('VARSEP_ADAM_BG_BLOCKS', '512'))
-        if VF.defer_call(lambda: self._update(0, group, self._buckets[bi], max_blocks=bg), late=os.environ.get('VARSEP_ADAM_EARLY_BUCKET') == '2'):
+        if VF.defer_call(lambda: self._update(0, group, self._buckets[bi], max_blocks=512)):
             # the bucket's weight gradients are being held back (functional.hold_deferred): the update joins that queue and runs
             # on the gradient stream right behind them; step() joins that stream like any deferred gradient work
             self._launched.add(bi)

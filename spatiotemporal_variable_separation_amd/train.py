@@ -123,35 +123,21 @@ def _compute_losses_mlp_batched(cond, target, sep_net, nt_cond, nt_pred, offset,
     if t_random is None:
         t_random = np.random.randint(nt_cond, T) if offset == 0 else np.random.randint(nt_cond, T + 1)
 
-    step_start = None
-    if (VF.side_streams_enabled() and flat.is_cuda and not isinstance(sep_net.Es, ConstantS) and os.environ.get('VARSEP_ES_EARLY', '0') in ('1', '2')):
-        step_start = torch.cuda.Event()
-        step_start.record()
-
     def window(end):
         return flat[:, end - nt_cond:end].reshape(B, -1)
 
     def spatial_codes():
         if isinstance(sep_net.Es, ConstantS):
             return sep_net.Es(full_data[:, :nt_cond]), sep_net.Es(full_data[:, -nt_cond:])
-        with VF.on_chain_forward_stream():           # (the input is built where the chain's forward launches go: see `step_start` below)
-            if on_device:
-                # [first window; last window] in the compute type by ONE kernel (like E_t's input below) instead of a concatenation + a cast
-                x_es = torch.empty((2 * B, nt_cond * D), dtype=VF.compute_dtype(), device=flat.device)
-                ops.copy2d_pair(flat, B, nt_cond * D, T * D, x_es, nt_cond * D, None, 0, 0, (T - nt_cond) * D)
-            else:
-                x_es = torch.cat([window(nt_cond), window(T)], dim=0)
+        if on_device:
+            # [first window; last window] in the compute type by ONE kernel (like E_t's input below) instead of a concatenation + a cast
+            x_es = torch.empty((2 * B, nt_cond * D), dtype=VF.compute_dtype(), device=flat.device)
+            ops.copy2d_pair(flat, B, nt_cond * D, T * D, x_es, nt_cond * D, None, 0, 0, (T - nt_cond) * D)
+        else:
+            x_es = torch.cat([window(nt_cond), window(T)], dim=0)
         s_both = sep_net.Es.mlp(x_es)
         return s_both.view(2, B, -1).unbind(0)       # unbind: its gradient is ONE stack kernel (two slices: fill+copy each, then add)
 
-    if (VF.side_streams_enabled() and torch.is_grad_enabled() and VF.compute_dtype() != torch.float32
-            and os.environ.get('VARSEP_PREPACK_EARLY', '0') == '1' and hasattr(sep_net.t_resnet, 'prepack')):
-        # the integrator's weight packs depend on the weights only: on the integrator's stream, ahead of everything.  Measured and NOT the
-        # default: 1.451-1.459 vs 1.450 ms (the 8 us launch leaves the critical path, the replayed step does not get shorter)
-        main, side = torch.cuda.current_stream(), VF._side_stream('rollout')
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            sep_net.t_resnet.prepack()
     if on_device:
         # rows [0, B): full[:, t - nt_cond : t] cut out by a kernel that reads t on the device; rows [B, 2B): the conditioning window
         x_et = torch.empty((2 * B, nt_cond * D), dtype=VF.compute_dtype(), device=flat.device)
@@ -170,30 +156,13 @@ def _compute_losses_mlp_batched(cond, target, sep_net, nt_cond, nt_pred, offset,
         t0.record_stream(side)
         with torch.cuda.stream(side):
             t_codes, _ = sep_net.t_resnet.rollout(t0, n)
-        if step_start is not None:
-            # E_s on a stream of its own that depends on the START of the step only: in the replayed recording its first layer (a 250-workgroup
-            # GEMM that streams 49 MB of weights) runs beside E_t's small layers instead of under the integrator's kernel, whose 192 resident
-            # workgroups leave it 64 CUs (timeline of round 6: 84 us there against 28 us alone, and E_s's chain -- 200 us -- outlasted the
-            # integrator's 148).  Only the FORWARD launches move (functional.chain_forward_stream): the chain's autograd node is created under
-            # the main stream, so backward runs where it ran before -- a sixth concurrent branch in backward is the runtime's scheduling cliff
-            # (2.50 ms per step, measured with the whole chain, backward included, on the new stream).
-            # MEASURED AND NOT THE DEFAULT (VARSEP_ES_EARLY=1: a stream of its own, 2: the last gradient lane's stream, idle in forward), same box,
-            # alternating with the default: '1' 2.64 / 2.64 / 2.67 ms -- a sixth stream in the recording is the same cliff as six hardware queues
-            # (profiles/r06_queues.md) even though only three branches are ever concurrent in forward; '2' 1.178 / 1.174 / 1.175 against
-            # 1.147 / 1.152 / 1.164 -- E_s's first layer then competes with E_t's chain, which the integrator (the critical path) waits for.
-            es = VF._lane_stream(VF.N_LANES - 1) if os.environ.get('VARSEP_ES_EARLY', '0') == '2' else VF._side_stream('es')
-            es.wait_event(step_start)
-            with VF.chain_forward_stream(es):
-                s_old, s_new = spatial_codes()
-            main.wait_stream(es)
-        else:
-            s_old, s_new = spatial_codes()
+        s_old, s_new = spatial_codes()
         main.wait_stream(side)
         t_codes.record_stream(main)
     else:
         s_old, s_new = spatial_codes()
         t_codes, _ = sep_net.t_resnet.rollout(t0, n)
-    handoff = VF.GradHandoff() if os.environ.get('VARSEP_LOSS_HANDOFF', '1') == '1' else None
+    handoff = VF.GradHandoff()
     # both frame losses in one fused pass: frame 0 vs full[:, t_random - offset], frame g vs full[:, fo + g - 1]
     fo = nt_cond if offset == 0 else 0
     # t_codes[:, 0] IS t0 (the rollout copies its input there), so the regulariser reads the encoder output directly
@@ -203,14 +172,14 @@ def _compute_losses_mlp_batched(cond, target, sep_net, nt_cond, nt_pred, offset,
     t0_f = t0.reshape(B, -1).float().contiguous()
     flat_c = flat.contiguous()
     up = VF.promised_loss_gradient()
-    if (frames_unused and handoff is not None and on_device and up is not None and torch.is_grad_enabled()
+    if (frames_unused and on_device and up is not None and torch.is_grad_enabled()
             and VF.compute_dtype() != torch.float32 and os.environ.get('VARSEP_FUSE_FRAME_LOSS', '1') == '1'):
         # recorded step (nobody reads the frames): the decoder's last GEMM compares them with their targets in its epilogue and
         # writes the gradient of its pre-activation; neither the fp32 frame stack nor a loss pass over it exists (functional.MLPChain)
         handoff.fuse = dict(full=flat_c, idx=(t_random, offset, fo), G=1 + n, s_old=s_old_f, s_new=s_new_f, t0=t0_f,
                             lambdas=(lamb_ae, lamb_s, lamb_t, lamb_pred), average=average_tloss, up=up)
     frames = sep_net.decoder.decode_rollout(s_old, t_rand, t_codes, handoff=handoff)                      # [B, 1+n, ...]
-    forecasts = None if (handoff is not None and handoff.fused is not None) else frames[:, 1:]
+    forecasts = None if handoff.fused is not None else frames[:, 1:]
     if on_device:
         idx = (t_random, offset, fo)                 # resolved inside the loss kernels: no index tensor to build per step
     else:
@@ -218,7 +187,7 @@ def _compute_losses_mlp_batched(cond, target, sep_net, nt_cond, nt_pred, offset,
     total_loss, ae_loss_value, spatial_ode_loss, forecast_loss, t_reg = VF.TrainLosses.apply(
         frames.reshape(B, 1 + n, -1), flat_c, idx, s_old_f, s_new_f, t0_f, (lamb_ae, lamb_s, lamb_t, lamb_pred), average_tloss, handoff)
     terms = {'ae': ae_loss_value, 'zero': spatial_ode_loss, 'pred': forecast_loss, 't_reg': t_reg}
-    if VF.side_streams_enabled() and os.environ.get('VARSEP_HOLD_WGRADS', '1') == '1':
+    if VF.side_streams_enabled():
         # backward: collect the decoder's and E_s's weight gradients and launch them under the integrator's backward kernel
         VF.hold_deferred(True)
     return total_loss, terms, forecasts, t_codes
@@ -251,7 +220,7 @@ class GraphedStep:
         # chains therefore write straight into its flat buckets (VF.set_grad_outputs) instead of going through autograd's `+=`
         # side streams and direct gradient destinations need ONE gradient per parameter and step: true for the batched MLP-family
         # step only (a conv family calls E_s twice, its Linear layers get two contributions)
-        self.side_streams = side_streams and self.mlp and os.environ.get('VARSEP_GRAPH_SIDE', '1') == '1'
+        self.side_streams = side_streams and self.mlp
         check_optimizer(optimizer, for_graph=True)
         self.net, self.opt, self.sync, self.scaler = sep_net, optimizer, grad_sync, scaler
         # conv families under a reducer: convolution / BatchNorm gradients accumulate straight into the reducer's bucket views
@@ -260,11 +229,10 @@ class GraphedStep:
         self._conv_sinks = conv_gradient_sinks(sep_net, grad_sync) if (grad_sync is not None and not self.mlp) else None
         # ... and its backward pass is recorded in TWO segments split at the decoder's inputs when the reducer keeps the decoder's gradients
         # in buckets of their own (GradAllReducer(early=decoder parameters)): their all-reduce is issued between the two replays and travels
-        # on the comm stream while the integrator's / encoders' backward kernels run (VARSEP_GRAPH_SEGMENTS=0: one segment, as in round 3)
+        # on the comm stream while the integrator's / encoders' backward kernels run
         self.segmented = (grad_sync is not None and not self.mlp and bool(getattr(grad_sync, 'early_buckets', None))
                           and getattr(sep_net, 'fused', False) and getattr(sep_net.Es, 'call_groups', False) and getattr(sep_net.Et, 'call_groups', False)
-                          and hasattr(sep_net.decoder, 'decode_sequence') and os.environ.get('VARSEP_GRAPH_SEGMENTS', '1') == '1'
-                          and os.environ.get('VARSEP_ENCODER_PAIRS', '1') == '1')
+                          and hasattr(sep_net.decoder, 'decode_sequence'))
         # single process, conv family: the same destinations WITHOUT a reducer (one flat fp32 buffer, zeroed at the start of the step) --
         # a weight gradient that accumulates into a tensor autograd never sees can run on a gradient stream beside the input-gradient /
         # BatchNorm chain it does not feed (functional._conv_weight_grad); joined before the optimizer.  VARSEP_CONV_WGRAD_SIDE=1 turns it on;
@@ -292,13 +260,11 @@ class GraphedStep:
         if self.sharded:
             grad_sync.adopt_operand_copies(VF.compute_dtype())
         # under a reducer the recorded step seeds its loss gradient with 1 / world_size and the collectives SUM (GradAllReducer.presummed);
-        # with loss scaling the scale tensor is the seed, so that path keeps ReduceOp.AVG.  VARSEP_DDP_PRESUM=0: averages as before
-        self.presum = bool(grad_sync is not None and hasattr(grad_sync, 'presummed')
-                           and (self.sharded or (scaler is None and os.environ.get('VARSEP_DDP_PRESUM', '1') == '1')))
+        # with loss scaling the scale tensor is the seed, so that path keeps ReduceOp.AVG
+        self.presum = bool(grad_sync is not None and hasattr(grad_sync, 'presummed') and (self.sharded or scaler is None))
         if self.presum:
             self._one = torch.full((), 1.0 / grad_sync.world_size, dtype=torch.float32, device=cond.device)
         enable_fused_update(optimizer, sep_net, grad_sync, scaler)
-        enable_update_in_backward(optimizer, sep_net, grad_sync, scaler=scaler)
         self.args = (nt_cond, nt_pred, offset) + tuple(lambdas) + (average_tloss,)
         # static inputs of the recording: one [B, T, ...] buffer, cond / target are views of it (no concatenation per step)
         self.full = torch.cat([cond, target], dim=1).contiguous()
@@ -386,7 +352,7 @@ class GraphedStep:
             finally:
                 VF.bn_counts_flushed_in_capture(False)
             self._reduce()
-            if self.sharded or (self.scaler is None and hasattr(self.opt, 'step_subset') and os.environ.get('VARSEP_ADAM_PER_BUCKET', '1') == '1'):
+            if self.sharded or (self.scaler is None and hasattr(self.opt, 'step_subset')):
                 # one Adam recording per all-reduce bucket: the update of bucket i runs while buckets i+1.. are still on the wire
                 self.graph_opt = []
                 for bi, (_, plist) in enumerate(grad_sync.buckets):
@@ -498,7 +464,7 @@ class GraphedStep:
         VF.enable_side_streams(self.side_streams)
         VF.collect_cuts(segment == 1)
         up = self._one if self.scaler is None else self.scaler.scale_tensor()
-        VF.promise_loss_gradient(up if (self.mlp and os.environ.get('VARSEP_LOSS_ONE_PASS', '1') == '1') else None)
+        VF.promise_loss_gradient(up if self.mlp else None)
         try:
             if self.mlp:
                 total, _, _, _ = _compute_losses_mlp_batched(self.cond, self.target, self.net, nt_cond, nt_pred, offset, l_ae, l_s, l_t,
@@ -513,7 +479,7 @@ class GraphedStep:
                 total.backward(up)
             from .optim import Adam as HipAdam
             partial = (self.sync is None and self.scaler is None and isinstance(self.opt, HipAdam)
-                       and bool(getattr(self.opt, '_fused', None)) and VF.tail_fused_updates())
+                       and bool(getattr(self.opt, '_fused', None)))
             self._pending_join = VF.join_side_streams(partial=partial)
         finally:
             VF.collect_cuts(False)
@@ -671,11 +637,10 @@ def enable_update_in_backward(optimizer, sep_net, grad_sync=None, force=False, s
     of their gradients is final, i.e. while backward is still in E_t (optim.Adam.overlap_with_backward).  One bucket on
     purpose: the update streams HBM at >5 TB/s and, launched earlier, would run beside the integrator's backward kernel,
     whose inter-workgroup exchange is latency-bound on the same memory fabric (measured: 204 -> 275 us)."""
-    # Opt-in (VARSEP_ADAM_OVERLAP=1): on the WaveEq step it is a wash (1.898 vs 1.891 ms) -- the update and E_t's backward
+    # Only with force=True: on the WaveEq step it is a wash (1.898 vs 1.891 ms) -- the update and E_t's backward
     # (98 MB of fp32 weight gradient per encoder) compete for the same HBM bandwidth, both just run slower side by side.
     from .optim import Adam as HipAdam
-    early_only = os.environ.get('VARSEP_ADAM_EARLY_BUCKET') in ('1', '2')
-    if not force and os.environ.get('VARSEP_ADAM_OVERLAP') != '1' and not early_only:
+    if not force:
         return
     if scaler is not None:
         # fp16 loss scaling: the update needs 1 / scale and the finite check of ALL gradients, which exist only after backward
@@ -685,13 +650,6 @@ def enable_update_in_backward(optimizer, sep_net, grad_sync=None, force=False, s
         owned = {id(p) for p in optimizer.param_groups[0]['params']}
         fused = {id(p) for p in getattr(optimizer, '_fused', [])}        # updated inside their weight-gradient GEMMs: in no bucket
         early = [p for m in (sep_net.decoder, sep_net.Es) for p in m.parameters() if id(p) in owned and id(p) not in fused]
-        if early_only and not force:
-            # decoder + E_s only: their gradients are complete once the held weight gradients have run (under the integrator's
-            # backward kernel), the update joins that queue; the optimizer launch at the end of the step shrinks to E_t + integrator.
-            # (The integrator's own gradients are recorded at the very end of backward -- functional.run_late -- after its hooks.)
-            if early:
-                optimizer.overlap_with_backward([early])
-            return
         buckets = [early, [p for p in sep_net.t_resnet.parameters() if id(p) in owned and id(p) not in fused],
                    [p for p in sep_net.Et.parameters() if id(p) in owned and id(p) not in fused]]
         if sum(len(b) for b in buckets) + len(fused) == len(owned):
@@ -708,7 +666,6 @@ def enable_fused_update(optimizer, sep_net, grad_sync=None, scaler=None, min_num
         return False
     if grad_sync is not None or scaler is not None or not _mlp_family(sep_net) or len(optimizer.param_groups) != 1 or optimizer._buckets:
         return False
-    min_numel = int(os.environ.get('VARSEP_FUSE_ADAM_MIN', min_numel))
     big = [p for p in chain_weight_parameters(sep_net) if p.numel() >= min_numel]
     if not big:
         return False
@@ -869,7 +826,8 @@ def recover_exchange(device, log=True, grad_sync=None):
     if err & 1:
         ops.rollout_xcd_local(False)
     if err & 2:
-        os.environ['VARSEP_FUSED_RESBLOCK'] = '1'
+        from . import functional as VF
+        VF.resblock_two_launch_only(True)
     if log:
         # (the fused weight-gradient updates -- vs_gemm_adam -- issued in the SAME backward pass before the exchange timed out have been applied:
         # that one step is partial (decoder updated, the rest not); every later step was skipped as a whole)
@@ -892,12 +850,12 @@ def compute_losses(cond, target, sep_net, nt_cond, nt_pred, offset, skipco, lamb
     if cond.is_cuda and torch.is_grad_enabled():
         from . import ops
         ops.exchange_epoch_advance(cond.device)      # the fused ConvResBlock layers number their launches from 1 under a new epoch base
-    if cond.is_cuda and torch.is_grad_enabled() and os.environ.get('VARSEP_PREPACK_CONV', '1') == '1':
+    if cond.is_cuda and torch.is_grad_enabled():
         from . import functional as VF
         VF.prepack_conv3_weights(sep_net)            # every stale 3x3 weight pre-pack of the step in one launch
     full_data = torch.cat([cond, target], dim=1)
     pairs = (cond.is_cuda and getattr(sep_net, 'fused', False) and getattr(sep_net.Es, 'call_groups', False)
-             and getattr(sep_net.Et, 'call_groups', False) and os.environ.get('VARSEP_ENCODER_PAIRS', '1') == '1')
+             and getattr(sep_net.Et, 'call_groups', False))
     if pairs:
         # the reference calls each encoder twice per step (E_s on the first and the last window, E_t on the random and the
         # conditioning window): run each pair as ONE batch of two call groups -- every BatchNorm keeps per-call statistics and
@@ -940,7 +898,7 @@ def compute_losses(cond, target, sep_net, nt_cond, nt_pred, offset, skipco, lamb
             reconstruction = sep_net.decoder(d_s[0], d_t, skip=d_s[1])
         else:
             reconstruction = sep_net.decoder(d_s, d_t)
-        fused_mse = os.environ.get('VARSEP_FUSED_FRAME_MSE', '1') == '1' and full_data.dtype == torch.float32
+        fused_mse = full_data.dtype == torch.float32
         ae_idx = None
         if fused_mse:
             from . import functional as VF
@@ -954,7 +912,7 @@ def compute_losses(cond, target, sep_net, nt_cond, nt_pred, offset, skipco, lamb
             forecasts, t_codes, _, _ = sep_net.get_forecast(cond, nt_pred + offset, init_t_code=t_cond, init_s_code=s_old, rolled=rolled)
         else:
             forecasts, t_codes, _, _ = sep_net.get_forecast(cond, nt_pred + offset, init_t_code=t_cond, init_s_code=s_old)
-        if fused_mse and os.environ.get('VARSEP_FUSED_CONV_LOSSES', '1') == '1':
+        if fused_mse:
             # the four losses and their weighted sum in 4 launches (3 backward): no concatenation of the skip tensors, no scalar launches.
             # t_codes[:, 0] IS t_cond (the first code of the rollout): the regulariser reads the encoder output directly, so its gradient
             # does not travel through a zero-filled [B, n, ...] tensor

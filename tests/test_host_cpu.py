@@ -188,3 +188,33 @@ def test_fp32_split_pieces_reconstruct_the_value_and_six_products_the_convolutio
     e6 = ((six - ref).norm() / ref.norm()).item()
     e3 = ((three - ref).norm() / ref.norm()).item()
     assert e6 < 2e-7 and e3 > 20 * e6, (e6, e3)
+
+
+def _switches_read_by_the_package():
+    """Every VARSEP_* / VS_* name the package reads from the environment: os.environ.get / os.environ[...] / `in os.environ` / os.getenv in its
+    Python, getenv("...") in csrc/."""
+    import glob
+    pkg = os.path.join(ROOT, 'spatiotemporal_variable_separation_amd')
+    name = r'''['"]((?:VARSEP|VS)_[A-Z0-9_]+)['"]'''
+    py = [r'environ\.get\(\s*' + name, r'environ\[\s*' + name + r'\s*\]', name + r'\s+(?:not\s+)?in\s+\w*\.?environ\b', r'getenv\(\s*' + name]
+    found = set()
+    for path in glob.glob(os.path.join(pkg, '**', '*.py'), recursive=True):
+        text = open(path).read()
+        for pat in py:
+            found.update(re.findall(pat, text))
+    for path in glob.glob(os.path.join(pkg, 'csrc', '*.hip')) + glob.glob(os.path.join(pkg, 'csrc', '*.h')):
+        found.update(re.findall(r'getenv\(\s*"((?:VARSEP|VS)_[A-Z0-9_]+)"', open(path).read()))
+    return found
+
+
+def test_every_environment_switch_is_in_the_integration_table():
+    """INTEGRATION.md, section "Environment switches", has one row per switch the package reads, and no row for a switch nothing reads: a new
+    switch needs a row (name, where it is read, values, default, who uses it), a retired one loses its row."""
+    text = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    m = re.search(r'^## Environment switches\n(.*?)(?=^## |\Z)', text, flags=re.S | re.M)
+    assert m, 'INTEGRATION.md has no section "Environment switches"'
+    rows = re.findall(r'^\|\s*`((?:VARSEP|VS)_[A-Z0-9_]+)`\s*\|', m.group(1), flags=re.M)
+    assert len(rows) == len(set(rows)), sorted(r for r in set(rows) if rows.count(r) > 1)
+    read = _switches_read_by_the_package()
+    assert len(read) >= 30
+    assert set(rows) == read, {'read but not in the table': sorted(read - set(rows)), 'in the table but not read': sorted(set(rows) - read)}
