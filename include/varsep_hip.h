@@ -333,6 +333,16 @@ int vs_frame_metrics(const float* pred, const float* target, int64_t planes, int
 int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
                           int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream);
 
+/* One batch of 3D Chairs sequences gathered from the decoded views resident in HBM (reference: data/chairs.py:45-64 `get_sequence` +
+ * `__getitem__`, for a whole batch of items).  frames [n_objects, views_per_object, H, W, C] uint8, HWC as `np.array(Image.open(f))`
+ * yields; desc [rows, 2] int32 = (object, first view); out [rows, seq_len, C, H, W] (fp32 or a 16-bit type).  Frame t of a row is view
+ * (first + t) % views_per_object (the reference's wrap-around, chairs.py:56-57); a value is (float)byte / 255.f, an IEEE division: the
+ * bits of the reference's float64 `/ 255` rounded to float32, for all 256 bytes.  The HWC -> CHW transposition happens in the launch.
+ * A descriptor whose object is outside [0, n_objects) or whose first view is outside [0, views_per_object) writes its row as zeros and
+ * sets *bad = 1 (bad may be NULL); the launch never reads out of bounds.  At most 65535 rows per launch.                              */
+int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int views_per_object, int H, int W, int C, const int32_t* desc, int64_t rows,
+                     int seq_len, void* out, int out_dtype, int32_t* bad, void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

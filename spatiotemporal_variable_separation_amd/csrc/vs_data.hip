@@ -1,4 +1,5 @@
-// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253).
+// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253) and the 3D
+// Chairs batch gather (reference: data/chairs.py:45-64, at the end of this file).
 //
 // The reference builds every training sequence on the host: per digit five draws from the global NumPy stream (digit index, start
 // position, speed), a trajectory of `seq_len` positions with elastic bounces off the frame borders computed in Python floats
@@ -95,7 +96,92 @@ __global__ __launch_bounds__(256) void moving_mnist_kernel(const unsigned char* 
     }
 }
 
+// ---- 3D Chairs: batch gather from the decoded views resident in HBM (data/chairs.py:45-64) ----------------------------------------
+// The reference opens and decodes seq_len PNG files per item on the host, stacks them HWC, divides by 255 in float64, rounds to float32
+// and permutes to CHW.  Here every view of the split is decoded once and kept as uint8 [n_objects][views][H][W][C]; a batch is one
+// launch: grid (seq_len, rows), one workgroup per output frame.  desc[row] = (object, first view); frame t is view
+// (first + t) % views (chairs.py:56-57).  (float)byte / 255.f as an IEEE division has, for all 256 bytes, the bits of the reference's
+// float64 division rounded to float32.
+//
+// C == 3 (the dataset): a thread owns PIX consecutive pixels = 3 * PIX consecutive bytes of the HWC frame (PIX = 4 for fp32 output: 12 B,
+// PIX = 8 for 16-bit output: 24 B), so a wave reads one contiguous 768 B / 1536 B span, and stores one 16 B vector per channel plane: a
+// wave writes 1 KiB contiguous per plane.  Both sides are coalesced without an LDS pass: the transposition is a register shuffle of the
+// thread's own bytes.  Other channel counts or H * W not a multiple of PIX take the element-wise form.
+template <int PIX, bool LOWP>
+__device__ __forceinline__ void chairs_frame_c3(const unsigned char* __restrict__ src, void* out, int64_t obase, int hw, int od) {
+    constexpr int NW = 3 * PIX / 4;
+    for (int g = threadIdx.x; g < hw / PIX; g += blockDim.x) {
+        unsigned int w[NW];
+        const unsigned int* p = reinterpret_cast<const unsigned int*>(src) + (int64_t)g * NW;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) w[j] = p[j];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v[PIX];
+#pragma unroll
+            for (int k = 0; k < PIX; ++k) {
+                const int byte = 3 * k + c;
+                v[k] = __fdiv_rn((float)((w[byte >> 2] >> (8 * (byte & 3))) & 0xffu), 255.f);
+            }
+            const int64_t o = obase + (int64_t)c * hw + (int64_t)g * PIX;
+            if constexpr (!LOWP) {
+                f32x4 q = {v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<f32x4*>((float*)out + o) = q;
+            } else {
+                u16x8 q;
+#pragma unroll
+                for (int k = 0; k < PIX; ++k) q[k] = vs_f2h(v[k], od);
+                *reinterpret_cast<u16x8*>((unsigned short*)out + o) = q;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void chairs_gather_kernel(const unsigned char* __restrict__ frames, int64_t n_objects, int views, int hw, int C,
+                                                            const int* __restrict__ desc, int T, void* out, int od, int vec, int* bad) {
+    const int t = blockIdx.x;
+    const int64_t row = blockIdx.y;
+    const int obj = desc[row * 2], first = desc[row * 2 + 1];
+    const bool ok = obj >= 0 && (int64_t)obj < n_objects && first >= 0 && first < views;        // uniform over the workgroup
+    const int64_t fe = (int64_t)hw * C;
+    const int64_t obase = (row * T + t) * fe;
+    if (!ok) {                                           // the row is written as zeros, nothing is read
+        if (bad && threadIdx.x == 0) *bad = 1;
+        for (int64_t i = threadIdx.x; i < fe; i += blockDim.x) vs_st(out, od, obase + i, 0.f);
+        return;
+    }
+    const unsigned char* src = frames + ((int64_t)obj * views + ((int64_t)first + t) % views) * fe;
+    if (vec) {
+        if (od == VS_F32) chairs_frame_c3<4, false>(src, out, obase, hw, od);
+        else chairs_frame_c3<8, true>(src, out, obase, hw, od);
+        return;
+    }
+    for (int64_t i = threadIdx.x; i < fe; i += blockDim.x) {       // out element (c, pix) <- byte pix * C + c
+        const int64_t c = i / hw, pix = i - c * hw;
+        vs_st(out, od, obase + i, __fdiv_rn((float)src[pix * C + c], 255.f));
+    }
+}
+
 }  // namespace
+
+extern "C" int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int views_per_object, int H, int W, int C, const int32_t* desc, int64_t rows,
+                                int seq_len, void* out, int out_dtype, int32_t* bad, void* stream) {
+    VS_CHECK_ARG(frames && desc && out, "vs_chairs_gather: null pointer");
+    VS_CHECK_ARG(n_objects > 0 && views_per_object > 0 && H > 0 && W > 0 && C > 0 && rows > 0, "vs_chairs_gather: sizes must be positive");
+    VS_CHECK_ARG(seq_len >= 1, "vs_chairs_gather: seq_len >= 1");
+    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "vs_chairs_gather: bad out_dtype");
+    VS_CHECK_ARG(rows < 65536, "vs_chairs_gather: at most 65535 rows per launch");
+    VS_CHECK_ARG((int64_t)H * W * C < (1ll << 31), "vs_chairs_gather: a frame of %d x %d x %d exceeds 2^31 bytes", H, W, C);
+    const int hw = H * W;
+    const int64_t fe = (int64_t)hw * C;
+    // the vector form needs whole thread spans per frame and aligned vectors: frame starts are multiples of `fe` from the base pointers
+    const int pix = out_dtype == VS_F32 ? 4 : 8;
+    const int vec = C == 3 && hw % pix == 0 && (uintptr_t)frames % 4 == 0 && fe % 4 == 0 && (uintptr_t)out % 16 == 0;
+    hipLaunchKernelGGL(chairs_gather_kernel, dim3((unsigned)seq_len, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, frames, n_objects,
+                       views_per_object, hw, C, desc, seq_len, out, out_dtype, vec, (int*)bad);
+    VS_CHECK_LAUNCH("vs_chairs_gather");
+    return VS_OK;
+}
 
 extern "C" int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
                                      int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream) {

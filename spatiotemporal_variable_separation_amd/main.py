@@ -21,8 +21,8 @@ from .train import train
 
 def load_dataset(args, device=None):
     """`--data_dir synthetic` needs nothing.  The WaveEq sets (main.py:91-102 of the reference) are this package's own HBM-resident
-    datasets (data/wave_eq.py: batches gathered on the device); Moving MNIST is generated on the device (data/moving_mnist.py).
-    Nothing here imports the reference package."""
+    datasets (data/wave_eq.py: batches gathered on the device); Moving MNIST is generated on the device (data/moving_mnist.py); the
+    3D Chairs views are decoded once and gathered on the device (data/chairs.py).  Nothing here imports the reference package."""
     if args.data_dir == 'synthetic':
         return SyntheticSequences(args.data, args.nt_cond, args.nt_pred, length=args.synthetic_len,
                                   seed=args.seed or 1234, n_wave_points=args.n_wave_points)
@@ -36,9 +36,12 @@ def load_dataset(args, device=None):
         from .data.moving_mnist import MovingMNIST                  # sequences generated on the device (data/moving_mnist.py)
         return MovingMNIST.make_dataset(args.data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, True,
                                         device=device, seed=args.seed)
+    if args.data == 'chairs' and device is not None and torch.device(device).type == 'cuda':
+        from .data.chairs import Chairs                             # main.py:77-79 of the reference; views resident in HBM
+        return Chairs(True, args.data_dir, args.nt_cond, seq_len=args.nt_cond + args.nt_pred, device=device)
     raise NotImplementedError(
-        'dataset %r: only the synthetic batches (--data_dir synthetic), the WaveEq sets and Moving MNIST are built into this package; '
-        'the TaxiBJ / SST / chairs loaders of the reference are host-side file readers (h5py / netCDF4 / image folders) outside the '
+        'dataset %r: only the synthetic batches (--data_dir synthetic), the WaveEq sets, Moving MNIST and the 3D Chairs are built into '
+        'this package; the TaxiBJ / SST loaders of the reference are host-side file readers (h5py / netCDF4) outside the '
         'MI355X hot path -- wrap them in any torch Dataset yielding (cond, target) and call train() directly' % args.data)
 
 

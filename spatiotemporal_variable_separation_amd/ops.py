@@ -1909,6 +1909,28 @@ def gather_windows(data, item_idx, windows_per_seq, seq_len, pixel_idx=None, out
     return out
 
 
+def chairs_gather(frames_u8, desc, seq_len, out_dtype=torch.float32, validate=True):
+    """frames_u8 uint8 [n_objects, views, H, W, C] on the device, desc int32 [rows, 2] = (object, first view) -> [rows, seq_len, C, H, W]
+    in `out_dtype`: frame t of a row is view (first + t) % views, values byte / 255 (vs_chairs_gather, one launch).
+    validate=True reads back the launch's error word (a host sync) and raises VarsepHipError for a descriptor out of range;
+    validate=False keeps the call free of host syncs (the caller has checked the table)."""
+    require_cuda(frames_u8, desc)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 5 or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 2:
+        raise _lib.VarsepHipError('chairs_gather: frames uint8 [n_objects, views, H, W, C] and desc int32 [rows, 2] expected')
+    frames_u8, desc = frames_u8.contiguous(), desc.contiguous()
+    n, views, H, W, C = frames_u8.shape
+    rows = desc.shape[0]
+    out = torch.empty((rows, max(int(seq_len), 0), C, H, W), dtype=out_dtype, device=frames_u8.device)
+    bad = torch.zeros((1,), dtype=torch.int32, device=frames_u8.device) if validate else None
+    e0 = _pb()
+    check(_lib.load_library().vs_chairs_gather(frames_u8.data_ptr(), n, views, H, W, C, desc.data_ptr(), rows, int(seq_len), out.data_ptr(),
+                                               _lib.code_of(out_dtype), _ptr(bad), stream_ptr()), 'vs_chairs_gather')
+    _pe(e0, 'vs_chairs_gather', nbytes=float(out.numel() * (1 + out.element_size())))
+    if validate and int(bad.item()):
+        raise _lib.VarsepHipError('chairs_gather: a descriptor names an object outside [0, %d) or a first view outside [0, %d)' % (n, views))
+    return out
+
+
 _MIXING = {'concat': 0, 'mul': 1}
 
 

@@ -1,0 +1,129 @@
+"""3D Warehouse Chairs content-swap (disentanglement) evaluation (reference: test/chairs/test_disentanglement.py:36-182, same flags and
+files):
+
+    python -m spatiotemporal_variable_separation_amd.test.chairs.test_disentanglement --xp_dir X --data_dir D --nt_pred 10 --device 0
+
+S is extracted from a randomly drawn test object seen from a randomly drawn first view; T comes from the test video of the same index;
+the forecast is scored against the drawn object seen along the test video's views.  The test split lives in HBM (data/chairs.py), the
+content and ground-truth videos of a batch come from one gather launch, the metrics run on the device (vs_frame_metrics_multi) and every
+saved array is converted to uint8 on the device (vs_frames_to_u8_nhwc).  There is no CPU mode: --device is required.
+"""
+import os
+
+import numpy as np
+import torch
+
+from ...data.chairs import Chairs
+from ...utils.helper import load_json
+from ..mnist.test_disentanglement import best_of_permutations
+from ..utils import add_precision_flag, base_parser, load_model, print_results, seed_all, setup_device, to_host_u8
+
+
+class SwapDataset(Chairs):
+    """test_disentanglement.py:36-49 on the device.  Item `index` draws a content object and a content first view from the global NumPy
+    stream (in that order) and yields the content video (drawn object, drawn first view) and the ground truth of the swap (drawn object,
+    the index's own first view)."""
+
+    def __init__(self, train, data_root, nt_cond, seq_len=20, image_size=64, device=None):
+        if seq_len >= self.max_length:
+            # the reference's `np.random.randint(self.max_length - self.seq_len)` fails for an empty range
+            raise ValueError('the content swap needs seq_len < %d (got %d)' % (self.max_length, seq_len))
+        super().__init__(train, data_root, nt_cond, seq_len=seq_len, image_size=image_size, device=device)
+
+    def swap_descriptors(self, indices):
+        """int32 [2 * B, 2]: rows 0..B-1 the content videos, rows B..2B-1 the ground truths of the swap.  Two draws per item, in item
+        order, as the reference's sequential loader (num_workers = 0) makes them."""
+        indices = list(indices)
+        idx_content, id_st_content = [], []
+        for _ in indices:
+            idx_content.append(np.random.randint(self.n_objects))
+            id_st_content.append(np.random.randint(self.max_length - self.seq_len))
+        content = self.descriptors(indices, chosen_idx=idx_content, chosen_id_st=id_st_content)
+        gt = self.descriptors(indices, chosen_idx=idx_content)
+        return np.concatenate([content, gt], axis=0)
+
+    def batch(self, indices, out_dtype=torch.float32):
+        """(cond, target, swap_cond, swap_target) of the items, as the reference's DataLoader collates them: [B, nt_cond, 3, 64, 64],
+        [B, seq_len - nt_cond, ...], [B, 1, nt_cond, ...], [B, 1, seq_len - nt_cond, ...]; one gather launch for all 2 B videos."""
+        indices = list(indices)
+        B = len(indices)
+        v = self.gather(self.swap_descriptors(indices), out_dtype)
+        content, gt = v[:B], v[B:].unsqueeze(1)
+        return content[:, :self.nt_cond], content[:, self.nt_cond:], gt[:, :, :self.nt_cond], gt[:, :, self.nt_cond:]
+
+    def __getitem__(self, index):
+        return tuple(t[0] for t in self.batch([int(index)]))
+
+
+def load_dataset(args, train=False, device='cuda'):
+    return Chairs(train, args.data_dir, args.nt_cond, seq_len=args.nt_cond + args.nt_pred, device=device)
+
+
+def main(args):
+    device = setup_device(args)
+    seed_all(args.test_seed)
+    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
+    xp_config.device = device
+    xp_config.data_dir = args.data_dir
+    xp_config.xp_dir = args.xp_dir
+    xp_config.nt_pred = args.nt_pred
+    xp_config.n_object = 1           # reference quirk: forced to 1 whatever params.json says (one "permutation" is scored)
+
+    print('Loading data...')
+    test_dataset = load_dataset(xp_config, train=False, device=device)
+    swap_dataset = SwapDataset(False, args.data_dir, xp_config.nt_cond, seq_len=xp_config.nt_cond + args.nt_pred, device=device)
+
+    print('Loading model...')
+    sep_net = load_model(xp_config, args.epoch)
+
+    print('Generating samples...')
+    torch.set_grad_enabled(False)
+    nt_test = xp_config.nt_cond + args.nt_pred
+    gt_swap, content_swap, cond_swap, target_swap = [], [], [], []
+    results = {'mse': [], 'psnr': [], 'ssim': []}
+    # both of the reference's loaders are sequential with the same batch size over sets of the same length: batch k of either holds
+    # items [k * batch_size, (k + 1) * batch_size), the last one ragged in both
+    for start in range(0, len(test_dataset), args.batch_size):
+        items = range(start, min(start + args.batch_size, len(test_dataset)))
+        # reference quirk: the swap item's own target frames (`x_target`) are never used
+        x_cond, _, _, x_gt_swap = swap_dataset.batch(items)
+        x_swap_cond, x_swap_target = test_dataset.batch(items)
+
+        # Extraction of S
+        _, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
+
+        # Content swap (reference quirk kept: `cond_swap_test` holds the content video's conditioning frames `x_cond`, not the swap
+        # video's `x_swap_cond`)
+        cond_swap.append(to_host_u8(x_cond))
+        target_swap.append(to_host_u8(x_swap_target))
+        x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
+        x_swap_pred = x_swap_pred[:, xp_config.nt_cond:].float().contiguous()
+        content_swap.append(to_host_u8(x_swap_pred))
+        # reference quirk: `gt_swap` is `x_gt_swap[:, 0]`, the first (and, with n_object = 1, only) candidate
+        gt_swap.append(to_host_u8(x_gt_swap[:, 0]))
+
+        # Pixelwise quantitative eval: P = 1 candidate per sample, so the best-of-permutations min / max are the values themselves
+        metrics_batch = best_of_permutations(x_swap_pred, x_gt_swap.float())
+        for name in results:
+            results[name].append(metrics_batch[name].cpu())
+
+    results = print_results(results)
+
+    np.savez_compressed(os.path.join(args.xp_dir, 'results_swap.npz'), **results)
+    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap_gt.npz'), gt_swap=torch.cat(gt_swap).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap_test.npz'), content_swap=torch.cat(content_swap).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'cond_swap_test.npz'), cond_swap=torch.cat(cond_swap).numpy())
+    np.savez_compressed(os.path.join(args.xp_dir, 'target_swap_test.npz'), target_swap=torch.cat(target_swap).numpy())
+    return results
+
+
+def build_parser():
+    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (3D Warehouse Chairs content swap testing)', batch_size=16)
+    p.add_argument('--test_seed', type=int, metavar='SEED', default=1,
+                   help='Manual seed.')
+    add_precision_flag(p)
+    return p
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())
