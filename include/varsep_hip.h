@@ -89,6 +89,13 @@ int vs_gemm_batched(int compute, int batch, int64_t M, int64_t N, int64_t K, con
 
 size_t vs_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
 
+/* Which tile kernel, in how many K splits, vs_gemm_batched (vs_gemm: batch 1, strides 0) runs for these arguments.  Host only, no GPU call;
+ * A and B are looked at for alignment only.  out[12]: kind (0 register-staged tile, 1 LDS-DMA 128x128 tile, 2 128x128 ring tile, 3 256x256
+ * tile, 4 staggered 256-row tile), tile rows, tile columns, splits, K tiles per split, tiles along M, tiles along N, ring stages (kind 2),
+ * ni, mi (kind 4), 1 if split-K may be finished inside the launch (VS_GEMM_SPLITK_FUSED), workspace bytes this call needs.             */
+int vs_gemm_plan(int compute, int batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int64_t stride_a, int layout_a,
+                 const void* B, int64_t ldb, int64_t stride_b, int layout_b, int64_t* out);
+
 int vs_gemm(int compute, int64_t M, int64_t N, int64_t K,
             const void* A, int64_t lda, int layout_a,
             const void* B, int64_t ldb, int layout_b,

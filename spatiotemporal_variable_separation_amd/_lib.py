@@ -102,6 +102,7 @@ SIGNATURES = {
     'vs_version': (ctypes.c_char_p, []),
     'vs_last_error': (ctypes.c_char_p, []),
     'vs_gemm_workspace_bytes': (_sz, [_i64, _i64, _i64]),
+    'vs_gemm_plan': (_i32, [_i32, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, ctypes.POINTER(_i64)]),
     'vs_gemm': (_i32, [_i32, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _f32, _vp, _i32,
                        _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
     'vs_cast': (_i32, [_vp, _i32, _vp, _i32, _i64, _vp]),

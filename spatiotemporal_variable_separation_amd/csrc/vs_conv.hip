@@ -31,8 +31,7 @@
 // Reference call sites: every nn.Conv2d / nn.ConvTranspose2d of networks/conv.py:119-122,147-170,258-263,294-318,
 // 326-343,362-382,402-417 and networks/resnet.py:57-59, plus their autograd.
 #include <type_traits>
-#include "vs_gemm_core.h"
-#include "vs_gemm_mid.h"
+#include "vs_gemm_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -262,7 +261,7 @@ int run(const OpA& a, const OpB& b, int64_t M, int64_t N, int64_t K, const Epi& 
         const char* what) {
     typedef typename CTraits<CT>::T T;
     constexpr int BK = CT != VS_F32 ? 64 : 16;
-    Plan plan = make_plan(CT, M, N, K);
+    GemmPlan plan = reg_plan(CT, M, N, K);
     constexpr bool both_dense = std::is_same<OpA, Dense<CT, OpA::layout>>::value && std::is_same<OpB, Dense<CT, OpB::layout>>::value;
     if (!both_dense && plan.bm == 128 && plan.bn == 128) plan.bn = 64;   // gather operands are register hungry: 128x128 drops to 2 waves/SIMD
     if ((!both_dense || CT == VS_F32) && plan.bm == 64 && plan.bn == 128) plan.bn = 64;
@@ -290,23 +289,15 @@ int run(const OpA& a, const OpB& b, int64_t M, int64_t N, int64_t K, const Epi& 
     else VS_LAUNCH(64, 64)
 #undef VS_LAUNCH
     VS_CHECK_LAUNCH(what);
-    if (slabs) {
-        int64_t blocks = vs_cdiv(M * N, 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slabs, plan.splits, M, N, epi);
-        VS_CHECK_LAUNCH(what);
-    }
-    return VS_OK;
+    return slabs ? launch_splitk_reduce(slabs, plan.splits, M, N, epi, 1, stream) : VS_OK;
 }
 
 inline Epi nchw_epi(void* out, int out_dtype, const float* bias, int64_t plane, int64_t channels) {
-    Epi e{out, 0, out_dtype, 1.f, bias, VS_ACT_NONE, nullptr, 0, 0, VS_ACT_NONE, 0, plane, channels, 0, 0, 0, 0, 0, 0, 0};
+    Epi e = plain_epi(out, 0, out_dtype, 1.f);
+    e.bias = bias; e.nchw_hw = plane; e.nchw_c = channels;
     return e;
 }
-inline Epi rowmajor_epi(void* out, int64_t ldc) {
-    Epi e{out, ldc, VS_F32, 1.f, nullptr, VS_ACT_NONE, nullptr, 0, 0, VS_ACT_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    return e;
-}
+inline Epi rowmajor_epi(void* out, int64_t ldc) { return plain_epi(out, ldc, VS_F32, 1.f); }
 
 int check_conv(const char* what, int compute, const void* a, const void* b, const void* c, int B, int Cin, int H, int W, int Cout,
                int kh, int kw, int stride, int pad) {
@@ -1026,13 +1017,7 @@ int wgrad_form(const void* r, const void* gsrc, float* dw, int B, int Cr, int PH
                     int rc2 = mid_launch<CT, LR, LR>(a_ptr, via_dense ? K : hw, ws, ld, M, N, K, splits, ktps, stages, 1, e, slabs, st, via_dense ? 0 : hw);
                     if (rc2 != VS_OK) return rc2;
                     VS_CHECK_LAUNCH(what);
-                    if (slabs) {
-                        int64_t blocks = vs_cdiv(M * N, 256);
-                        if (blocks > 2048) blocks = 2048;
-                        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, slabs, splits, M, N, e);
-                        VS_CHECK_LAUNCH(what);
-                    }
-                    return VS_OK;
+                    return slabs ? launch_splitk_reduce(slabs, splits, M, N, e, 1, st) : VS_OK;
                 }
             }
         }

@@ -19,57 +19,88 @@
 //   * few-tile/long-K problems (encoder first layer: M=128..256, K=20480) are split along K over
 //     gridDim.z into fp32 slabs and combined by a second kernel that also applies the epilogue, so the
 //     result is bitwise reproducible (no float atomics).
-#include "vs_gemm_core.h"
-#include "vs_gemm_glds.h"
-#include "vs_gemm_big.h"
-#include "vs_gemm_mid.h"
-#include "vs_gemm_p8.h"
+#include <type_traits>
+#include "vs_gemm_plan.h"
 #include "vs_loss.h"
 
 namespace {
 
+// one dense contraction as the launchers see it (problem i of a batch: A + i * epi.batch_a, B + i * epi.batch_b)
+struct GemmCall {
+    const void* A; int64_t lda; int la;
+    const void* B; int64_t ldb; int lb;
+    int64_t M, N, K;
+    int batch;
+    hipStream_t stream;
+};
+
+// runtime compute type / operand layouts -> template arguments: f(IC<CT>) and f(IC<CT>, IC<LA>, IC<LB>)
+template <int V> using IC = std::integral_constant<int, V>;
+template <class F>
+int with_compute(int compute, F&& f) {
+    return compute == VS_BF16 ? f(IC<VS_BF16>{}) : compute == VS_F16 ? f(IC<VS_F16>{}) : f(IC<VS_F32>{});
+}
+template <class F>
+int with_types(int compute, int la, int lb, F&& f) {
+    return with_compute(compute, [&](auto ct) {
+        if (la == LR && lb == LR) return f(ct, IC<LR>{}, IC<LR>{});
+        if (la == LR && lb == LS) return f(ct, IC<LR>{}, IC<LS>{});
+        if (la == LS && lb == LR) return f(ct, IC<LS>{}, IC<LR>{});
+        return f(ct, IC<LS>{}, IC<LS>{});
+    });
+}
+
 template <int CT, int LA, int LB, int BM, int BN>
-int launch(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const Plan& plan,
-           const Epi& epi, float* slabs, hipStream_t stream) {
+int launch(const GemmCall& c, const GemmPlan& plan, const Epi& epi, float* slabs) {
     typedef typename CTraits<CT>::T T;
     constexpr int BK = bk_of<CT>();
     constexpr int U = CTraits<CT>::U;
     // 16-byte vector loads need every problem of a batch to start 16-byte aligned too
-    Dense<CT, LA> a{(const T*)A, lda, M, K, ((uintptr_t)A % 16 == 0) && (lda % U == 0) && (epi.batch_a % U == 0)};
-    Dense<CT, LB> b{(const T*)B, ldb, N, K, ((uintptr_t)B % 16 == 0) && (ldb % U == 0) && (epi.batch_b % U == 0)};
+    Dense<CT, LA> a{(const T*)c.A, c.lda, c.M, c.K, ((uintptr_t)c.A % 16 == 0) && (c.lda % U == 0) && (epi.batch_a % U == 0)};
+    Dense<CT, LB> b{(const T*)c.B, c.ldb, c.N, c.K, ((uintptr_t)c.B % 16 == 0) && (c.ldb % U == 0) && (epi.batch_b % U == 0)};
     constexpr size_t smem = (TileGeom<CT, LA, BM, BK>::ELEMS + TileGeom<CT, LB, BN, BK>::ELEMS) * sizeof(T);
-    const int batch = epi.splits_per_batch > 0 ? plan.batch : 1;
-    dim3 grid((unsigned)vs_cdiv(N, BN), (unsigned)vs_cdiv(M, BM), (unsigned)(plan.splits * batch));
+    dim3 grid((unsigned)vs_cdiv(c.N, BN), (unsigned)vs_cdiv(c.M, BM), (unsigned)(plan.splits * c.batch));
     // XCD runs (Epi::xcd_runs) from 64 workgroups upwards: PMC on the WaveEq decoder layers (3328 x 1200 x 1200, 988 tiles of 64 x 64) showed
     // 77 MB fetched per launch for 11 MB of operands -- each of the eight L2s pulled the whole of A and B.
     Epi e = epi;
     e.xcd_runs = (int64_t)grid.x * grid.y * grid.z >= 64;
-    hipLaunchKernelGGL((gemm_kernel<CT, Dense<CT, LA>, Dense<CT, LB>, BM, BN, BK>), grid, dim3(256), smem, stream, a, b, M, N,
-                       K, (int)plan.k_tiles_per_split, e, slabs);
+    hipLaunchKernelGGL((gemm_kernel<CT, Dense<CT, LA>, Dense<CT, LB>, BM, BN, BK>), grid, dim3(256), smem, c.stream, a, b, c.M, c.N,
+                       c.K, (int)plan.k_tiles_per_split, e, slabs);
     VS_CHECK_LAUNCH("vs_gemm");
     return VS_OK;
 }
 
+// the register-staged tile in the shape the plan names (64x128: 16-bit only)
 template <int CT, int LA, int LB>
-int launch_glds(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const Plan& plan, const Epi& epi,
-                float* slabs, hipStream_t stream) {
-    const int batch = epi.splits_per_batch > 0 ? plan.batch : 1;
-    dim3 grid((unsigned)vs_cdiv(N, 128), (unsigned)vs_cdiv(M, 128), (unsigned)(plan.splits * batch));
-    static const int forced = getenv("VS_GEMM_GLDS_STAGES") ? atoi(getenv("VS_GEMM_GLDS_STAGES")) : 0;
-    const int stages = forced ? forced : ((int64_t)grid.x * grid.y * grid.z >= 1024 ? 2 : 1);
-    if (stages == 2)
-        hipLaunchKernelGGL((gemm_glds_kernel<LA, LB, false, 2, CT>), grid, dim3(256), 65536, stream, (const __bf16*)A, lda, (const __bf16*)B, ldb, M, N,
-                           K, (int)plan.k_tiles_per_split, epi, slabs);
-    else
-        hipLaunchKernelGGL((gemm_glds_kernel<LA, LB, false, 1, CT>), grid, dim3(256), 32768, stream, (const __bf16*)A, lda, (const __bf16*)B, ldb, M, N,
-                           K, (int)plan.k_tiles_per_split, epi, slabs);
-    VS_CHECK_LAUNCH("vs_gemm (LDS-DMA tile)");
-    return VS_OK;
+int launch_reg(const GemmCall& c, const GemmPlan& plan, const Epi& epi, float* slabs) {
+    if (plan.bm == 128 && plan.bn == 128) return launch<CT, LA, LB, 128, 128>(c, plan, epi, slabs);
+    if (plan.bm == 128 && plan.bn == 64) return launch<CT, LA, LB, 128, 64>(c, plan, epi, slabs);
+    if constexpr (CT != VS_F32)
+        if (plan.bm == 64 && plan.bn == 128) return launch<CT, LA, LB, 64, 128>(c, plan, epi, slabs);
+    return launch<CT, LA, LB, 64, 64>(c, plan, epi, slabs);
+}
+
+template <int CT, int LA, int LB>
+int launch_glds(const GemmCall& c, const GemmPlan& plan, const Epi& epi, float* slabs) {
+    if constexpr (CT == VS_F32) {
+        return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm: the LDS-DMA 128x128 tile is a 16-bit kernel");
+    } else {
+        dim3 grid((unsigned)vs_cdiv(c.N, 128), (unsigned)vs_cdiv(c.M, 128), (unsigned)(plan.splits * c.batch));
+        static const int forced = getenv("VS_GEMM_GLDS_STAGES") ? atoi(getenv("VS_GEMM_GLDS_STAGES")) : 0;
+        const int stages = forced ? forced : ((int64_t)grid.x * grid.y * grid.z >= 1024 ? 2 : 1);
+        if (stages == 2)
+            hipLaunchKernelGGL((gemm_glds_kernel<LA, LB, false, 2, CT>), grid, dim3(256), 65536, c.stream, (const __bf16*)c.A, c.lda, (const __bf16*)c.B,
+                               c.ldb, c.M, c.N, c.K, (int)plan.k_tiles_per_split, epi, slabs);
+        else
+            hipLaunchKernelGGL((gemm_glds_kernel<LA, LB, false, 1, CT>), grid, dim3(256), 32768, c.stream, (const __bf16*)c.A, c.lda, (const __bf16*)c.B,
+                               c.ldb, c.M, c.N, c.K, (int)plan.k_tiles_per_split, epi, slabs);
+        VS_CHECK_LAUNCH("vs_gemm (LDS-DMA tile)");
+        return VS_OK;
+    }
 }
 
 template <int CT, int LA, int LB, bool LOSS = false>
-int launch_big(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const BigPlan& bp, int batch, const Epi& epi,
-               float* slabs, hipStream_t stream) {
+int launch_big(const GemmCall& c, const GemmPlan& bp, const Epi& epi, float* slabs) {
     if constexpr (CT == VS_F32) {
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm: the 256x256 tile is a 16-bit kernel");
     } else {
@@ -80,27 +111,17 @@ int launch_big(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M
                 return vs_fail(VS_ERR_LAUNCH, "vs_gemm: cannot raise the dynamic LDS limit to 160 KiB");
             attr_set = true;
         }
-        dim3 grid((unsigned)(bp.tiles_m * bp.tiles_n), 1, (unsigned)(bp.splits * batch));
-        hipLaunchKernelGGL(kfn, grid, dim3(512), GEMM_BIG_STAGES * BIG_TILE_BYTES, stream, (const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, N, K,
-                           (int)bp.k_tiles_per_split, bp.tiles_n, epi, slabs);
+        dim3 grid((unsigned)(bp.tiles_m * bp.tiles_n), 1, (unsigned)(bp.splits * c.batch));
+        hipLaunchKernelGGL(kfn, grid, dim3(512), GEMM_BIG_STAGES * BIG_TILE_BYTES, c.stream, (const unsigned short*)c.A, c.lda, (const unsigned short*)c.B,
+                           c.ldb, c.M, c.N, c.K, (int)bp.k_tiles_per_split, bp.tiles_n, epi, slabs);
         VS_CHECK_LAUNCH("vs_gemm (256x256 tile)");
         return VS_OK;
     }
 }
 
-template <int CT>
-int launch_big_layout(int la, int lb, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const BigPlan& bp,
-                      int batch, const Epi& epi, float* slabs, hipStream_t stream) {
-    if (la == LR && lb == LR) return launch_big<CT, LR, LR>(A, lda, B, ldb, M, N, K, bp, batch, epi, slabs, stream);
-    if (la == LR && lb == LS) return launch_big<CT, LR, LS>(A, lda, B, ldb, M, N, K, bp, batch, epi, slabs, stream);
-    if (la == LS && lb == LR) return launch_big<CT, LS, LR>(A, lda, B, ldb, M, N, K, bp, batch, epi, slabs, stream);
-    return launch_big<CT, LS, LS>(A, lda, B, ldb, M, N, K, bp, batch, epi, slabs, stream);
-}
-
 // the 256 x 256 / 256 x 128 tile with two staggered wave groups (vs_gemm_p8.h)
 template <int CT, int LA, int LB, int NI, int LOSS = 0, int MI = 4>
-int launch_p8(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const P8Plan& pp, int batch, const Epi& epi, float* slabs,
-              hipStream_t stream) {
+int launch_p8(const GemmCall& c, const GemmPlan& pp, const Epi& epi, float* slabs) {
     if constexpr (CT == VS_F32) {
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm: the staggered 256-row tile is a 16-bit kernel");
     } else {
@@ -112,111 +133,37 @@ int launch_p8(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M,
                 return vs_fail(VS_ERR_LAUNCH, "vs_gemm: cannot raise the dynamic LDS limit to %d bytes", lds);
             attr_set = true;
         }
-        dim3 grid((unsigned)(pp.tiles_m * pp.tiles_n), 1, (unsigned)(pp.splits * batch));
-        hipLaunchKernelGGL(kfn, grid, dim3(512), lds, stream, (const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, N, K, (int)pp.k_tiles_per_split,
-                           pp.tiles_n, epi, slabs);
+        dim3 grid((unsigned)(pp.tiles_m * pp.tiles_n), 1, (unsigned)(pp.splits * c.batch));
+        hipLaunchKernelGGL(kfn, grid, dim3(512), lds, c.stream, (const unsigned short*)c.A, c.lda, (const unsigned short*)c.B, c.ldb, c.M, c.N, c.K,
+                           (int)pp.k_tiles_per_split, pp.tiles_n, epi, slabs);
         VS_CHECK_LAUNCH("vs_gemm (staggered 256-row tile)");
         return VS_OK;
     }
 }
 
-template <int CT>
-int launch_p8_layout(int la, int lb, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const P8Plan& pp, int batch,
-                     const Epi& epi, float* slabs, hipStream_t stream) {
-    if (pp.ni == 1 && pp.mi == 2) {
-        if (la == LR && lb == LR) return launch_p8<CT, LR, LR, 1, 0, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-        if (la == LR && lb == LS) return launch_p8<CT, LR, LS, 1, 0, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-        if (la == LS && lb == LR) return launch_p8<CT, LS, LR, 1, 0, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-        return launch_p8<CT, LS, LS, 1, 0, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-    }
-    if (pp.ni == 1) {
-        if (la == LR && lb == LR) return launch_p8<CT, LR, LR, 1>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-        if (la == LR && lb == LS) return launch_p8<CT, LR, LS, 1>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-        if (la == LS && lb == LR) return launch_p8<CT, LS, LR, 1>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-        return launch_p8<CT, LS, LS, 1>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-    }
-    if (la == LR && lb == LR) return launch_p8<CT, LR, LR, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-    if (la == LR && lb == LS) return launch_p8<CT, LR, LS, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-    if (la == LS && lb == LR) return launch_p8<CT, LS, LR, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-    return launch_p8<CT, LS, LS, 2>(A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-}
-
-inline P8Plan p8_plan_for(int compute, int64_t M, int64_t N, int64_t K, int64_t batch, const void* A, int64_t lda, int la, const void* B, int64_t ldb, int lb,
-                          int64_t stride_a, int64_t stride_b) {
-    P8Plan pp = make_p8_plan(compute, M, N, K, batch, lb);
-    if (pp.use && !(glds_operand_ok(A, lda, la, M, K, stride_a) && glds_operand_ok(B, ldb, lb, N, K, stride_b))) pp.use = false;
-    if (pp.use && (lda >= (1ll << 22) || ldb >= (1ll << 22))) pp.use = false;       // 32-bit lane offsets inside a tile
-    return pp;
-}
-
 template <int CT, int LA, int LB>
-int launch_mid(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const MidPlan& mp, int batch, const Epi& epi,
-               float* slabs, hipStream_t stream) {
-    const int rc = mid_launch<CT, LA, LB>(A, lda, B, ldb, M, N, K, mp.splits, mp.k_tiles_per_split, mp.stages, batch, epi, slabs, stream);
+int launch_mid(const GemmCall& c, const GemmPlan& mp, const Epi& epi, float* slabs) {
+    const int rc = mid_launch<CT, LA, LB>(c.A, c.lda, c.B, c.ldb, c.M, c.N, c.K, mp.splits, mp.k_tiles_per_split, mp.stages, c.batch, epi, slabs, c.stream);
     if (rc != VS_OK) return rc;
     VS_CHECK_LAUNCH("vs_gemm (128x128 ring tile)");
     return VS_OK;
 }
 
-template <int CT>
-int launch_mid_layout(int la, int lb, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const MidPlan& mp,
-                      int batch, const Epi& epi, float* slabs, hipStream_t stream) {
-    if (la == LR && lb == LR) return launch_mid<CT, LR, LR>(A, lda, B, ldb, M, N, K, mp, batch, epi, slabs, stream);
-    if (la == LR && lb == LS) return launch_mid<CT, LR, LS>(A, lda, B, ldb, M, N, K, mp, batch, epi, slabs, stream);
-    if (la == LS && lb == LR) return launch_mid<CT, LS, LR>(A, lda, B, ldb, M, N, K, mp, batch, epi, slabs, stream);
-    return launch_mid<CT, LS, LS>(A, lda, B, ldb, M, N, K, mp, batch, epi, slabs, stream);
-}
-
-inline MidPlan mid_plan_for(int compute, int64_t M, int64_t N, int64_t K, int64_t batch, const void* A, int64_t lda, int la, const void* B,
-                            int64_t ldb, int lb, int64_t stride_a, int64_t stride_b) {
-    MidPlan mp = make_mid_plan(compute, M, N, K, batch);
-    if (mp.use && !(glds_operand_ok(A, lda, la, M, K, stride_a) && glds_operand_ok(B, ldb, lb, N, K, stride_b))) mp.use = false;
-    if (mp.use && (lda >= (1ll << 23) || ldb >= (1ll << 23))) mp.use = false;       // 32-bit lane offsets inside a tile
-    return mp;
-}
-
-// the 256x256 tile is taken when its plan says so and both operands fit the LDS-DMA loader (alignment, multiples of 8)
-inline BigPlan big_plan_for(int compute, int64_t M, int64_t N, int64_t K, int64_t batch, const void* A, int64_t lda, int la, const void* B,
-                            int64_t ldb, int lb, int64_t stride_a, int64_t stride_b) {
-    BigPlan bp = make_big_plan(compute, M, N, K, batch);
-    if (bp.use && !(glds_operand_ok(A, lda, la, M, K, stride_a) && glds_operand_ok(B, ldb, lb, N, K, stride_b))) bp.use = false;
-    if (bp.use && (lda >= (1ll << 22) || ldb >= (1ll << 22))) bp.use = false;       // 32-bit lane offsets inside a tile
-    return bp;
-}
-
-template <int CT, int LA, int LB>
-int launch_tile(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const Plan& plan,
-                const Epi& epi, float* slabs, hipStream_t stream) {
-    if constexpr (CT != VS_F32 && LA == LR && LB == LR) {
-        // LDS-DMA staged tile (vs_gemm_glds.h) wherever the plan picks 128x128 (>= 1024 tiles).  Measured on MI355X
-        // (tools/gemm_bench.py): 732 vs 588 TF/s at 4096^3 with two LDS buffers; with S operands it is not faster than the
-        // register-staged tile yet (598 vs 593), so only R x R takes this path.  At 512-1023 tiles (the decoder's
-        // 3328x4096x1200: 832 tiles on 768 / 512 resident slots) 128x64 register staging stays ahead: 75 vs 89-98 us.
-        // VS_GEMM_GLDS=0 disables, =2 forces all layouts.
-        static const int glds_mode = getenv("VS_GEMM_GLDS") ? atoi(getenv("VS_GEMM_GLDS")) : 1;
-        if (plan.bm == 128 && plan.bn == 128 && glds_mode && glds_operand_ok(A, lda, LA, M, K, epi.batch_a) &&
-            glds_operand_ok(B, ldb, LB, N, K, epi.batch_b))
-            return launch_glds<CT, LA, LB>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    } else if constexpr (CT != VS_F32) {
-        static const int glds_mode = getenv("VS_GEMM_GLDS") ? atoi(getenv("VS_GEMM_GLDS")) : 1;
-        if (plan.bm == 128 && plan.bn == 128 && glds_mode == 2 && glds_operand_ok(A, lda, LA, M, K, epi.batch_a) &&
-            glds_operand_ok(B, ldb, LB, N, K, epi.batch_b))
-            return launch_glds<CT, LA, LB>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    }
-    if (plan.bm == 128 && plan.bn == 128) return launch<CT, LA, LB, 128, 128>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    if (plan.bm == 128 && plan.bn == 64) return launch<CT, LA, LB, 128, 64>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    if constexpr (CT != VS_F32)
-        if (plan.bm == 64 && plan.bn == 128) return launch<CT, LA, LB, 64, 128>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    return launch<CT, LA, LB, 64, 64>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-}
-
-template <int CT>
-int launch_layout(int la, int lb, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
-                  const Plan& plan, const Epi& epi, float* slabs, hipStream_t stream) {
-    if (la == LR && lb == LR) return launch_tile<CT, LR, LR>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    if (la == LR && lb == LS) return launch_tile<CT, LR, LS>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    if (la == LS && lb == LR) return launch_tile<CT, LS, LR>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    return launch_tile<CT, LS, LS>(A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
+// the kernel the plan names, for the call's compute type and layouts
+int launch_plan(int compute, const GemmCall& c, const GemmPlan& p, const Epi& epi, float* slabs) {
+    return with_types(compute, c.la, c.lb, [&](auto ct, auto la, auto lb) -> int {
+        constexpr int CT = decltype(ct)::value, LA = decltype(la)::value, LB = decltype(lb)::value;
+        switch (p.kind) {
+            case GEMM_P8:
+                if (p.ni == 1 && p.mi == 2) return launch_p8<CT, LA, LB, 1, 0, 2>(c, p, epi, slabs);
+                if (p.ni == 1) return launch_p8<CT, LA, LB, 1>(c, p, epi, slabs);
+                return launch_p8<CT, LA, LB, 2>(c, p, epi, slabs);
+            case GEMM_BIG: return launch_big<CT, LA, LB>(c, p, epi, slabs);
+            case GEMM_MID: return launch_mid<CT, LA, LB>(c, p, epi, slabs);
+            case GEMM_GLDS: return launch_glds<CT, LA, LB>(c, p, epi, slabs);
+            default: return launch_reg<CT, LA, LB>(c, p, epi, slabs);
+        }
+    });
 }
 
 // ---- split-K arrival counters -------------------------------------------------------------------------------------------------
@@ -248,36 +195,44 @@ unsigned* sk_take(int64_t words, int64_t tile_slab_bytes) {
     return p;
 }
 
-}  // namespace
-
-extern "C" size_t vs_gemm_batched_workspace_bytes(int batch, int64_t M, int64_t N, int64_t K) {
-    if (batch <= 0 || M <= 0 || N <= 0 || K <= 0) return 0;
-    size_t worst = 0;
-    for (int c = 0; c < 2; ++c) {                        // fp32 and the 16-bit types (bf16 and fp16 plan alike)
-        Plan p = make_plan(c, M, N, K, batch);
-        if (p.splits > 1) {
-            size_t b = (size_t)batch * p.splits * (size_t)M * (size_t)N * sizeof(float);
-            if (b > worst) worst = b;
-        }
-        const BigPlan bp = make_big_plan(c, M, N, K, batch);
-        if (bp.use && bp.splits > 1) {
-            size_t b = (size_t)batch * bp.splits * (size_t)M * (size_t)N * sizeof(float);
-            if (b > worst) worst = b;
-        }
-        const MidPlan mp = make_mid_plan(c, M, N, K, batch);
-        if (mp.use && mp.splits > 1) {
-            size_t b = (size_t)batch * mp.splits * (size_t)M * (size_t)N * sizeof(float);
-            if (b > worst) worst = b;
-        }
-        for (int lb = 0; lb < 2; ++lb) {
-            const P8Plan pp = make_p8_plan(c, M, N, K, batch, lb);
-            if (pp.use && pp.splits > 1) {
-                size_t b = (size_t)batch * pp.splits * (size_t)M * (size_t)N * sizeof(float);
-                if (b > worst) worst = b;
-            }
+// One planned contraction: slab check, arrival counters, the launch, the reduce launch.  `who` prefixes the error text.
+int run_gemm(const char* who, int compute, const GemmCall& c, const GemmPlan& plan, Epi epi, void* workspace, size_t workspace_bytes) {
+    float* slabs = nullptr;
+    if (plan.splits > 1) {
+        const size_t need = gemm_slab_bytes(plan, c.M, c.N, c.batch);
+        if (!workspace || workspace_bytes < need)
+            return vs_fail(VS_ERR_WORKSPACE, "%s: split-K needs %zu workspace bytes, got %zu", who, need, workspace_bytes);
+        slabs = (float*)workspace;
+        if (gemm_splitk_in_launch(plan)) {
+            epi.sk_counters = sk_take(gemm_splitk_counters(plan, c.M, c.N, c.batch), gemm_splitk_tile_bytes(plan));
+            epi.sk_splits = plan.splits;
+            epi.sk_bytes = (int64_t)need;
         }
     }
-    return worst;
+    const int rc = launch_plan(compute, c, plan, epi, slabs);
+    if (rc != VS_OK) return rc;
+    if (slabs && !epi.sk_counters) return launch_splitk_reduce(slabs, plan.splits, c.M, c.N, epi, c.batch, c.stream);
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t vs_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) { return gemm_workspace_bytes(M, N, K, 1); }
+extern "C" size_t vs_gemm_batched_workspace_bytes(int batch, int64_t M, int64_t N, int64_t K) { return gemm_workspace_bytes(M, N, K, batch); }
+
+// Host-only view of the decision vs_gemm / vs_gemm_batched take for these arguments: plan_gemm, printed.  No GPU call; the operand
+// addresses are looked at for alignment only.
+extern "C" int vs_gemm_plan(int compute, int batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int64_t stride_a, int layout_a,
+                            const void* B, int64_t ldb, int64_t stride_b, int layout_b, int64_t* out) {
+    VS_CHECK_ARG(vs_dtype_ok(compute), "vs_gemm_plan: compute type %d", compute);
+    VS_CHECK_ARG(batch >= 1 && batch <= 1024 && M > 0 && N > 0 && K > 0, "vs_gemm_plan: bad sizes");
+    VS_CHECK_ARG((layout_a == LR || layout_a == LS) && (layout_b == LR || layout_b == LS), "vs_gemm_plan: bad layout");
+    VS_CHECK_ARG(out, "vs_gemm_plan: null pointer");
+    const GemmPlan p = plan_gemm(compute, M, N, K, batch, A, lda, layout_a, stride_a, B, ldb, layout_b, stride_b);
+    const int64_t row[12] = {p.kind, p.bm, p.bn, p.splits, p.k_tiles_per_split, p.tiles_m, p.tiles_n, p.stages, p.ni, p.mi,
+                             gemm_splitk_in_launch(p) && gemm_splitk_counters(p, M, N, batch) > 0, (int64_t)gemm_slab_bytes(p, M, N, batch)};
+    memcpy(out, row, sizeof(row));
+    return VS_OK;
 }
 
 // `batch` independent problems of one shape in one launch (the weight gradients of the integrator's blocks: the same three
@@ -286,60 +241,19 @@ extern "C" int vs_gemm_batched(int compute, int batch, int64_t M, int64_t N, int
                                int layout_a, const void* B, int64_t ldb, int64_t stride_b, int layout_b, void* C, int64_t ldc,
                                int64_t stride_c, int c_dtype, float alpha, int accumulate, void* workspace, size_t workspace_bytes,
                                void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     VS_CHECK_ARG(vs_dtype_ok(compute), "vs_gemm_batched: compute type %d", compute);
     VS_CHECK_ARG(batch >= 1 && batch <= 1024 && M > 0 && N > 0 && K > 0, "vs_gemm_batched: bad sizes");
     VS_CHECK_ARG(A && B && C, "vs_gemm_batched: null operand");
     VS_CHECK_ARG((layout_a == LR || layout_a == LS) && (layout_b == LR || layout_b == LS), "vs_gemm_batched: bad layout");
     VS_CHECK_ARG(vs_dtype_ok(c_dtype), "vs_gemm_batched: bad c_dtype");
     VS_CHECK_ARG(lda >= (layout_a == LR ? K : M) && ldb >= (layout_b == LR ? K : N) && ldc >= N, "vs_gemm_batched: leading dimension too small");
-    Plan plan = make_plan(compute, M, N, K, batch);
-    plan.batch = batch;
-    const P8Plan pp = p8_plan_for(compute, M, N, K, batch, A, lda, layout_a, B, ldb, layout_b, stride_a, stride_b);
-    BigPlan bp = big_plan_for(compute, M, N, K, batch, A, lda, layout_a, B, ldb, layout_b, stride_a, stride_b);
-    if (pp.use) bp.use = false;
-    MidPlan mp{false, 1, 0, 0, 0, 5};
-    if (!bp.use && !pp.use) mp = mid_plan_for(compute, M, N, K, batch, A, lda, layout_a, B, ldb, layout_b, stride_a, stride_b);
-    if (pp.use) { plan.splits = pp.splits; plan.k_tiles_per_split = pp.k_tiles_per_split; }
-    if (bp.use) { plan.splits = bp.splits; plan.k_tiles_per_split = bp.k_tiles_per_split; }
-    if (mp.use) { plan.splits = mp.splits; plan.k_tiles_per_split = mp.k_tiles_per_split; }
-    Epi epi{C, ldc, c_dtype, alpha, nullptr, VS_ACT_NONE, nullptr, 0, 0, 0, accumulate, 0, 0, 0, 0, 0, 0, 0, 0, 0, plan.splits, stride_a, stride_b, stride_c};
-    float* slabs = nullptr;
-    if (plan.splits > 1) {
-        const size_t need = (size_t)batch * plan.splits * (size_t)M * (size_t)N * sizeof(float);
-        if (!workspace || workspace_bytes < need)
-            return vs_fail(VS_ERR_WORKSPACE, "vs_gemm_batched: split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
-        slabs = (float*)workspace;
-        // one counter per (problem, tile) of the kernel that runs: 128-wide tiles on the ring kernel, plan.bm x plan.bn otherwise
-        if (!bp.use && !pp.use && (mp.use || !(plan.bm == 128 && plan.bn == 128))) {      // (the 128x128 LDS-DMA tile never splits in practice: no fix-up there)
-            if (need < (1ull << 31)) epi.sk_counters = sk_take(batch * (mp.use ? (int64_t)mp.tiles_m * mp.tiles_n : vs_cdiv(M, plan.bm) * vs_cdiv(N, plan.bn)),
-                                                             (int64_t)plan.splits * (mp.use ? 128 * 128 : plan.bm * plan.bn) * 4);
-            epi.sk_splits = plan.splits;
-            epi.sk_bytes = (int64_t)need;
-        }
-    }
-    int rc;
-    if (pp.use)
-        rc = compute == VS_BF16 ? launch_p8_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream)
-                                : launch_p8_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, pp, batch, epi, slabs, stream);
-    else if (bp.use)
-        rc = compute == VS_BF16 ? launch_big_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, bp, batch, epi, slabs, stream)
-                                : launch_big_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, bp, batch, epi, slabs, stream);
-    else if (mp.use)
-        rc = compute == VS_BF16 ? launch_mid_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, mp, batch, epi, slabs, stream)
-                                : launch_mid_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, mp, batch, epi, slabs, stream);
-    else
-        rc = compute == VS_BF16  ? launch_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, plan, epi, slabs, stream)
-             : compute == VS_F16 ? launch_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, plan, epi, slabs, stream)
-                                 : launch_layout<VS_F32>(layout_a, layout_b, A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    if (rc != VS_OK) return rc;
-    if (slabs && !epi.sk_counters) {
-        int64_t blocks = vs_cdiv(M * N, 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, stream, slabs, plan.splits, M, N, epi);
-        VS_CHECK_LAUNCH("vs_gemm_batched split-K reduce");
-    }
-    return VS_OK;
+    const GemmPlan plan = plan_gemm(compute, M, N, K, batch, A, lda, layout_a, stride_a, B, ldb, layout_b, stride_b);
+    Epi epi = plain_epi(C, ldc, c_dtype, alpha);
+    epi.accumulate = accumulate;
+    epi.splits_per_batch = plan.splits;            // > 0 marks the batched form for the kernels, even for a batch of 1
+    epi.batch_a = stride_a; epi.batch_b = stride_b; epi.batch_c = stride_c;
+    const GemmCall call{A, lda, layout_a, B, ldb, layout_b, M, N, K, batch, (hipStream_t)stream_};
+    return run_gemm("vs_gemm_batched", compute, call, plan, epi, workspace, workspace_bytes);
 }
 
 // Weight gradient + optimizer in one launch: G = A * B^T (as vs_gemm) is the gradient of the fp32 parameter `param` [M, N]; the
@@ -350,23 +264,22 @@ extern "C" int vs_gemm_batched(int compute, int batch, int64_t M, int64_t N, int
 extern "C" int vs_gemm_adam(int compute, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int layout_a, const void* B, int64_t ldb,
                             int layout_b, float alpha, float* param, float* exp_avg, float* exp_avg_sq, void* shadow, int shadow_dtype,
                             const int32_t* step, int32_t skipped, double lr, double beta1, double beta2, double eps, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     VS_CHECK_ARG(compute == VS_BF16 || compute == VS_F16, "vs_gemm_adam: 16-bit compute types only (%d)", compute);
     VS_CHECK_ARG(M > 0 && N > 0 && K > 0, "vs_gemm_adam: M, N, K must be positive");
     VS_CHECK_ARG(A && B && param && exp_avg && exp_avg_sq && step, "vs_gemm_adam: null pointer");
     VS_CHECK_ARG((layout_a == LR || layout_a == LS) && (layout_b == LR || layout_b == LS), "vs_gemm_adam: bad layout");
     VS_CHECK_ARG(lda >= (layout_a == LR ? K : M) && ldb >= (layout_b == LR ? K : N), "vs_gemm_adam: leading dimension too small");
     VS_CHECK_ARG(!shadow || shadow_dtype == VS_BF16 || shadow_dtype == VS_F16, "vs_gemm_adam: bad shadow dtype");
-    if (!(glds_operand_ok(A, lda, layout_a, M, K, 0) && glds_operand_ok(B, ldb, layout_b, N, K, 0)) || lda >= (1ll << 23) || ldb >= (1ll << 23))
+    if (!dma_operands_ok(GEMM_MID, A, lda, layout_a, 0, B, ldb, layout_b, 0, M, N, K))
         return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_adam: operands do not fit the LDS-DMA loader (16-byte alignment, multiples of 8)");
-    Epi epi{param, N, VS_F32, alpha, nullptr, VS_ACT_NONE, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    Epi epi = plain_epi(param, N, VS_F32, alpha);
     epi.adam_m = exp_avg; epi.adam_v = exp_avg_sq; epi.adam_shadow = (unsigned short*)shadow; epi.adam_shadow_dtype = shadow_dtype;
     epi.adam_step = step; epi.adam_skipped = skipped; epi.adam_guard = vs_g_exchange_guard;
     epi.adam_lr = lr; epi.adam_beta1 = beta1; epi.adam_beta2 = beta2; epi.adam_eps = (float)eps;
-    MidPlan mp{true, 1, vs_cdiv(K, BIG_BK), (int)vs_cdiv(M, 128), (int)vs_cdiv(N, 128), 5};
+    const GemmPlan mp = ring_plan_one_split(M, N, K);
     if ((int64_t)mp.tiles_m * mp.tiles_n > 0x7fffffffll) return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_adam: too many tiles");
-    return compute == VS_BF16 ? launch_mid_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, mp, 1, epi, nullptr, stream)
-                              : launch_mid_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, mp, 1, epi, nullptr, stream);
+    const GemmCall call{A, lda, layout_a, B, ldb, layout_b, M, N, K, 1, (hipStream_t)stream_};
+    return launch_plan(compute, call, mp, epi, nullptr);
 }
 
 // The decoder's last Linear layer with the frame losses in its epilogue (recorded MLP-family step): frames = act(A W^T + bias) is row
@@ -392,24 +305,25 @@ extern "C" int vs_gemm_frame_loss(int compute, int64_t M, int64_t N, int64_t K, 
     int rc = fill_loss_args(a, nullptr, full, nullptr, t_random_dev, ae_shift, first_forecast, M / G, G, T, N, s_old, s_new, n_s, t0, Bt, Ct,
                             average_tloss, lambdas);
     if (rc != VS_OK) return rc;
-    const P8Plan pp = p8_plan_for(compute, M, N, K, 1, A, lda, LR, W, ldw, LR, 0, 0);
-    const bool p8 = pp.use && pp.ni == 2 && pp.splits == 1 && (int64_t)pp.tiles_m * pp.tiles_n <= VS_LOSS_MAX_PARTIALS;
-    const BigPlan bp = big_plan_for(compute, M, N, K, 1, A, lda, LR, W, ldw, LR, 0, 0);
-    if (!p8 && (!bp.use || bp.splits != 1 || (int64_t)bp.tiles_m * bp.tiles_n > VS_LOSS_MAX_PARTIALS))
-        return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_frame_loss: the problem does not run on the 256x256 tile kernels");
-    Epi epi{nullptr, N, VS_F32, 1.f, bias, act, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // its own acceptance, not plan_gemm's chain: the staggered tile in its 256 x 256 form, else the 256x256 tile, one split each
+    const GemmPlan pp = p8_plan(compute, M, N, K, 1), bp = big_plan(compute, M, N, K, 1);
+    auto takes = [&](const GemmPlan& p) {
+        return p.use && dma_operands_ok(p.kind, A, lda, LR, 0, W, ldw, LR, 0, M, N, K) && p.splits == 1 && (int64_t)p.tiles_m * p.tiles_n <= VS_LOSS_MAX_PARTIALS;
+    };
+    const bool p8 = takes(pp) && pp.ni == 2;
+    if (!p8 && !takes(bp)) return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_frame_loss: the problem does not run on the 256x256 tile kernels");
+    Epi epi = plain_epi(nullptr, N, VS_F32, 1.f);
+    epi.bias = bias; epi.act = act;
     epi.fl_full = full; epi.fl_tdev = t_random_dev; epi.fl_ae_shift = ae_shift; epi.fl_first = first_forecast; epi.fl_G = G; epi.fl_T = T;
     epi.fl_up = grad_total; epi.fl_l_ae = a.l_ae; epi.fl_l_pred = a.l_pred; epi.fl_inv_ae = a.inv_ae; epi.fl_inv_pred = a.inv_pred;
     epi.fl_dz = dz; epi.fl_dz_dtype = dz_dtype; epi.fl_partials = out + 16;
-    if (p8 && act == VS_ACT_SIGMOID)
-        rc = compute == VS_BF16 ? launch_p8<VS_BF16, LR, LR, 2, 2>(A, lda, W, ldw, M, N, K, pp, 1, epi, nullptr, stream)
-                                : launch_p8<VS_F16, LR, LR, 2, 2>(A, lda, W, ldw, M, N, K, pp, 1, epi, nullptr, stream);
-    else if (p8)
-        rc = compute == VS_BF16 ? launch_p8<VS_BF16, LR, LR, 2, 1>(A, lda, W, ldw, M, N, K, pp, 1, epi, nullptr, stream)
-                                : launch_p8<VS_F16, LR, LR, 2, 1>(A, lda, W, ldw, M, N, K, pp, 1, epi, nullptr, stream);
-    else
-        rc = compute == VS_BF16 ? launch_big<VS_BF16, LR, LR, true>(A, lda, W, ldw, M, N, K, bp, 1, epi, nullptr, stream)
-                                : launch_big<VS_F16, LR, LR, true>(A, lda, W, ldw, M, N, K, bp, 1, epi, nullptr, stream);
+    const GemmCall call{A, lda, LR, W, ldw, LR, M, N, K, 1, stream};
+    rc = with_compute(compute, [&](auto ct) -> int {
+        constexpr int CT = decltype(ct)::value;
+        if (p8 && act == VS_ACT_SIGMOID) return launch_p8<CT, LR, LR, 2, 2>(call, pp, epi, nullptr);
+        if (p8) return launch_p8<CT, LR, LR, 2, 1>(call, pp, epi, nullptr);
+        return launch_big<CT, LR, LR, true>(call, bp, epi, nullptr);
+    });
     if (rc != VS_OK) return rc;
     LossGrads gr{grad_total, dz, dz_dtype, act, ds_old, ds_new, dt0};
     hipLaunchKernelGGL(frame_loss_finish_kernel, dim3(1), dim3(256), 0, stream, a, out, p8 ? pp.tiles_m * pp.tiles_n : bp.tiles_m * bp.tiles_n, gr);
@@ -417,41 +331,10 @@ extern "C" int vs_gemm_frame_loss(int compute, int64_t M, int64_t N, int64_t K, 
     return VS_OK;
 }
 
-extern "C" size_t vs_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    size_t worst = 0;
-    for (int c = 0; c < 2; ++c) {
-        Plan p = make_plan(c, M, N, K);
-        if (p.splits > 1) {
-            size_t b = (size_t)p.splits * (size_t)M * (size_t)N * sizeof(float);
-            if (b > worst) worst = b;
-        }
-        const BigPlan bp = make_big_plan(c, M, N, K, 1);
-        if (bp.use && bp.splits > 1) {
-            size_t b = (size_t)bp.splits * (size_t)M * (size_t)N * sizeof(float);
-            if (b > worst) worst = b;
-        }
-        const MidPlan mp = make_mid_plan(c, M, N, K, 1);
-        if (mp.use && mp.splits > 1) {
-            size_t b = (size_t)mp.splits * (size_t)M * (size_t)N * sizeof(float);
-            if (b > worst) worst = b;
-        }
-        for (int lb = 0; lb < 2; ++lb) {
-            const P8Plan pp = make_p8_plan(c, M, N, K, 1, lb);
-            if (pp.use && pp.splits > 1) {
-                size_t b = (size_t)pp.splits * (size_t)M * (size_t)N * sizeof(float);
-                if (b > worst) worst = b;
-            }
-        }
-    }
-    return worst;
-}
-
 extern "C" int vs_gemm(int compute, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int layout_a, const void* B,
                        int64_t ldb, int layout_b, void* C, int64_t ldc, int c_dtype, float alpha, const float* bias, int act,
                        const void* mask, int64_t ldmask, int mask_dtype, int mask_act, int accumulate, void* workspace,
                        size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     VS_CHECK_ARG(vs_dtype_ok(compute), "vs_gemm: compute type %d", compute);
     VS_CHECK_ARG(M > 0 && N > 0 && K > 0, "vs_gemm: M, N, K must be positive (%lld %lld %lld)", (long long)M, (long long)N, (long long)K);
     VS_CHECK_ARG(A && B && C, "vs_gemm: null operand");
@@ -460,49 +343,11 @@ extern "C" int vs_gemm(int compute, int64_t M, int64_t N, int64_t K, const void*
     VS_CHECK_ARG(lda >= (layout_a == LR ? K : M) && ldb >= (layout_b == LR ? K : N) && ldc >= N, "vs_gemm: leading dimension too small");
     VS_CHECK_ARG(!mask || ldmask >= N, "vs_gemm: ldmask too small");
     VS_CHECK_ARG(act >= VS_ACT_NONE && act <= VS_ACT_ELU, "vs_gemm: bad activation");
-    Epi epi{C, ldc, c_dtype, alpha, bias, act, mask, ldmask, mask_dtype, mask_act, accumulate, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    Plan plan = make_plan(compute, M, N, K);
-    const P8Plan pp = p8_plan_for(compute, M, N, K, 1, A, lda, layout_a, B, ldb, layout_b, 0, 0);
-    BigPlan bp = big_plan_for(compute, M, N, K, 1, A, lda, layout_a, B, ldb, layout_b, 0, 0);
-    if (pp.use) bp.use = false;
-    MidPlan mp{false, 1, 0, 0, 0, 5};
-    if (!bp.use && !pp.use) mp = mid_plan_for(compute, M, N, K, 1, A, lda, layout_a, B, ldb, layout_b, 0, 0);
-    if (pp.use) { plan.splits = pp.splits; plan.k_tiles_per_split = pp.k_tiles_per_split; }
-    if (bp.use) { plan.splits = bp.splits; plan.k_tiles_per_split = bp.k_tiles_per_split; }
-    if (mp.use) { plan.splits = mp.splits; plan.k_tiles_per_split = mp.k_tiles_per_split; }
-    float* slabs = nullptr;
-    if (plan.splits > 1) {
-        const size_t need = (size_t)plan.splits * (size_t)M * (size_t)N * sizeof(float);
-        if (!workspace || workspace_bytes < need)
-            return vs_fail(VS_ERR_WORKSPACE, "vs_gemm: split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
-        slabs = (float*)workspace;
-        if (!bp.use && !pp.use && (mp.use || !(plan.bm == 128 && plan.bn == 128))) {
-            if (need < (1ull << 31)) epi.sk_counters = sk_take(mp.use ? (int64_t)mp.tiles_m * mp.tiles_n : vs_cdiv(M, plan.bm) * vs_cdiv(N, plan.bn),
-                                                             (int64_t)plan.splits * (mp.use ? 128 * 128 : plan.bm * plan.bn) * 4);
-            epi.sk_splits = plan.splits;
-            epi.sk_bytes = (int64_t)need;
-        }
-    }
-    int rc;
-    if (pp.use)
-        rc = compute == VS_BF16 ? launch_p8_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, pp, 1, epi, slabs, stream)
-                                : launch_p8_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, pp, 1, epi, slabs, stream);
-    else if (bp.use)
-        rc = compute == VS_BF16 ? launch_big_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, bp, 1, epi, slabs, stream)
-                                : launch_big_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, bp, 1, epi, slabs, stream);
-    else if (mp.use)
-        rc = compute == VS_BF16 ? launch_mid_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, mp, 1, epi, slabs, stream)
-                                : launch_mid_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, mp, 1, epi, slabs, stream);
-    else
-        rc = compute == VS_BF16  ? launch_layout<VS_BF16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, plan, epi, slabs, stream)
-             : compute == VS_F16 ? launch_layout<VS_F16>(layout_a, layout_b, A, lda, B, ldb, M, N, K, plan, epi, slabs, stream)
-                                 : launch_layout<VS_F32>(layout_a, layout_b, A, lda, B, ldb, M, N, K, plan, epi, slabs, stream);
-    if (rc != VS_OK) return rc;
-    if (slabs && !epi.sk_counters) {
-        int64_t blocks = vs_cdiv(M * N, 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slabs, plan.splits, M, N, epi);
-        VS_CHECK_LAUNCH("vs_gemm split-K reduce");
-    }
-    return VS_OK;
+    Epi epi = plain_epi(C, ldc, c_dtype, alpha);       // splits_per_batch = 0 and no batch strides: the single-problem form
+    epi.bias = bias; epi.act = act;
+    epi.mask = mask; epi.ldmask = ldmask; epi.mask_dtype = mask_dtype; epi.mask_act = mask_act;
+    epi.accumulate = accumulate;
+    const GemmPlan plan = plan_gemm(compute, M, N, K, 1, A, lda, layout_a, 0, B, ldb, layout_b, 0);
+    const GemmCall call{A, lda, layout_a, B, ldb, layout_b, M, N, K, 1, (hipStream_t)stream_};
+    return run_gemm("vs_gemm", compute, call, plan, epi, workspace, workspace_bytes);
 }

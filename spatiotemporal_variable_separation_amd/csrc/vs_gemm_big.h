@@ -467,38 +467,4 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(const unsigned short* Ap,
     }
 }
 
-// ---- when to take it ---------------------------------------------------------------------------------------------------------
-// One workgroup per CU.  The plan asks for ONE round of 160..256 workgroups, >= 12 K tiles (of 32) (amortises prologue + epilogue:
-// ~26 us of a 63 us launch at 3328 x 4096 x 1200 are launch, ring fill and the 54 MB of fp32 output), and enough work that the
-// 256-wide tile is not mostly padding.  VS_GEMM_BIG=0 disables, =2 takes it whenever the operands allow (tests; split-K off).
-// k_tiles_per_split counts K tiles of BIG_BK.  Measured (MI355X, bf16, random operands): 3328 x 4096 x 1200 63 us (128x64 tile:
-// 76 us), 4096^3 158 us = 870 TFLOP/s (128x128 LDS-DMA tile: 184 us).  Timing-only variants of the loop: without
-// the MFMAs and fragment reads the DMA ring alone runs at 0.57 us per 32 KiB tile (57 GB/s per CU), without real DMA traffic
-// the multiply alone at 0.74 us per tile (MFMA-issue bound at the clock the chip holds under load), both together at 1.03 us.
-struct BigPlan { bool use; int splits; int64_t k_tiles_per_split; int tiles_m, tiles_n; };
-
-inline BigPlan make_big_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch) {
-    BigPlan p{false, 1, 0, (int)vs_cdiv(M, 256), (int)vs_cdiv(N, 256)};
-    const char* env = getenv("VS_GEMM_BIG");                      // read per call: tests switch it
-    const int mode = env ? atoi(env) : 1;
-    if (compute == VS_F32 || mode == 0) return p;
-    const int64_t kt = vs_cdiv(K, BIG_BK);
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * batch;
-    p.k_tiles_per_split = kt;
-    if (mode == 2) { p.use = tiles <= 65535; return p; }
-    if (M < 512 || N < 512 || kt < 12 || tiles > 256) return p;
-    // padding waste of the 256-wide tiles
-    const double fill = (double)M * (double)N / ((double)p.tiles_m * 256.0 * (double)p.tiles_n * 256.0);
-    if (fill < 0.8) return p;
-    // Split-K is NOT planned: measured on the WaveEq decoder shapes the slab round trip of 256-wide tiles (4 B written + read per
-    // output element and split) costs more than it buys -- 3328x1200x4096: 90 us split in 3 vs 78 us on the 128x64 tile,
-    // 3328x1200x1200: 53 vs 35 us -- so the tile is taken where its tiles alone fill most of the chip (>= 160 of 256 CUs).
-    int splits = 1;
-    if (tiles < 160) return p;
-    p.k_tiles_per_split = vs_cdiv(kt, splits);
-    p.splits = (int)vs_cdiv(kt, p.k_tiles_per_split);
-    p.use = true;
-    return p;
-}
-
 }  // namespace

@@ -60,6 +60,13 @@ struct Epi {
     void* fl_dz; int fl_dz_dtype; float* fl_partials;
 };
 
+// alpha * acc stored to C [M, ldc] as c_dtype and nothing else; callers set the further fields by name
+inline Epi plain_epi(void* C, int64_t ldc, int c_dtype, float alpha) {
+    Epi e{};
+    e.C = C; e.ldc = ldc; e.c_dtype = c_dtype; e.alpha = alpha;
+    return e;
+}
+
 // XCD-aware, bijective block -> tile index (blocks b and b + 8 share an XCD under round-robin dispatch: speed only)
 __device__ __forceinline__ unsigned big_tile_of(unsigned b, unsigned nwg) {
     const unsigned xcd = b & 7u, q = nwg >> 3, r = nwg & 7u;
@@ -461,57 +468,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* slabs, 
     }
 }
 
-struct Plan { int bm, bn, splits; int64_t k_tiles_per_split; int batch = 1; };
+// the reduce launch of a split-K GEMM: slabs [batch][splits][M][N] -> epilogue -> C
+inline int launch_splitk_reduce(const float* slabs, int splits, int64_t M, int64_t N, const Epi& epi, int batch, hipStream_t stream) {
+    int64_t blocks = vs_cdiv(M * N, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, stream, slabs, splits, M, N, epi);
+    VS_CHECK_LAUNCH("split-K reduce");
+    return VS_OK;
+}
 
 template <int CT> constexpr int bk_of() { return CT != VS_F32 ? 64 : 16; }
-
-Plan make_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch = 1) {
-    const int bk = compute != VS_F32 ? 64 : 16;
-    Plan p;
-    // Tile choice (measured on the config-2 shapes, tools/gemm_bench.py): the kernel keeps ~3 workgroups (12 waves) per CU
-    // busy; with fewer than ~4 tiles of 128x128 per CU most SIMDs hold a single wave that cannot overlap its LDS reads with
-    // MFMA and 128x64 wins (421 vs 312 TF/s at 3328x4096x1200); 64x64 wins when K is short (310 vs 172 TF/s at K = 256);
-    // few-tile problems go to split-K, where larger tiles mean fewer fp32 slabs.
-    const int64_t t128 = vs_cdiv(M, 128) * vs_cdiv(N, 128);
-    const int64_t t12864 = vs_cdiv(M, 128) * vs_cdiv(N, 64);
-    // 128x64 only from ~2.3 tiles per CU upwards.  Below that the step is faster with 64x64 tiles although the isolated kernel is
-    // not (WaveEq B=128, whole recorded step: 1.51 -> 1.43 ms; 3328x1200 outputs are 494 tiles of 128x64 but 988 of 64x64, and
-    // the 256x1200 encoder outputs 38 against 76): the launches overlap with the gradient branches, where more and lighter
-    // workgroups fill the CUs the neighbours leave.
-    constexpr int64_t t64_below = 600;
-    if (const char* f = getenv("VS_GEMM_TILE")) {                       // debugging aid: force a tile ("128x128", "128x64", "64x64")
-        p.bm = atoi(f); const char* x = strchr(f, 'x'); p.bn = x ? atoi(x + 1) : p.bm;
-    } else if (K <= 512 && t128 >= 256) { p.bm = 64; p.bn = 64; }      // short K: prologue/epilogue bound, many small tiles win
-    else if (t128 >= 1024) { p.bm = 128; p.bn = 128; }                 // >= 4 big tiles per CU: best LDS reuse
-    else if ((t12864 >= 160 || vs_cdiv(M, 64) * vs_cdiv(N, 64) < 256) && M > 64 && t12864 >= t64_below) { p.bm = 128; p.bn = 64; }
-    else { p.bm = 64; p.bn = 64; }
-    if (M <= 64) p.bm = 64;
-    if (N <= 64) p.bn = 64;
-    if (p.bm == 64) p.bn = 64;
-    // <= 64 output rows x very many columns (64-channel convolution layers over a whole batch of pixels): a 64x128 tile gives
-    // every wave two accumulators per A fragment (1.5 LDS fragment reads per MFMA instead of 2)
-    if (compute != VS_F32 && !getenv("VS_GEMM_TILE") && M <= 64 && M > 32 && vs_cdiv(N, 128) >= 1024 && K >= 128) { p.bm = 64; p.bn = 128; }
-    const int64_t tiles = vs_cdiv(M, p.bm) * vs_cdiv(N, p.bn) * batch;
-    const int64_t kt = vs_cdiv(K, bk);
-    int splits = 1;
-    if (tiles < 192 && kt >= 8) {
-        splits = (int)((512 + tiles - 1) / tiles);
-        const int64_t max_by_k = kt / 4;            // keep >= 4 K tiles per split
-        if (splits > max_by_k) splits = (int)max_by_k;
-        if (splits > 64) splits = 64;
-        if (splits < 1) splits = 1;
-    } else if (tiles < 1024 && kt >= 128) {
-        // long reductions over few tiles (convolution weight gradients: K = batch x pixels up to ~10^6): one workgroup per CU
-        // walking thousands of K tiles is latency bound; aim at ~1024 workgroups, >= 32 K tiles each
-        splits = (int)((1024 + tiles - 1) / tiles);
-        const int64_t max_by_k = kt / 32;
-        if (splits > max_by_k) splits = (int)max_by_k;
-        if (splits > 64) splits = 64;
-        if (splits < 1) splits = 1;
-    }
-    p.k_tiles_per_split = vs_cdiv(kt, splits);
-    p.splits = (int)vs_cdiv(kt, p.k_tiles_per_split);
-    return p;
-}
 
 }  // namespace

@@ -364,42 +364,4 @@ int mid_launch(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M
     }
 }
 
-// ---- when to take it ---------------------------------------------------------------------------------------------------------
-// k_tiles_per_split counts K tiles of BIG_BK.  VS_GEMM_MID=0 disables, =2 takes it whenever the operands allow (tests).
-struct MidPlan { bool use; int splits; int64_t k_tiles_per_split; int tiles_m, tiles_n; int stages; };
-
-inline MidPlan make_mid_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch) {
-    MidPlan p{false, 1, 0, (int)vs_cdiv(M, 128), (int)vs_cdiv(N, 128), 5};
-    const char* env = getenv("VS_GEMM_MID");                      // read per call: tests switch it
-    const int mode = env ? atoi(env) : 1;
-    if (compute == VS_F32 || mode == 0) return p;
-    const int64_t kt = vs_cdiv(K, BIG_BK);
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * batch;
-    p.k_tiles_per_split = kt;
-    if (mode == 2) { p.use = tiles <= 65535 * 4; p.stages = tiles <= 256 ? 10 : 5; return p; }
-    if (M < 128 || N < 128 || kt < 16) return p;                   // short K: prologue / epilogue bound, the small tiles win
-    const double fill = (double)M * (double)N / ((double)p.tiles_m * 128.0 * (double)p.tiles_n * 128.0);
-    if (fill < 0.75) return p;
-    // two workgroups per CU are resident: up to 512 in one round.  Few tiles and a long K: split so that ~one round is filled
-    // and every split keeps >= 12 K tiles (prologue + epilogue + the slab round trip cost ~8 tiles' worth).
-    int splits = 1;
-    if (tiles < 200 && kt >= 24) {
-        splits = (int)(448 / tiles);
-        const int64_t max_by_k = kt / 12;
-        if (splits > max_by_k) splits = (int)max_by_k;
-        if (splits > 32) splits = 32;
-        if (splits < 1) splits = 1;
-    }
-    // Taken where it wins INSIDE the WaveEq step, not only alone (same-box A/B of the replayed step): problems of 280..520
-    // workgroups -- 4096 x 1200 x 3328 (320 tiles: 54 vs 81 us alone, 70 vs 140 us under the integrator's backward kernel),
-    // 1200 x 1200 x 3328 split in 4, 256 x 1200 x 20480 split in 22.  At 260 workgroups (3328 x 1200 x K: one per CU) it is
-    // 33.8 vs 35.3 us alone but 54 vs 45 us in the step, where its 80 KiB of LDS per workgroup keeps neighbours off the CU.
-    if (tiles * splits < 280 || tiles * splits > 520) return p;
-    p.k_tiles_per_split = vs_cdiv(kt, splits);
-    p.splits = (int)vs_cdiv(kt, p.k_tiles_per_split);
-    p.stages = tiles * p.splits <= 256 ? 10 : 5;
-    p.use = true;
-    return p;
-}
-
 }  // namespace

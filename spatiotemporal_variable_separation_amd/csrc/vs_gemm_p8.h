@@ -632,68 +632,4 @@ __global__ __launch_bounds__(512, MI == 4 ? 2 : 4) void gemm_p8_kernel(const uns
     P8_STAMPS_OUT();
 }
 
-// ---- when to take it ---------------------------------------------------------------------------------------------------------
-// One workgroup per CU (128 / 96 KiB of LDS).  VS_GEMM_P8: 0 = never, 1 = by plan (default), 2 = whenever the operands allow (tests).
-struct P8Plan { bool use; int ni; int splits; int64_t k_tiles_per_split; int tiles_m, tiles_n; int mi = 4; };
-
-inline P8Plan make_p8_plan(int compute, int64_t M, int64_t N, int64_t K, int64_t batch, int lb) {
-    P8Plan p{false, 2, 1, vs_cdiv(K, P8_BK), (int)vs_cdiv(M, 256), (int)vs_cdiv(N, 256)};
-    const char* env = getenv("VS_GEMM_P8");                       // read per call: tests switch it
-    const int mode = env ? atoi(env) : 1;
-    if (compute == VS_F32 || mode == 0) return p;
-    const char* env_ni = getenv("VS_GEMM_P8_NI");
-    const int force_ni = env_ni ? atoi(env_ni) : 0;
-    auto fill_of = [&](int bn) { return (double)M * (double)N / ((double)vs_cdiv(M, 256) * 256.0 * (double)vs_cdiv(N, bn) * (double)bn); };
-    const char* env_mi = getenv("VS_GEMM_P8_MI");
-    const int force_mi = env_mi ? atoi(env_mi) : 0;
-    if (mode == 2) {
-        p.ni = force_ni == 1 ? 1 : 2;
-        if (force_mi == 2 && p.ni == 1) { p.mi = 2; p.tiles_m = (int)vs_cdiv(M, 128); }
-        p.tiles_n = (int)vs_cdiv(N, 128 * p.ni);
-        p.use = (int64_t)p.tiles_m * p.tiles_n * batch <= 65535;
-        return p;
-    }
-    // One tile row, long K (the encoders' first layer, 256 x 1200 x 20480: the weight matrix is streamed once, HBM-bound): 256 x 128 tiles, K split
-    // over ~one round of CUs into fp32 slabs (reduced by splitk_reduce_kernel).  Measured against the 128 x 128 ring tile (20 tiles x 22 splits):
-    // alone, cold operands 43.5 -> 38.1 us; replayed WaveEq step, two interleaved pairs 1.2414 / 1.2337 -> 1.2114 / 1.2079 ms.
-    {
-        const int64_t kt = p.k_tiles_per_split, tn = vs_cdiv(N, 128);
-        if (M > 128 && M <= 256 && N >= 512 && kt >= 64 && tn * batch <= 64 && (double)N / (tn * 128.0) >= 0.85) {
-            int64_t splits = 250 / (tn * batch);
-            if (splits > kt / 8) splits = kt / 8;
-            if (splits >= 2) {
-                p.ni = 1;
-                p.tiles_n = (int)tn;
-                p.k_tiles_per_split = vs_cdiv(kt, splits);
-                p.splits = (int)vs_cdiv(kt, p.k_tiles_per_split);
-                p.use = true;
-                return p;
-            }
-        }
-    }
-    if (M < 512 || N < 512 || p.k_tiles_per_split < 6) return p;
-    const int64_t t256 = (int64_t)p.tiles_m * p.tiles_n * batch;
-    if (t256 >= 160 && fill_of(256) >= 0.8) { p.use = true; return p; }
-    // 256 x 128 where the 256-wide tiles leave most CUs idle (decoder layers of the WaveEq model, 3328 x 1200: 65 -> 130 tiles; measured in the
-    // replayed WaveEq step against the 64 x 64 tile, two interleaved pairs: 1.2309 / 1.2380 vs 1.2424 / 1.2459 ms).  VS_GEMM_P8_NI=2: never.
-    // 128 x 128 (MI = 2, two workgroups per CU) where that fills the chip once: 3328 x 1200 -> 260 workgroups on 512 slots.  VS_GEMM_P8_MI=4: never.
-    const int64_t t128sq = (int64_t)vs_cdiv(M, 128) * vs_cdiv(N, 128) * batch;
-    const double fill128sq = (double)M * (double)N / ((double)vs_cdiv(M, 128) * 128.0 * (double)vs_cdiv(N, 128) * 128.0);
-    if (force_ni != 2 && force_mi != 4 && force_mi == 2 && t128sq >= 200 && t128sq <= 512 && fill128sq >= 0.85 && p.k_tiles_per_split >= 8) {
-        p.ni = 1;
-        p.mi = 2;
-        p.tiles_m = (int)vs_cdiv(M, 128);
-        p.tiles_n = (int)vs_cdiv(N, 128);
-        p.use = true;
-        return p;
-    }
-    const int64_t t128 = (int64_t)p.tiles_m * vs_cdiv(N, 128) * batch;
-    if (force_ni != 2 && t128 >= 96 && t128 <= 256 && fill_of(128) >= 0.85 && p.k_tiles_per_split >= 8) {
-        p.ni = 1;
-        p.tiles_n = (int)vs_cdiv(N, 128);
-        p.use = true;
-    }
-    return p;
-}
-
 }  // namespace

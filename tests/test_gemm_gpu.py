@@ -259,7 +259,7 @@ def test_colsum_multi_is_bitwise_repeatable():
 
 @pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('dims', [(3, 512, 32, 3072, 1, 1), (3, 512, 512, 3072, 1, 1), (2, 32, 512, 96, 1, 1), (4, 100, 72, 264, 0, 0),
-                                  (5, 64, 40, 128, 0, 1)])
+                                  (5, 64, 40, 128, 0, 1), (1, 96, 72, 1024, 0, 0)])
 def test_gemm_batched_equals_loop(dt, dims):
     """vs_gemm_batched == a loop of vs_gemm over the problems (same kernel, same split-K plan per problem class)."""
     from spatiotemporal_variable_separation_amd import ops
@@ -268,6 +268,10 @@ def test_gemm_batched_equals_loop(dt, dims):
     a = (det_uniform((batch, M, K) if la == 0 else (batch, K, M), 41) - 0.5).to(dt).cuda()
     b = (det_uniform((batch, N, K) if lb == 0 else (batch, K, N), 42) - 0.5).to(dt).cuda()
     out = ops.gemm_batched(a, la, b, lb, M, N, K)
+    if batch == 1:
+        # a batch of one through either entry runs the same plan and adds the split-K slabs in the same order (16-bit: 4 tiles, 16 K tiles,
+        # the register tile splits K in 4)
+        assert torch.equal(out[0], ops.gemm(a[0], la, b[0], lb, M, N, K))
     for i in range(batch):
         ai = a[i].float() if la == 0 else a[i].float().t()
         bi = b[i].float() if lb == 0 else b[i].float().t()
