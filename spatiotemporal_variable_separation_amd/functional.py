@@ -17,6 +17,10 @@ import torch
 
 from . import ops
 from ._lib import LAYOUT_R as R, LAYOUT_S as S, VarsepHipError, require_cuda
+# the derived copies of the parameters (operand copies, weight pre-packs, eval-mode folds) live in weights.py; they are used as functional.<name>
+from .weights import (adopt_shadow, folded_conv_bn, invalidate_shadows, note_bn_update, note_replay, packed_conv_weight, packed_img_weight,
+                      packed_k3_weight, packed_k4s2_weight, packed_tap_weight, packed_weight, prepack_conv3_weights, prepack_weights,
+                      refresh_shadows, shadow, shadow_buffer_for_update, shadows_written)
 
 _STATE = {'precision': 'fp32'}
 
@@ -153,7 +157,7 @@ def count_bn_calls(bn, calls):
     """`num_batches_tracked += calls` of a training-mode BatchNorm (one per reference call).  While gradients are folded (the
     training loop owns the step and calls `flush_bn_call_counts()` at its end) the increments are collected and applied by ONE
     multi-tensor launch per step instead of one launch per BatchNorm call (SST: ~300 per step)."""
-    _EPOCH['bn'] += 1                    # the call rewrites running_mean / running_var through raw pointers: eval-mode folds are outdated
+    note_bn_update()                     # the call rewrites running_mean / running_var through raw pointers: eval-mode folds are outdated
     # a recording must contain the increment: either right here, or -- when the recorder has promised to call
     # flush_bn_call_counts() inside the capture (train.GraphedStep) -- in that one multi-tensor launch
     if not _STATE.get('fold_grads') or (torch.cuda.is_current_stream_capturing() and not _STATE.get('bn_counts_flushed_in_capture')):
@@ -455,20 +459,34 @@ def release_deferred(after=None, late_after=None):
 # (the add would read a weight gradient its stream has not finished).  With destinations registered, the Linear chains write
 # their weight gradients (GEMM output) and bias gradients (column sums into the zeroed bucket) straight into those views and
 # return nothing for them.
-_GRAD_OUT = {}
+class _ParamRegistry(dict):
+    """id(parameter) -> (weak reference to the parameter, what is registered for it).  An id() outlives its tensor, so a lookup answers only
+    for the very tensor that was registered.  `accepts(parameter, value)` is asserted of every registered pair."""
+
+    def __init__(self, accepts=None):
+        self.accepts = accepts
+
+    def set(self, mapping):
+        self.clear()
+        for prm, value in (mapping or {}).items():
+            assert self.accepts is None or self.accepts(prm, value)
+            self[id(prm)] = (weakref.ref(prm), value)
+
+    def lookup(self, prm):
+        ent = self.get(id(prm)) if self else None
+        return ent[1] if ent is not None and ent[0]() is prm else None
+
+
+_GRAD_OUT = _ParamRegistry(lambda prm, view: view.shape == prm.shape and view.dtype in (torch.float32, torch.bfloat16) and view.is_contiguous())
 
 
 def set_grad_outputs(mapping):
     """mapping: {parameter: fp32 tensor of its shape that must receive its gradient} or None to clear."""
-    _GRAD_OUT.clear()
-    if mapping:
-        for prm, view in mapping.items():
-            assert view.shape == prm.shape and view.dtype in (torch.float32, torch.bfloat16) and view.is_contiguous()
-            _GRAD_OUT[id(prm)] = view
+    _GRAD_OUT.set(mapping)
 
 
 def grad_output(prm):
-    return _GRAD_OUT.get(id(prm)) if _GRAD_OUT else None
+    return _GRAD_OUT.lookup(prm)
 
 
 # Convolution families under a gradient reducer.  A convolution / BatchNorm parameter receives several contributions per step (the decoder
@@ -477,23 +495,16 @@ def grad_output(prm):
 # to the parameter's bucket view (weight gradients in the epilogue of their kernel, the small vectors by one multi-tensor add per
 # block, the batched weight gradients of repeatedly applied convolutions by the end-of-backward flush) and autograd is handed nothing
 # for such a parameter: no AccumulateGrad launch, no per-call adds, and the step under a reducer runs the same kernels as without one.
-_CONV_GRAD_OUT = {}
+_CONV_GRAD_OUT = _ParamRegistry(lambda prm, view: view.shape == prm.shape and view.dtype == torch.float32 and view.is_contiguous())
 
 
 def set_conv_grad_outputs(mapping):
     """mapping: {conv / BatchNorm parameter: zero-initialised fp32 tensor of its shape that accumulates its gradient} or None to clear."""
-    _CONV_GRAD_OUT.clear()
-    if mapping:
-        for prm, view in mapping.items():
-            assert view.shape == prm.shape and view.dtype == torch.float32 and view.is_contiguous()
-            _CONV_GRAD_OUT[id(prm)] = (prm, view)
+    _CONV_GRAD_OUT.set(mapping)
 
 
 def conv_grad_output(prm):
-    if not _CONV_GRAD_OUT or prm is None:
-        return None
-    ent = _CONV_GRAD_OUT.get(id(prm))
-    return ent[1] if ent is not None and ent[0] is prm else None
+    return _CONV_GRAD_OUT.lookup(prm)
 
 
 def conv_parameters(net):
@@ -509,39 +520,31 @@ def conv_parameters(net):
 # A gradient destination may be a bf16 tensor (the reducer's wire image): the weight-gradient GEMM rounds once in its epilogue,
 # the all-reduce averages that image in place and the optimizer reads it (optim.Adam consults lowp_gradient), so the fp32
 # gradient of such a weight never exists and neither do the casts to and from the wire format.
-_LOWP_GRAD = {}
+_LOWP_GRAD = _ParamRegistry(lambda prm, view: view.shape == prm.shape and view.dtype == torch.bfloat16 and view.is_contiguous())
 
 
 def set_lowp_gradients(mapping):
-    _LOWP_GRAD.clear()
-    if mapping:
-        for prm, view in mapping.items():
-            assert view.shape == prm.shape and view.dtype == torch.bfloat16 and view.is_contiguous()
-            _LOWP_GRAD[id(prm)] = view
+    _LOWP_GRAD.set(mapping)
 
 
 def lowp_gradient(prm):
-    return _LOWP_GRAD.get(id(prm)) if _LOWP_GRAD else None
+    return _LOWP_GRAD.lookup(prm)
 
 
 # ---- optimizer fused into the weight gradient -----------------------------------------------------------------------------------
 # optim.Adam.fuse_into_wgrad(params) registers 2-D Linear weights whose weight-gradient GEMM applies the Adam update in its epilogue
 # (ops.gemm_adam): the gradient of such a weight is never stored and autograd gets nothing for it.  Valid where the chain's
 # backward produces THE gradient of the step (one contribution, no all-reduce, no loss scaling) -- the recorded single-GPU MLP step.
-_FUSED_OPT = {}
+_FUSED_OPT = _ParamRegistry()
 
 
 def set_fused_optimizer(mapping):
     """mapping: {parameter: optimizer with fused_update(parameter, a, la, b, lb, M, N, K)} or None to clear."""
-    _FUSED_OPT.clear()
-    if mapping:
-        for prm, opt in mapping.items():
-            _FUSED_OPT[id(prm)] = (prm, opt)
+    _FUSED_OPT.set(mapping)
 
 
 def fused_optimizer(prm):
-    ent = _FUSED_OPT.get(id(prm)) if _FUSED_OPT else None
-    return ent[1] if ent is not None and ent[0] is prm else None
+    return _FUSED_OPT.lookup(prm)
 
 
 def side_streams_in_use():
@@ -585,95 +588,6 @@ def join_side_streams(partial=False):
     if _SIDE['rollout'] is not None:
         cur.wait_stream(_SIDE['rollout'])
     return pending
-
-
-# ------------------------------------------------------------------------------------------------ weight shadows
-# Every derived copy of a parameter (16-bit operand copy, MFMA pre-pack, eval-mode BatchNorm fold) is valid for one (version counter,
-# replay epoch) pair.  The version counter moves when torch or optim.Adam updates the parameter from Python; it does NOT move when a
-# recorded step is replayed (`increment_version` ran at capture time only) nor when a kernel writes BatchNorm running statistics through
-# raw pointers.  `note_replay()` (train.GraphedStep.step) and `count_bn_calls` (every training-mode BatchNorm call) advance the epochs
-# instead, so an eager use after replays -- evaluation between recorded training steps, a re-recording after a learning-rate change --
-# re-derives what the replays have outdated (into the same storage: recorded graphs keep addressing it).
-_EPOCH = {'replay': 0, 'bn': 0}
-_shadow = {}
-
-
-def _ver(p):
-    return (p._version, _EPOCH['replay'])
-
-
-def _wref(cache, key, p):
-    """Weak reference to the tensor a cache entry belongs to; the entry (and the device memory of its copy) goes when the tensor does."""
-    return weakref.ref(p, lambda _r: cache.pop(key, None))
-
-
-def note_replay():
-    """A recorded step has been replayed: parameters and BatchNorm statistics changed without moving any version counter."""
-    _EPOCH['replay'] += 1
-    _EPOCH['bn'] += 1
-
-
-def shadow(p, dtype):
-    """Parameter as a GEMM operand: itself in fp32 mode, a cached bf16 copy (refreshed on version change) otherwise."""
-    if dtype == torch.float32:
-        return p.detach()
-    key = id(p)
-    ent = _shadow.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[1].data_ptr() == 0 or ent[2]() is not p or ent[1].dtype != dtype:
-        buf = ent[1] if ent is not None and ent[2]() is p and ent[1].shape == p.shape and ent[1].dtype == dtype else None
-        buf = ops.cast(p.detach(), dtype, out=buf)
-        _shadow[key] = (_ver(p), buf, _wref(_shadow, key, p))
-        return buf
-    return ent[1]
-
-
-def adopt_shadow(p, buf):
-    """Make `buf` (a 16-bit tensor of p's shape, e.g. a view into the sharded optimizer's arena: parallel.GradAllReducer) THE operand copy
-    of `p`: filled from the current fp32 value now, rewritten in place by the optimizer launches and the arena's all-gather afterwards."""
-    assert buf.shape == p.shape and buf.dtype in (torch.bfloat16, torch.float16) and buf.is_contiguous()
-    ops.cast(p.detach(), buf.dtype, out=buf)
-    _shadow[id(p)] = (_ver(p), buf, _wref(_shadow, id(p), p))
-
-
-def shadow_buffer_for_update(p):
-    """The live bf16 operand copy of `p`, if one exists: the optimizer kernel rewrites it in the pass that updates `p`."""
-    ent = _shadow.get(id(p))
-    if ent is not None and ent[2]() is p and ent[1].shape == p.shape and ent[1].dtype in (torch.bfloat16, torch.float16) and ent[1].is_contiguous():
-        return ent[1]
-    return None
-
-
-def shadows_written(params):
-    """Called after an optimizer kernel refreshed the shadows of `params` in place: mark them current."""
-    for p in params:
-        ent = _shadow.get(id(p))
-        if ent is not None and ent[2]() is p:
-            _shadow[id(p)] = (_ver(p), ent[1], ent[2])
-
-
-def refresh_shadows(params, dtype=None):
-    """Re-cast every shadow in place (same storage) -- the form used inside a captured hipGraph step."""
-    dtype = dtype or compute_dtype()
-    for p in params:
-        key = id(p)
-        ent = _shadow.get(key)
-        if ent is not None and ent[2]() is p:
-            ops.cast(p.detach(), dtype, out=ent[1])
-            _shadow[key] = (_ver(p), ent[1], ent[2])
-
-
-def invalidate_shadows(params):
-    """Mark the operand copies (and every weight pre-pack) of `params` stale: their next use re-casts / re-packs into the same storage.  A
-    recorded step whose optimizer does not maintain the copies itself calls this right before the capture, so that the recording contains
-    the casts."""
-    for p in params:
-        ent = _shadow.get(id(p))
-        if ent is not None and ent[2]() is p:
-            _shadow[id(p)] = ((-1, -1), ent[1], ent[2])
-        for cache in (_packed, _packed_conv, _packed_tap, _packed_k3, _packed_img, _packed_k4s2):
-            for key, e in list(cache.items()):
-                if e[2]() is p:
-                    cache[key] = ((-1, -1), e[1], e[2])
 
 
 def to_compute(x, dtype):
@@ -859,35 +773,6 @@ def mlp_chain(x, linears, hidden_act='relu', out_act='none', x_lowp=None, handof
 
 
 # ------------------------------------------------------------------------------------------------ fused rollout
-_packed = {}
-
-
-def packed_weight(p, dtype, transpose):
-    """Rollout pre-pack of a 2-D parameter (fragment order, compute dtype), cached per parameter version."""
-    key = (id(p), bool(transpose), dtype)
-    ent = _packed.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-        buf = ent[1] if ent is not None and ent[2]() is p else None
-        buf = ops.pack_rollout_weight(p.detach().contiguous(), dtype, transpose, out=buf)
-        _packed[key] = (_ver(p), buf, _wref(_packed, key, p))
-        return buf
-    return ent[1]
-
-
-def prepack_weights(requests, dtype):
-    """Bring several rollout pre-packs up to date with ONE launch: requests = [(parameter, transpose)]."""
-    stale = []
-    for p, tr in requests:
-        key = (id(p), bool(tr), dtype)
-        ent = _packed.get(key)
-        if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-            stale.append((key, p, tr, ent[1] if ent is not None and ent[2]() is p else None))
-    if stale:
-        bufs = ops.pack_rollout_weights([(p.detach().contiguous(), tr, buf) for _, p, tr, buf in stale], dtype)
-        for (key, p, _, _), buf in zip(stale, bufs):
-            _packed[key] = (_ver(p), buf, _wref(_packed, key, p))
-
-
 def _stacked_grad_outputs(params, nb):
     """([nb, H, C], [nb, H, H], [nb, C, H] fp32 views over the registered gradient destinations of the integrator's weights, [bias views in
     (block, layer) order]) when every parameter has a destination and the blocks' weights of each layer lie back to back; None otherwise."""
@@ -1018,67 +903,6 @@ class MLPRollout(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ conv blocks
-_packed_conv = {}
-
-
-def packed_conv_weight(p, dtype, stride, pad):
-    """Transposed-form pre-pack of a conv weight (ops.conv_pack_weight), cached per parameter version."""
-    key = (id(p), dtype, stride, pad)
-    ent = _packed_conv.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-        buf = ent[1] if ent is not None and ent[2]() is p else None
-        buf = ops.conv_pack_weight(p.detach().contiguous(), dtype, stride, pad, out=buf)
-        _packed_conv[key] = (_ver(p), buf, _wref(_packed_conv, key, p))
-        return buf
-    return ent[1]
-
-
-_packed_tap = {}
-
-
-def packed_tap_weight(p, dtype):
-    """Tap-GEMM pre-pack of a ConvTranspose2d k4 s2 p1 weight (ops.convt_tap_pack_weight), cached per parameter version."""
-    key = (id(p), dtype)
-    ent = _packed_tap.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-        buf = ent[1] if ent is not None and ent[2]() is p else None
-        buf = ops.convt_tap_pack_weight(p.detach().contiguous(), dtype, out=buf)
-        _packed_tap[key] = (_ver(p), buf, _wref(_packed_tap, key, p))
-        return buf
-    return ent[1]
-
-
-_packed_k3 = {}
-
-
-def packed_k3_weight(p, dtype, flip):
-    """Tap-GEMM pre-pack of a Conv2d k3 s1 p1 weight (forward, or flipped / transposed for the input gradient)."""
-    key = (id(p), dtype, bool(flip))
-    ent = _packed_k3.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-        buf = ent[1] if ent is not None and ent[2]() is p else None
-        buf = ops.conv_k3_tap_pack_weight(p.detach().contiguous(), dtype, flip, out=buf)
-        _packed_k3[key] = (_ver(p), buf, _wref(_packed_k3, key, p))
-        return buf
-    return ent[1]
-
-
-_packed_k4s2 = {}
-
-
-def packed_k4s2_weight(p, dtype):
-    """Row-band pre-pack of a k4 s2 p1 weight over the parity planes of its gather operand (ops.conv_k4s2_pack_weight): a Conv2d weight
-    [Cout, Cin, 4, 4] for its forward, a ConvTranspose2d weight [Cin, Cout, 4, 4] for its input gradient; cached per parameter version."""
-    key = (id(p), dtype)
-    ent = _packed_k4s2.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-        buf = ent[1] if ent is not None and ent[2]() is p else None
-        buf = ops.conv_k4s2_pack_weight(p.detach().contiguous(), dtype, out=buf)
-        _packed_k4s2[key] = (_ver(p), buf, _wref(_packed_k4s2, key, p))
-        return buf
-    return ent[1]
-
-
 def _conv_weight_grad(w, dz, xc, stride, pad, transposed, k4s2=None):
     """Weight gradient of one convolution call for autograd, or None when it was added to / will be batched into the tensor autograd
     already holds.  `k4s2` = (small map, parity planes of the large map): the k4 s2 p1 family on the row-band kernels (ops.conv_k4s2_wgrad)."""
@@ -1195,49 +1019,6 @@ def flush_pending_adds():
         rounds[k][1].append(g)
     for dsts, gs in rounds:
         torch._foreach_add_(dsts, gs)
-
-
-_packed_img = {}
-
-
-def packed_img_weight(p, dtype, flip):
-    """MFMA-fragment pre-pack of a Conv2d k3 s1 p1 weight for `ops.conv3_img16` (forward, or flipped / transposed: input gradient)."""
-    key = (id(p), dtype, bool(flip))
-    ent = _packed_img.get(key)
-    if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-        buf = ent[1] if ent is not None and ent[2]() is p else None
-        buf = ops.conv3_img16_pack_weight(p.detach().contiguous(), dtype, flip, out=buf)
-        _packed_img[key] = (_ver(p), buf, _wref(_packed_img, key, p))
-        return buf
-    return ent[1]
-
-
-def prepack_conv3_weights(net, dtype=None):
-    """Bring the row-band / few-maps pre-packs (forward and flipped) of every 3x3 stride-1 pad-1 convolution of `net` up to date with ONE
-    launch per 96 packs (instead of one launch per pack at its first use: 36-67 launches per TaxiBJ / SST step, every step, because the
-    optimizer changes every weight).  Called by the training step right before the forward pass; what is not stale is skipped."""
-    import torch.nn as nn
-    dtype = dtype or compute_dtype()
-    if dtype == torch.float32:
-        return 0
-    stale = []
-    for m in net.modules():
-        if not (isinstance(m, nn.Conv2d) and tuple(m.kernel_size) == (3, 3) and tuple(m.stride) == (1, 1) and tuple(m.padding) == (1, 1) and m.groups == 1):
-            continue
-        p = m.weight
-        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-            continue
-        for flip in (False, True):
-            K = p.shape[0] if flip else p.shape[1]          # (any K: the pack pads the contraction to whole 64-channel phases)
-            key = (id(p), dtype, flip)
-            ent = _packed_img.get(key)
-            if ent is None or ent[0] != _ver(p) or ent[2]() is not p:
-                stale.append((key, p, flip, ent[1] if ent is not None and ent[2]() is p else None))
-    if stale:
-        bufs = ops.conv3_img16_pack_weights([(p.detach(), flip, buf) for _, p, flip, buf in stale], dtype)
-        for (key, p, _, _), buf in zip(stale, bufs):
-            _packed_img[key] = (_ver(p), buf, _wref(_packed_img, key, p))
-    return len(stale)
 
 
 # Form of the ConvResBlock layers: VARSEP_FUSED_RESBLOCK = '0' (the plain ConvBlock path), '1' (default: convolution and BatchNorm as two launches
@@ -1389,55 +1170,6 @@ class ConvResBlockFn(torch.autograd.Function):
             dx = ops.slab_sum(slabs, None, torch.float32, addend=g_new.contiguous().float() if g_new is not None else None,
                               addend2=g_alias.contiguous().float() if g_alias is not None else None)
         return (dx, None) + tuple(grads) + (None,)
-
-
-# ---- inference: BatchNorm folded into the convolution ---------------------------------------------------------------------------------
-# In `.eval()` a BatchNorm2d normalises with its RUNNING statistics, i.e. it is a fixed per-channel affine map of the convolution's
-# output: act(gamma (conv(x) + b - mean) / sqrt(var + eps) + beta) = act(conv'(x) + b') with W' = W s, b' = (b - mean) s + beta,
-# s = gamma / sqrt(var + eps).  The folded block is ONE kernel (the activation sits in the convolution's epilogue or in the pass that
-# follows it) instead of convolution + BatchNorm pass; SURVEY section 8f rank 1.  Only without autograd (`torch.no_grad()`: the way the
-# reference's evaluation scripts run, test/mnist/test.py:99) -- with gradients enabled the unfolded block is kept so that d gamma / d beta
-# exist.  In the 16-bit modes the rounding points move with it: the folded weight is rounded once (instead of the weight), the convolution
-# output is not stored before the affine map.
-_folded = {}
-
-
-def folded_conv_bn(conv, bn):
-    """(W', b') fp32 tensors of the eval-mode conv -> BatchNorm pair, cached until any of the six tensors involved changes.  The tensors
-    keep their identity across refreshes (in-place update), so the operand copies / weight pre-packs keyed on them refresh themselves."""
-    srcs = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    key = id(conv.weight)
-    vers = (tuple(-1 if t is None else t._version for t in srcs) + tuple(0 if t is None else t.data_ptr() for t in srcs)
-            + (_EPOCH['replay'], _EPOCH['bn']))
-    ent = _folded.get(key)
-    if ent is not None and ent[0] == vers and ent[3]() is conv.weight:
-        return ent[1], ent[2]
-    with torch.no_grad():
-        s = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-        shape = (1, -1, 1, 1) if isinstance(conv, torch.nn.ConvTranspose2d) else (-1, 1, 1, 1)
-        wf = conv.weight.detach().float() * s.view(shape)
-        b0 = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(s)
-        bf = (b0 - bn.running_mean.detach().float()) * s + bn.bias.detach().float()
-        if ent is not None and ent[3]() is conv.weight and ent[1].shape == wf.shape:
-            ent[1].copy_(wf)
-            ent[2].copy_(bf)
-            wf, bf = ent[1], ent[2]
-        else:
-            wf, bf = wf.contiguous(), bf.contiguous()
-    if ent is None or ent[3]() is not conv.weight:
-        # the entry dies with the weight it belongs to (models built and evaluated repeatedly in one process: tests, sweeps)
-        _folded[key] = (vers, wf, bf, weakref.ref(conv.weight, lambda _r, k=key: _drop_folded(k)))
-    else:
-        _folded[key] = (vers, wf, bf, ent[3])
-    return wf, bf
-
-
-def _drop_folded(key):
-    ent = _folded.pop(key, None)
-    if ent is not None:
-        for cache in (_shadow, _packed, _packed_conv, _packed_tap, _packed_k3, _packed_img, _packed_k4s2):
-            for k in [k for k, e in cache.items() if e[2]() is ent[1] or e[2]() is ent[2]]:
-                cache.pop(k, None)
 
 
 def _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt):

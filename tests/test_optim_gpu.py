@@ -446,3 +446,59 @@ def test_loss_scaling_refuses_updates_issued_during_backward():
     assert opt._buckets
     with pytest.raises(ValueError):
         scaler.step(opt)
+
+
+def test_weight_prepacks_follow_the_version_counter_in_place():
+    """The pre-packs of the convolution kernels on the device: derived once, re-derived by the same kernel into the same storage after the
+    weight's version counter moved, and then equal to a pack made from scratch (the batched 3x3 pre-pack included)."""
+    from spatiotemporal_variable_separation_amd import functional as VF
+    from spatiotemporal_variable_separation_amd import ops
+    bf16 = torch.bfloat16
+    launches = []
+
+    def counted(name):
+        fn = getattr(ops, name)
+
+        def call(*a, **k):
+            launches.append(name)
+            return fn(*a, **k)
+        return fn, call
+
+    singles = ('conv3_img16_pack_weight', 'convt_tap_pack_weight', 'conv_k4s2_pack_weight', 'conv_pack_weight')
+    plain = {name: counted(name) for name in singles + ('conv3_img16_pack_weights',)}
+    with pytest.MonkeyPatch.context() as mp:
+        for name, (_, call) in plain.items():
+            mp.setattr(ops, name, call)
+        torch.manual_seed(3)
+        net = torch.nn.Sequential(torch.nn.Conv2d(16, 16, 3, 1, 1), torch.nn.Conv2d(16, 16, 3, 1, 1)).cuda()
+        with VF.precision('bf16'):
+            assert VF.prepack_conv3_weights(net) == 4 and launches == ['conv3_img16_pack_weights']
+            assert VF.prepack_conv3_weights(net) == 0 and len(launches) == 1
+            p = net[1].weight
+            before = {flip: VF.packed_img_weight(p, bf16, flip) for flip in (False, True)}
+            address = {flip: before[flip].data_ptr() for flip in before}
+            with torch.no_grad():
+                p.add_(0.25)
+            assert VF.prepack_conv3_weights(net) == 2 and launches == ['conv3_img16_pack_weights'] * 2
+        for flip in (False, True):
+            pack = VF.packed_img_weight(p, bf16, flip)
+            assert len(launches) == 2 and pack is before[flip] and pack.data_ptr() == address[flip]
+            assert torch.equal(pack, plain['conv3_img16_pack_weight'][0](p.detach().contiguous(), bf16, flip))
+            assert torch.equal(VF.packed_img_weight(net[0].weight, bf16, flip),
+                               plain['conv3_img16_pack_weight'][0](net[0].weight.detach().contiguous(), bf16, flip))
+        assert len(launches) == 2
+        w = torch.nn.ConvTranspose2d(8, 8, 4, 2, 1).cuda().weight
+        for use, name, args in ((lambda: VF.packed_tap_weight(w, bf16), 'convt_tap_pack_weight', ()),
+                                (lambda: VF.packed_k4s2_weight(w, bf16), 'conv_k4s2_pack_weight', ()),
+                                (lambda: VF.packed_conv_weight(w, bf16, 2, 1), 'conv_pack_weight', (2, 1))):
+            del launches[:]
+            pack = use()
+            assert use() is pack and launches == [name]
+            address = pack.data_ptr()
+            assert torch.equal(pack, plain[name][0](w.detach().contiguous(), bf16, *args))
+            with torch.no_grad():
+                w.mul_(-1.5)
+            again = use()
+            assert again is pack and again.data_ptr() == address and launches == [name] * 2
+            assert use() is pack and len(launches) == 2
+            assert torch.equal(pack, plain[name][0](w.detach().contiguous(), bf16, *args))
