@@ -9,8 +9,10 @@ Precision policy (`set_precision` / `precision(...)`):
   'fp16' -- the same rounding points with IEEE half operands (v_mfma_f32_*_f16): the reference's --torch_amp mode
             (torch.cuda.amp autocast, train.py:96-97); trained with dynamic loss scaling (train.LossScaler).
 """
+import collections
 import contextlib
 import os
+import types
 import weakref
 
 import torch
@@ -1172,28 +1174,147 @@ class ConvResBlockFn(torch.autograd.Function):
         return (dx, None) + tuple(grads) + (None,)
 
 
-def _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt):
-    """BatchNorm (+ activation) of a convolution output z on the two-launch path: (y, mean, invstd).  Training with tracked running estimates:
-    the fold of the running estimates rides in the apply launch."""
-    if training:
-        if ops.bn_slab_supported(z, groups):
-            # (a call's channel slab fits one workgroup's registers: statistics and apply from ONE read of z)
-            return ops.bn_train_fwd_slab(z, gamma.detach(), beta.detach(), act, out_dt, rmean, rvar, momentum, eps, groups=groups)
-        if rmean is not None:
-            mean, invstd, ub = ops.bn_stats_ub(z, eps, groups=groups)
-            y = ops.bn_act_fwd(z, mean, invstd, gamma.detach(), beta.detach(), act, out_dt, groups=groups, running=(ub, rmean, rvar, momentum))
-            return y, mean, invstd
-        mean, invstd = ops.bn_stats(z, rmean, rvar, momentum, eps, groups=groups)
-    else:
-        mean = rmean.detach().unsqueeze(0).expand(groups, -1).contiguous()
-        invstd = torch.rsqrt(rvar.detach() + eps).unsqueeze(0).expand(groups, -1).contiguous()
-    return ops.bn_act_fwd(z, mean, invstd, gamma.detach(), beta.detach(), act, out_dt, groups=groups), mean, invstd
+def _conv_family(w, transposed, stride, pad):
+    """The kernel family of a layer, from its geometry: 'k3' (Conv2d k3 s1 p1), 'k4' (Conv2d k4 s2 p1), 'k4t' (ConvTranspose2d k4 s2 p1) or
+    'other'."""
+    k = tuple(w.shape[2:])
+    if k == (3, 3) and not transposed and stride == 1 and pad == 1:
+        return 'k3'
+    if k == (4, 4) and stride == 2 and pad == 1:
+        return 'k4t' if transposed else 'k4'
+    return 'other'
 
 
 def band_ok(x, w, transposed, stride, pad, dgrad=False):
     """Conv2d k3 s1 p1 of `x` with weight `w` ([Cout, Cin, 3, 3]) -- or, dgrad=True, its input gradient from x = dz -- on the row-band kernel."""
-    return (not transposed and stride == 1 and pad == 1 and w.shape[2] == 3 and w.shape[3] == 3
-            and ops.conv3_band_supported(x, w.shape[1] if dgrad else w.shape[0]))
+    return _conv_family(w, transposed, stride, pad) == 'k3' and ops.conv3_band_supported(x, w.shape[1] if dgrad else w.shape[0])
+
+
+def _conv_route(x_dtype, x_shape, w_shape, family, has_bn, groups, out_dt, cdt):
+    """The forward route of one ConvBlock call (no side effects); the first that holds, a family at a time:
+    'k4_planes', 'k4_gather', 'img16', 'band', 'tap', 'k3tap', 'cols' (DESIGN.md section 5)."""
+    # what the host-only `ops.*_supported` tests read of a tensor, and no more: one that starts to read anything else (contiguity, an address)
+    # gets an AttributeError here, not a wrong answer, and has to be given the tensor
+    x = types.SimpleNamespace(dtype=x_dtype, shape=tuple(x_shape), dim=lambda: len(x_shape))
+    if family == 'k4':
+        # Conv2d k4 s2 p1 (the DCGAN encoder's stride-2 layers): on the four parity planes of the input the 4x4 stride-2 window is a 3x3
+        # stride-1 window, so the row-band kernel carries it -- no column matrix; the planes are what the weight gradient needs, too
+        if ops.conv_k4s2_supported(x, w_shape[0]):
+            return 'k4_planes'
+        # 8 x 8 -> 4 x 4 (the DCGAN encoder's c4, conv.py:122): the forward on the parity planes; the weight gradient keeps the column matrix
+        # (where the row-band weight gradient does not serve the planes), so backward gets x itself.  Only in front of a BatchNorm.
+        if has_bn and ops.conv_k4s2_gather_supported(x, w_shape[0]):
+            return 'k4_gather'
+    elif family == 'k3':
+        # Conv2d k3 s1 p1 on a few 16x16 maps (the SST ConvResnet integrator, resnet.py:53-88): one chip-filling launch that leaves
+        # split partial sums; the slab sum, the bias and the whole BatchNorm forward are the next (single) launch
+        if groups == 1 and ops.conv3_img16_supported(x, w_shape[0]):
+            return 'img16'
+        # 3x3 on many maps of width 16 / 32 / 64: row bands through LDS, no column matrix; BatchNorm as for the column-matrix path
+        if ops.conv3_band_supported(x, w_shape[0]):
+            return 'band'
+        # long contractions only (ops.conv_k3_tap_supported: 512 -> 512 at 16x16 45 vs 65 us, 128 -> 128 489 vs 371 us); without a BatchNorm
+        # it is launched with groups=1
+        if ops.conv_k3_tap_supported(x, w_shape[0], groups):
+            return 'k3tap'
+    elif family == 'k4t':
+        # ConvTranspose2d k4 s2 p1 on 4x4 / 8x8 / 16x16 maps (the DCGAN decoder's middle layers): LDS-staged tap GEMM with the
+        # col2im and the BatchNorm sums in its epilogue -- no column matrix, no separate statistics pass.  Without a BatchNorm (inference with
+        # it folded into the weight) the tap kernel without its statistics epilogue, which writes the compute type only
+        if ops.convt_tap_supported(x, w_shape[1], groups) and (has_bn or out_dt == cdt):
+            return 'tap'
+    return 'cols'
+
+
+# The routes whose BatchNorm may be the one-launch `bn_train_fwd_small` (small maps, the SST integrator: 8 x 16 x 16 per channel: statistics,
+# running update, affine + activation in one launch).  The k4 and tap routes never tried it; img16 has its own one-launch form on the slabs.
+_TRIES_SMALL_BN = ('band', 'cols')
+_ConvCfg = collections.namedtuple('_ConvCfg', 'transposed stride pad has_bn act training momentum eps out_fp32 groups')      # (ConvBlock's cfg, named)
+
+
+def _conv_stage(route, xc, w, bias, cfg, gamma, out_dt, cdt):
+    """The convolution of `route` -> (keep, raw, stats).  keep: what backward needs as the layer input (xc, or its parity planes on 'k4_planes').
+    raw: z in the compute type when a BatchNorm follows, y in out_dt when none does; on 'img16' in front of a BatchNorm the fp32 split slabs.
+    stats: where `_bn_apply` takes the batch statistics from -- None (from z), ('sums', fp64 sums, reset), ('parts', table), ('slabs', bias)."""
+    has_bn, training, groups = cfg.has_bn, cfg.training, cfg.groups
+    dt = cdt if has_bn else out_dt
+    Cout = w.shape[1] if cfg.transposed else w.shape[0]
+    keep, stats = xc, None
+    if route in ('k4_planes', 'k4_gather', 'band'):
+        k4 = route != 'band'
+        src = ops.space_to_depth2(xc) if k4 else xc
+        wpk = packed_k4s2_weight(w, cdt) if k4 else packed_img_weight(w, cdt, False)
+        conv = ops.conv_k4s2_gather if k4 else ops.conv3_band
+        if route == 'k4_planes':
+            keep = src
+        B, C, H, W = src.shape
+        # the BatchNorm sums taken in the convolution's epilogue (VS_BAND_BN_SUMS): no statistics pass over z.  Not on the 4x4 planes of
+        # 'k4_gather', and on the band not where the one-launch BatchNorm takes the layer
+        epilogue = has_bn and training and route != 'k4_gather'
+        if epilogue and route == 'band':
+            epilogue = not (ops.bn_small_supported_shape(cdt, B, Cout, H * W) and (groups == 1 or ops.bn_small_groups_enabled()))
+        if epilogue and ops.conv_band_bn_supported(B, C, H, W, Cout, groups, cdt):
+            if ops.band_bn_mode() == '1':
+                sums = ops.bn_sums_buffer(gamma.data_ptr(), groups, Cout, src.device)
+                raw = conv(src, wpk, bias, Cout, cdt, bn_sums=sums, groups=groups)
+                stats = ('sums', sums, True)
+            else:                                    # per-workgroup partial sums + one fold launch (no atomics)
+                raw, parts = ops.conv3_band_parts(src, wpk, bias, Cout, cdt, k4=k4)
+                stats = ('parts', parts)
+        else:
+            raw = conv(src, wpk, bias, Cout, dt)
+    elif route == 'img16':
+        raw = ops.conv3_img16(xc, packed_img_weight(w, cdt, False), Cout)
+        if has_bn:
+            stats = ('slabs', bias)
+        else:
+            raw = ops.slab_sum(raw, bias, out_dt)
+    elif route in ('tap', 'k3tap'):
+        want_sums = has_bn and training
+        if route == 'tap':
+            raw, sums = ops.convt_tap_fwd(xc, packed_tap_weight(w, cdt), bias, Cout, groups=groups, want_sums=want_sums)
+        else:
+            raw, sums = ops.conv_k3_tap_fwd(xc, packed_k3_weight(w, cdt, False), bias, Cout, dt, groups=groups if has_bn else 1, want_sums=want_sums)
+        if want_sums:
+            stats = ('sums', sums, False)            # (a buffer of this call: nothing to reset)
+    else:
+        wc = shadow(w, cdt)
+        wp = packed_conv_weight(w, cdt, cfg.stride, cfg.pad) if cfg.transposed else None
+        raw = ops.conv_fwd(xc, wc, bias, cfg.stride, cfg.pad, cfg.transposed, dt, w_packed=wp)
+    return keep, raw, stats
+
+
+def _bn_apply(raw, stats, try_small, cfg, rmean, rvar, gamma, beta, out_dt, cdt):
+    """BatchNorm (+ activation) behind `_conv_stage`: (y, z, mean, invstd).  Training with tracked running estimates folds them in the launch
+    that takes the statistics, or in the apply launch."""
+    act, training, momentum, eps, groups = cfg.act, cfg.training, cfg.momentum, cfg.eps, cfg.groups
+    gamma, beta = gamma.detach(), beta.detach()
+    kind, z, y = (stats[0] if stats else None), raw, None
+    if kind == 'slabs':
+        if training and ops.bn_small_supported_shape(cdt, raw.shape[1], raw.shape[2], 256):
+            return ops.bn_train_fwd_small_slabs(raw, stats[1], cdt, gamma, beta, act, out_dt, rmean, rvar, momentum, eps)
+        z = ops.slab_sum(raw, stats[1], cdt)         # ... and the plain path below (groups == 1 on this route)
+    n_per = (z.shape[0] // groups) * z.shape[2] * z.shape[3]
+    if kind == 'sums':
+        mean, invstd = ops.bn_stats_from_sums_fold(stats[1], n_per, rmean, rvar, momentum, eps, reset=stats[2])     # (one launch: statistics + running fold)
+    elif kind == 'parts':
+        mean, invstd = ops.bn_stats_from_parts_fold(stats[1], groups, n_per, rmean, rvar, momentum, eps)
+    elif not training:
+        mean = rmean.detach().unsqueeze(0).expand(groups, -1).contiguous()
+        invstd = torch.rsqrt(rvar.detach() + eps).unsqueeze(0).expand(groups, -1).contiguous()
+    elif try_small and ops.bn_small_supported(z, groups):
+        y, mean, invstd = ops.bn_train_fwd_small(z, gamma, beta, act, out_dt, rmean, rvar, momentum, eps, groups=groups)
+    elif ops.bn_slab_supported(z, groups):
+        # (a call's channel slab fits one workgroup's registers: statistics and apply from ONE read of z)
+        y, mean, invstd = ops.bn_train_fwd_slab(z, gamma, beta, act, out_dt, rmean, rvar, momentum, eps, groups=groups)
+    elif rmean is not None:
+        mean, invstd, ub = ops.bn_stats_ub(z, eps, groups=groups)
+        y = ops.bn_act_fwd(z, mean, invstd, gamma, beta, act, out_dt, groups=groups, running=(ub, rmean, rvar, momentum))
+    else:
+        mean, invstd = ops.bn_stats(z, rmean, rvar, momentum, eps, groups=groups)
+    if y is None:
+        y = ops.bn_act_fwd(z, mean, invstd, gamma, beta, act, out_dt, groups=groups)
+    return y, z, mean, invstd
 
 
 class ConvBlock(torch.autograd.Function):
@@ -1207,155 +1328,31 @@ class ConvBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, rmean, rvar, cfg):
         require_cuda(x)
-        transposed, stride, pad, has_bn, act, training, momentum, eps, out_fp32, groups = cfg
+        c = _ConvCfg(*cfg)
         cdt = compute_dtype()
-        out_dt = torch.float32 if out_fp32 else cdt
+        out_dt = torch.float32 if c.out_fp32 else cdt
         xc = to_compute(x, cdt)
-        bias = b.detach() if b is not None else None
-        # ConvTranspose2d k4 s2 p1 on 4x4 / 8x8 / 16x16 maps (the DCGAN decoder's middle layers): LDS-staged tap GEMM with the
-        # col2im and the BatchNorm sums in its epilogue -- no column matrix, no separate statistics pass
-        tap_geom = (transposed and stride == 2 and pad == 1 and w.shape[2] == 4 and w.shape[3] == 4
-                    and ops.convt_tap_supported(xc, w.shape[1], groups))
-        tap = tap_geom and has_bn
-        k3 = (not transposed and stride == 1 and pad == 1 and w.shape[2] == 3 and w.shape[3] == 3
-              and ops.conv_k3_tap_supported(xc, w.shape[0], groups))
-        # Conv2d k3 s1 p1 on a few 16x16 maps (the SST ConvResnet integrator, resnet.py:53-88): one chip-filling launch that leaves
-        # split partial sums; the slab sum, the bias and the whole BatchNorm forward are the next (single) launch
-        img = (not transposed and stride == 1 and pad == 1 and w.shape[2] == 3 and w.shape[3] == 3 and groups == 1
-               and ops.conv3_img16_supported(xc, w.shape[0]))
-        # Conv2d k4 s2 p1 (the DCGAN encoder's stride-2 layers): on the four parity planes of the input the 4x4 stride-2 window is a 3x3
-        # stride-1 window, so the row-band kernel carries it -- no column matrix; the planes are what the weight gradient needs, too
-        k4 = (not transposed and stride == 2 and pad == 1 and w.shape[2] == 4 and w.shape[3] == 4 and ops.conv_k4s2_supported(xc, w.shape[0]))
-        ctx.k4_planes = False
-        if k4:
-            planes = ops.space_to_depth2(xc)
-            wpk = packed_k4s2_weight(w, cdt)
-            ctx.k4_planes = True
-            if has_bn:
-                Bp, C4, Hp, Wp = planes.shape
-                if training and ops.conv_band_bn_supported(Bp, C4, Hp, Wp, w.shape[0], groups, cdt):
-                    # the BatchNorm sums are taken in the convolution's epilogue: no statistics pass over z
-                    if ops.band_bn_mode() == '1':
-                        sums = ops.bn_sums_buffer(gamma.data_ptr(), groups, w.shape[0], planes.device)
-                        z = ops.conv_k4s2_gather(planes, wpk, bias, w.shape[0], cdt, bn_sums=sums, groups=groups)
-                        mean, invstd = ops.bn_stats_from_sums_fold(sums, (Bp // groups) * Hp * Wp, rmean, rvar, momentum, eps)
-                    else:                            # per-workgroup partial sums + one fold launch (no atomics)
-                        z, parts = ops.conv3_band_parts(planes, wpk, bias, w.shape[0], cdt, k4=True)
-                        mean, invstd = ops.bn_stats_from_parts_fold(parts, groups, (Bp // groups) * Hp * Wp, rmean, rvar, momentum, eps)
-                    y = ops.bn_act_fwd(z, mean, invstd, gamma.detach(), beta.detach(), act, out_dt, groups=groups)
-                else:
-                    z = ops.conv_k4s2_gather(planes, wpk, bias, w.shape[0], cdt)
-                    y, mean, invstd = _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt)
-                ctx.save_for_backward(planes, z, mean, invstd)
-            else:
-                y = ops.conv_k4s2_gather(planes, wpk, bias, w.shape[0], out_dt)
-                if act not in ('none', None):
-                    ops.act_fwd(y, act, out=y)
-                ctx.save_for_backward(planes, y)
-            ctx.x_shape = tuple(xc.shape)
-        elif (has_bn and not transposed and stride == 2 and pad == 1 and w.shape[2] == 4 and w.shape[3] == 4
-              and ops.conv_k4s2_gather_supported(xc, w.shape[0])):
-            # 8 x 8 -> 4 x 4 (the DCGAN encoder's c4, conv.py:122): the forward on the parity planes; the weight gradient keeps the column matrix
-            # (the row-band weight gradient does not serve 4 x 4 planes), so backward gets x itself
-            planes = ops.space_to_depth2(xc)
-            z = ops.conv_k4s2_gather(planes, packed_k4s2_weight(w, cdt), bias, w.shape[0], cdt)
-            y, mean, invstd = _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt)
-            ctx.save_for_backward(xc, z, mean, invstd)
-        elif img:
-            slabs = ops.conv3_img16(xc, packed_img_weight(w, cdt, False), w.shape[0])
-            if has_bn:
-                if training and ops.bn_small_supported_shape(cdt, xc.shape[0], w.shape[0], 256):
-                    y, z, mean, invstd = ops.bn_train_fwd_small_slabs(slabs, bias, cdt, gamma.detach(), beta.detach(), act, out_dt, rmean, rvar,
-                                                                      momentum, eps)
-                else:
-                    z = ops.slab_sum(slabs, bias, cdt)
-                    y, mean, invstd = _bn_apply(z, training, rmean, rvar, momentum, eps, 1, gamma, beta, act, out_dt)
-                ctx.save_for_backward(xc, z, mean, invstd)
-            else:
-                y = ops.slab_sum(slabs, bias, out_dt)
-                if act not in ('none', None):
-                    ops.act_fwd(y, act, out=y)
-                ctx.save_for_backward(xc, y)
-        elif band_ok(xc, w, transposed, stride, pad) and not tap:
-            # 3x3 on many maps of width 16 / 32 / 64: row bands through LDS, no column matrix; BatchNorm as for the column-matrix path
-            wpk = packed_img_weight(w, cdt, False)
-            if has_bn:
-                Bx, Cx, Hx, Wx = xc.shape
-                small = training and ops.bn_small_supported_shape(cdt, Bx, w.shape[0], Hx * Wx) and (groups == 1 or ops.bn_small_groups_enabled())
-                if training and not small and ops.conv_band_bn_supported(Bx, Cx, Hx, Wx, w.shape[0], groups, cdt):
-                    # the BatchNorm sums are taken in the convolution's epilogue: no statistics pass over z
-                    if ops.band_bn_mode() == '1':
-                        sums = ops.bn_sums_buffer(gamma.data_ptr(), groups, w.shape[0], xc.device)
-                        z = ops.conv3_band(xc, wpk, bias, w.shape[0], cdt, bn_sums=sums, groups=groups)
-                        mean, invstd = ops.bn_stats_from_sums_fold(sums, (Bx // groups) * Hx * Wx, rmean, rvar, momentum, eps)
-                    else:                            # per-workgroup partial sums + one fold launch (no atomics)
-                        z, parts = ops.conv3_band_parts(xc, wpk, bias, w.shape[0], cdt)
-                        mean, invstd = ops.bn_stats_from_parts_fold(parts, groups, (Bx // groups) * Hx * Wx, rmean, rvar, momentum, eps)
-                    y = ops.bn_act_fwd(z, mean, invstd, gamma.detach(), beta.detach(), act, out_dt, groups=groups)
-                    ctx.save_for_backward(xc, z, mean, invstd)
-                    ctx.cfg, ctx.cdt = cfg, cdt
-                    ctx.w, ctx.b, ctx.gamma, ctx.beta = w, b, gamma, beta
-                    ctx.x_dtype, ctx.x_needs_grad = x.dtype, x.requires_grad
-                    ctx.x_shape = tuple(xc.shape)
-                    return y
-                z = ops.conv3_band(xc, wpk, bias, w.shape[0], cdt)
-                if training and ops.bn_small_supported(z, groups):
-                    y, mean, invstd = ops.bn_train_fwd_small(z, gamma.detach(), beta.detach(), act, out_dt, rmean, rvar, momentum, eps, groups=groups)
-                else:
-                    y, mean, invstd = _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt)
-                ctx.save_for_backward(xc, z, mean, invstd)
-            else:
-                y = ops.conv3_band(xc, wpk, bias, w.shape[0], out_dt)
-                if act not in ('none', None):
-                    ops.act_fwd(y, act, out=y)
-                ctx.save_for_backward(xc, y)
-        elif tap or (k3 and has_bn):
-            if tap:
-                z, sums = ops.convt_tap_fwd(xc, packed_tap_weight(w, cdt), bias, w.shape[1], groups=groups, want_sums=training)
-            else:
-                z, sums = ops.conv_k3_tap_fwd(xc, packed_k3_weight(w, cdt, False), bias, w.shape[0], cdt, groups=groups, want_sums=training)
-            if training:
-                n_per = (z.shape[0] // groups) * z.shape[2] * z.shape[3]
-                mean, invstd = ops.bn_stats_from_sums_fold(sums, n_per, rmean, rvar, momentum, eps, reset=False)     # (one launch: statistics + running fold)
-            else:
-                mean = rmean.detach().unsqueeze(0).expand(groups, -1).contiguous()
-                invstd = torch.rsqrt(rvar.detach() + eps).unsqueeze(0).expand(groups, -1).contiguous()
-            y = ops.bn_act_fwd(z, mean, invstd, gamma.detach(), beta.detach(), act, out_dt, groups=groups)
-            ctx.save_for_backward(xc, z, mean, invstd)
-        elif has_bn:
-            wc = shadow(w, cdt)
-            wp = packed_conv_weight(w, cdt, stride, pad) if transposed else None
-            z = ops.conv_fwd(xc, wc, bias, stride, pad, transposed, cdt, w_packed=wp)
-            if training and ops.bn_small_supported(z, groups):
-                # small maps (the SST integrator: 8 x 16 x 16 per channel): statistics, running update, affine + activation in one launch
-                y, mean, invstd = ops.bn_train_fwd_small(z, gamma.detach(), beta.detach(), act, out_dt, rmean, rvar, momentum, eps, groups=groups)
-            else:
-                y, mean, invstd = _bn_apply(z, training, rmean, rvar, momentum, eps, groups, gamma, beta, act, out_dt)
-            ctx.save_for_backward(xc, z, mean, invstd)
+        route = _conv_route(xc.dtype, xc.shape, w.shape, _conv_family(w, c.transposed, c.stride, c.pad), c.has_bn, c.groups, out_dt, cdt)
+        keep, raw, stats = _conv_stage(route, xc, w, b.detach() if b is not None else None, c, gamma, out_dt, cdt)
+        if c.has_bn:
+            y, z, mean, invstd = _bn_apply(raw, stats, route in _TRIES_SMALL_BN, c, rmean, rvar, gamma, beta, out_dt, cdt)
+            ctx.save_for_backward(keep, z, mean, invstd)
         else:
-            if k3:
-                y, _ = ops.conv_k3_tap_fwd(xc, packed_k3_weight(w, cdt, False), bias, w.shape[0], out_dt, groups=1)
-            elif tap_geom and out_dt == cdt:
-                # (inference with the BatchNorm folded into the weight: the tap kernel without its statistics epilogue)
-                y, _ = ops.convt_tap_fwd(xc, packed_tap_weight(w, cdt), bias, w.shape[1], groups=groups, want_sums=False)
-            else:
-                wc = shadow(w, cdt)
-                wp = packed_conv_weight(w, cdt, stride, pad) if transposed else None
-                y = ops.conv_fwd(xc, wc, bias, stride, pad, transposed, out_dt, w_packed=wp)
-            if act not in ('none', None):
-                ops.act_fwd(y, act, out=y)
-            ctx.save_for_backward(xc, y)
+            y = raw
+            if c.act not in ('none', None):
+                ops.act_fwd(y, c.act, out=y)
+            ctx.save_for_backward(keep, y)
         ctx.cfg, ctx.cdt = cfg, cdt
         ctx.w, ctx.b, ctx.gamma, ctx.beta = w, b, gamma, beta
         ctx.x_dtype, ctx.x_needs_grad = x.dtype, x.requires_grad
-        if not ctx.k4_planes:
-            ctx.x_shape = tuple(xc.shape)
+        ctx.x_shape, ctx.k4_planes = tuple(xc.shape), route == 'k4_planes'
         return y
 
     @staticmethod
     def backward(ctx, dy):
         transposed, stride, pad, has_bn, act, training, momentum, eps, out_fp32, groups = ctx.cfg
         cdt, w, b = ctx.cdt, ctx.w, ctx.b
+        family = _conv_family(w, transposed, stride, pad)
         dgamma = dbeta = None
         if has_bn:
             xc, z, mean, invstd = ctx.saved_tensors
@@ -1378,8 +1375,7 @@ class ConvBlock(torch.autograd.Function):
         if ctx.k4_planes:
             # forward kept the parity planes of the input: they are the large operand of the weight gradient
             dw = _conv_weight_grad(w, dz, None, stride, pad, transposed, k4s2=(dz, xc)) if w.requires_grad else None
-        elif (transposed and stride == 2 and pad == 1 and w.shape[2] == 4 and w.shape[3] == 4 and dz.dtype == xc.dtype
-              and ops.conv_k4s2_supported(dz, w.shape[0])):
+        elif family == 'k4t' and dz.dtype == xc.dtype and ops.conv_k4s2_supported(dz, w.shape[0]):
             # ConvTranspose2d k4 s2 p1 (the DCGAN decoder): the parity planes of the output gradient serve the weight gradient (small map
             # = the layer input) AND the input gradient (a k4 s2 p1 gather of dz with the weight read as [out = Cin][in = Cout])
             dz_planes = ops.space_to_depth2(dz)
@@ -1387,22 +1383,20 @@ class ConvBlock(torch.autograd.Function):
         else:
             dw = _conv_weight_grad(w, dz, xc, stride, pad, transposed) if w.requires_grad else None
         dx = None
-        if ctx.x_needs_grad and dz_planes is not None:
-            dx = ops.conv_k4s2_gather(dz_planes, packed_k4s2_weight(w, cdt), None, w.shape[0], ctx.x_dtype, role='dgrad')
-        elif ctx.x_needs_grad:
-            # the input gradient of Conv2d k4 s2 p1 IS a ConvTranspose2d k4 s2 p1 of dz with the same weight tensor ([Cout, Cin, 4, 4]
-            # read as [in, out, 4, 4]): on 4x4 / 8x8 / 16x16 gradient maps it takes the LDS-staged tap kernel (no column matrix)
-            if (not transposed and stride == 2 and pad == 1 and w.shape[2] == 4 and w.shape[3] == 4 and ctx.x_dtype == dz.dtype
-                    and x_shape[2] == 2 * dz.shape[2] and x_shape[3] == 2 * dz.shape[3] and ops.convt_tap_supported(dz, w.shape[1], 1)):
+        if ctx.x_needs_grad:
+            if dz_planes is not None:
+                dx = ops.conv_k4s2_gather(dz_planes, packed_k4s2_weight(w, cdt), None, w.shape[0], ctx.x_dtype, role='dgrad')
+            elif (family == 'k4' and ctx.x_dtype == dz.dtype and x_shape[2] == 2 * dz.shape[2] and x_shape[3] == 2 * dz.shape[3]
+                  and ops.convt_tap_supported(dz, w.shape[1], 1)):
+                # the input gradient of Conv2d k4 s2 p1 IS a ConvTranspose2d k4 s2 p1 of dz with the same weight tensor ([Cout, Cin, 4, 4]
+                # read as [in, out, 4, 4]): on 4x4 / 8x8 / 16x16 gradient maps it takes the LDS-staged tap kernel (no column matrix)
                 dx, _ = ops.convt_tap_fwd(dz, packed_tap_weight(w, cdt), None, w.shape[1], groups=1, want_sums=False, role='dgrad')
-            elif (not transposed and stride == 1 and pad == 1 and w.shape[2] == 3 and w.shape[3] == 3 and groups == 1
-                  and ops.conv3_img16_supported(dz, w.shape[1])):
+            elif family == 'k3' and groups == 1 and ops.conv3_img16_supported(dz, w.shape[1]):
                 # few 16x16 maps: the same one-launch kernel on dz with the weight packed transposed and flipped
                 dx = ops.slab_sum(ops.conv3_img16(dz, packed_img_weight(w, cdt, True), w.shape[1], role='dgrad'), None, ctx.x_dtype)
-            elif band_ok(dz, w, transposed, stride, pad, dgrad=True):
+            elif family == 'k3' and ops.conv3_band_supported(dz, w.shape[1]):
                 dx = ops.conv3_band(dz, packed_img_weight(w, cdt, True), None, w.shape[1], ctx.x_dtype, role='dgrad')
-            elif (not transposed and stride == 1 and pad == 1 and w.shape[2] == 3 and w.shape[3] == 3
-                  and ops.conv_k3_tap_supported(dz, w.shape[1], 1)):
+            elif family == 'k3' and ops.conv_k3_tap_supported(dz, w.shape[1], 1):
                 # Conv2d k3 s1 p1: the input gradient is the same convolution of dz with the weight transposed and flipped
                 dx, _ = ops.conv_k3_tap_fwd(dz, packed_k3_weight(w, cdt, True), None, w.shape[1], ctx.x_dtype, groups=1, role='dgrad')
             else:

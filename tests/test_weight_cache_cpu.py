@@ -6,56 +6,14 @@ WHEN a copy is derived and INTO WHICH storage: a copy is valid for one (version 
 into the same storage (recorded graphs keep addressing it) and an entry dies with its tensor.
 """
 import gc
-import weakref
 
 import pytest
 import torch
 
+from ops_standins import StandIns
 from spatiotemporal_variable_separation_amd import functional as VF
-from spatiotemporal_variable_separation_amd import ops
 
 BF, HF = torch.bfloat16, torch.float16
-
-
-class StandIns:
-    """CPU versions of the nine `ops` functions the caches call.  `calls`: (name, source tensor, extra arguments, the `out` given);
-    the batched ones log (name, [(source, flag, out given)]).  `made`: weak references to every buffer a stand-in allocated."""
-
-    def __init__(self):
-        self.calls, self.made = [], []
-
-    def _new(self, shape, dtype):
-        buf = torch.empty(shape, dtype=dtype)
-        self.made.append(weakref.ref(buf))
-        return buf
-
-    def live(self):
-        return sum(r() is not None for r in self.made)
-
-    def cast(self, src, dtype, out=None):
-        self.calls.append(('cast', src, (dtype,), out))
-        buf = self._new(src.shape, dtype) if out is None else out
-        return buf.copy_(src)
-
-    def _pack(self, name, w, dtype, extra, out):
-        self.calls.append((name, w, (dtype,) + extra, out))
-        buf = self._new((w.numel(),), dtype) if out is None else out
-        return buf.copy_(w.reshape(-1) * (-1 if extra and extra[0] is True else 1))       # (a flipped / transposed pack differs)
-
-    def _packs(self, name, jobs, dtype):
-        self.calls.append((name, [tuple(j) for j in jobs]))
-        return [(self._new((w.numel(),), dtype) if out is None else out).copy_(w.reshape(-1) * (-1 if flag else 1)) for w, flag, out in jobs]
-
-    def install(self, monkeypatch):
-        monkeypatch.setattr(ops, 'cast', self.cast)
-        monkeypatch.setattr(ops, 'pack_rollout_weight', lambda w, dtype, transpose, out=None: self._pack('pack_rollout_weight', w, dtype, (bool(transpose),), out))
-        monkeypatch.setattr(ops, 'pack_rollout_weights', lambda jobs, dtype: self._packs('pack_rollout_weights', jobs, dtype))
-        monkeypatch.setattr(ops, 'conv_pack_weight', lambda w, dtype, stride, pad, out=None: self._pack('conv_pack_weight', w, dtype, (stride, pad), out))
-        monkeypatch.setattr(ops, 'convt_tap_pack_weight', lambda w, dtype, out=None: self._pack('convt_tap_pack_weight', w, dtype, (), out))
-        monkeypatch.setattr(ops, 'conv_k3_tap_pack_weight', lambda w, dtype, flip, out=None: self._pack('conv_k3_tap_pack_weight', w, dtype, (bool(flip),), out))
-        monkeypatch.setattr(ops, 'conv_k4s2_pack_weight', lambda w, dtype, out=None: self._pack('conv_k4s2_pack_weight', w, dtype, (), out))
-        monkeypatch.setattr(ops, 'conv3_img16_pack_weight', lambda w, dtype, flip, out=None: self._pack('conv3_img16_pack_weight', w, dtype, (bool(flip),), out))
-        monkeypatch.setattr(ops, 'conv3_img16_pack_weights', lambda jobs, dtype: self._packs('conv3_img16_pack_weights', jobs, dtype))
 
 
 @pytest.fixture
