@@ -100,6 +100,85 @@ def test_colsum_cast_act():
     assert torch.allclose(g, x * y * (1 - y), rtol=1e-5, atol=1e-7)
 
 
+# ---- vs_act_fwd / vs_act_bwd / vs_cast: every activation, every (input, output) type pair, lengths around the 4-element vector and past
+# ---- one grid sweep of map4 (2048 workgroups x 256 threads x 4 elements = 2 097 152: both of its loops wrap at 2 097 157)
+_EW_LENGTHS = (1, 3, 4, 1027, 2097157)
+_EW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+_EW_WORST = {}
+
+
+def _ew_input(n, salt=17):
+    """Uniform in (-6, 6); 0.0, -0.0, +-20, +-100 at the head (as many as half the length holds) and, for the long ones, -0.0, +-100 in the tail."""
+    from oracle.detdata import det_uniform
+    x = det_uniform((n,), salt) * 12.0 - 6.0
+    planted = torch.tensor([0.0, -0.0, 20.0, -20.0, 100.0, -100.0])
+    k = min(6, n // 2)
+    x[:k] = planted[:k]
+    if n >= 1027:
+        x[n - 3:] = torch.tensor([-0.0, 100.0, -100.0])
+    return x
+
+
+def _ew_check(got, ref64, ref_dev, act, out_dt, what):
+    """none / relu / leaky_relu: one product or a copy -- bit-exact against the fp64 value rounded to the output type.  sigmoid / tanh / elu:
+    rtol = atol = 1e-6 (the bar of test_colsum_cast_act), plus one rounding of a 16-bit output type."""
+    if act in ('none', 'relu', 'leaky_relu'):
+        assert torch.equal(got.cpu(), ref64.to(torch.float32).to(out_dt)), what
+        return
+    tol = 1e-6 + 1e-6 * ref_dev.abs()
+    if out_dt == torch.bfloat16:
+        tol = tol + 2.0 ** -8 * ref_dev.abs()
+    elif out_dt == torch.float16:
+        tol = tol + 2.0 ** -11 * ref_dev.abs() + (ref_dev.abs() < 2.0 ** -14).double() * 2.0 ** -24
+    err = (got.double() - ref_dev).abs()
+    frac = float((err / tol).max())
+    key = 'act %s %s -> %s: fraction of the bound' % (act, what.split()[0], str(out_dt).replace('torch.', ''))
+    _EW_WORST[key] = max(_EW_WORST.get(key, 0.0), frac)
+    if out_dt == torch.float32:
+        key = 'act %s %s -> float32: absolute error' % (act, what.split()[0])
+        _EW_WORST[key] = max(_EW_WORST.get(key, 0.0), float(err.max()))
+    assert frac <= 1.0, (what, frac)
+
+
+@pytest.mark.parametrize('act', ['none', 'relu', 'leaky_relu', 'sigmoid', 'tanh', 'elu'])
+def test_act_fwd_bwd_all_types_match_fp64(act):
+    """ops.act_fwd / ops.act_bwd against the fp64 activation (tests/loss_refs.py) of the same rounded inputs.  The backward's y is the fp64
+    activation output rounded to the input type, its dy uniform in (-6, 6)."""
+    import loss_refs as LR
+    from spatiotemporal_variable_separation_amd import ops
+    for n in _EW_LENGTHS:
+        x32, dy32 = _ew_input(n), _ew_input(n, 19).clamp(-6.0, 6.0)
+        for in_dt in _EW_DTYPES:
+            x, dy = x32.to(in_dt), dy32.to(in_dt)
+            y64 = LR.ACT_FWD[act](x.double())
+            y = y64.to(torch.float32).to(in_dt)
+            dz64 = dy.double() * LR.ACT_GRAD_FROM_OUT[act](y.double())
+            xd, dyd, yd, y64d, dz64d = x.cuda(), dy.cuda(), y.cuda(), y64.cuda(), dz64.cuda()
+            for out_dt in _EW_DTYPES:
+                what = '%s n %d %s -> %s' % (act, n, in_dt, out_dt)
+                got = ops.act_fwd(xd, act, out_dtype=out_dt)
+                assert got.dtype == out_dt and got.shape == x.shape
+                _ew_check(got, y64, y64d, act, out_dt, 'act_fwd ' + what)
+                gz = ops.act_bwd(dyd, yd, act, out_dtype=out_dt)
+                assert gz.dtype == out_dt and gz.shape == x.shape
+                _ew_check(gz, dz64, dz64d, act, out_dt, 'act_bwd ' + what)
+    for k in sorted(_EW_WORST):
+        if k.startswith('act %s ' % act):
+            print('worst', k, '%.4g' % _EW_WORST[k])
+
+
+def test_cast_all_type_pairs_bit_exact():
+    from spatiotemporal_variable_separation_amd import ops
+    for n in _EW_LENGTHS:
+        x32 = _ew_input(n)
+        for in_dt in _EW_DTYPES:
+            x = x32.to(in_dt)
+            xd = x.cuda()
+            for out_dt in _EW_DTYPES:
+                got = ops.cast(xd, out_dt)
+                assert got.dtype == out_dt and torch.equal(got.cpu(), x.to(out_dt)), (n, in_dt, out_dt)
+
+
 @pytest.mark.parametrize('precision', ['fp32', 'bf16'])
 @pytest.mark.parametrize('dims', [(5, 8, 16, 3, 6), (128, 32, 512, 3, 25), (37, 20, 512, 1, 15), (16, 4, 8, 1, 2), (3, 5, 8, 2, 1),
                                   (20, 16, 128, 2, 4), (48, 32, 256, 4, 7), (16, 32, 512, 3, 2)])
