@@ -350,6 +350,16 @@ int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int dig
 int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int views_per_object, int H, int W, int C, const int32_t* desc, int64_t rows,
                      int seq_len, void* out, int out_dtype, int32_t* bad, void* stream);
 
+/* One batch of windows gathered through a table from a timeline of frames resident in HBM (reference: data/taxibj.py:74-100
+ * `STMatrix.create_dataset` + `TaxiBJ.__getitem__`, for a whole batch of items).  frames [n_frames, frame_elems] fp32; first [n_windows]
+ * int32 = index of the frame at position 0 of each window; item_idx [rows] int32 = the windows of the batch (both tables on the device);
+ * step = +1 (forward windows) or -1 (newest frame first, as the reference stores TaxiBJ).  out [rows, seq_len, frame_elems] (fp32 or a
+ * 16-bit type): out[r, k, :] = frames[first[item_idx[r]] + k * step, :], the fp32 bits or their round-to-nearest-even 16-bit cast.
+ * A row whose item index is outside [0, n_windows), or whose window would leave [0, n_frames) at either end, reads nothing, is written
+ * as zeros and sets *bad = 1 (bad may be NULL); the launch never reads out of bounds.  At most 65535 rows per launch.              */
+int vs_gather_timeline(const float* frames, int64_t n_frames, int64_t frame_elems, const int32_t* first, int64_t n_windows, int step,
+                       const int32_t* item_idx, int64_t rows, int seq_len, void* out, int out_dtype, int32_t* bad, void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

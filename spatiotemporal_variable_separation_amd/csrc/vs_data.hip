@@ -1,5 +1,6 @@
-// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253) and the 3D
-// Chairs batch gather (reference: data/chairs.py:45-64, at the end of this file).
+// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253), the 3D
+// Chairs batch gather (reference: data/chairs.py:45-64) and the table-driven window gather of the TaxiBJ timeline (reference:
+// data/taxibj.py:74-100), both at the end of this file.
 //
 // The reference builds every training sequence on the host: per digit five draws from the global NumPy stream (digit index, start
 // position, speed), a trajectory of `seq_len` positions with elastic bounces off the frame borders computed in Python floats
@@ -162,7 +163,69 @@ __global__ __launch_bounds__(256) void chairs_gather_kernel(const unsigned char*
     }
 }
 
+// ---- table-driven window gather from a timeline of frames resident in HBM (data/taxibj.py of the reference: STMatrix.create_dataset) --
+// The reference materialises every window on the host; its windows are a SPARSE set (none crosses a missing slot, an incomplete day or a
+// file boundary) and each is stored NEWEST FRAME FIRST.  Here the normalised frames live in HBM once as fp32 [n_frames][frame] and a window
+// is an entry of a device table: first[w] = index of the frame at position 0; position k is frame first[w] + k * step, step = +1 or -1.
+// A batch is one launch driven by the sampler's item indices: out[r, k, :] = frames[first[item[r]] + k * step, :].
+// grid (chunks of a row, rows).  A row whose item index is outside [0, n_windows), or whose window would leave [0, n_frames) at either
+// end, reads nothing, is written as zeros and raises *bad (the condition is uniform over the workgroup).
+// frame % 4 == 0 and aligned bases (`vec`): a thread moves 16 B per load (a 16 B store, or 8 B of 16-bit output), and no vector crosses a
+// frame, so a wave reads 1 KiB contiguous inside one frame; other frame sizes go element by element.
+__global__ __launch_bounds__(256) void gather_timeline_kernel(const float* __restrict__ frames, int64_t n_frames, int64_t frame,
+                                                              const int* __restrict__ first, int64_t n_windows, int step,
+                                                              const int* __restrict__ item, int seq_len, void* out, int od, int vec, int* bad) {
+    const int64_t row = blockIdx.y;
+    const int idx = item[row];
+    bool ok = idx >= 0 && (int64_t)idx < n_windows;
+    int64_t f0 = 0;
+    if (ok) {
+        f0 = first[idx];
+        const int64_t last = f0 + (int64_t)(seq_len - 1) * step;
+        ok = f0 >= 0 && f0 < n_frames && last >= 0 && last < n_frames;
+    }
+    const int64_t total = (int64_t)seq_len * frame;
+    const int64_t obase = row * total;
+    if (!ok) {                                           // the row is written as zeros, nothing is read
+        if (bad && blockIdx.x == 0 && threadIdx.x == 0) *bad = 1;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) vs_st(out, od, obase + i, 0.f);
+        return;
+    }
+    if (vec) {
+        for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 1024) {
+            const int64_t k = i / frame, p = i - k * frame;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(frames + (f0 + k * step) * frame + p);
+            if (od == VS_F32) *reinterpret_cast<f32x4*>((float*)out + obase + i) = v;
+            else { const u16x4 w = {vs_f2h(v[0], od), vs_f2h(v[1], od), vs_f2h(v[2], od), vs_f2h(v[3], od)}; *reinterpret_cast<u16x4*>((unsigned short*)out + obase + i) = w; }
+        }
+        return;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t k = i / frame, p = i - k * frame;
+        vs_st(out, od, obase + i, frames[(f0 + k * step) * frame + p]);
+    }
+}
+
 }  // namespace
+
+extern "C" int vs_gather_timeline(const float* frames, int64_t n_frames, int64_t frame_elems, const int32_t* first, int64_t n_windows, int step,
+                                  const int32_t* item_idx, int64_t rows, int seq_len, void* out, int out_dtype, int32_t* bad, void* stream) {
+    VS_CHECK_ARG(frames && first && item_idx && out, "vs_gather_timeline: null pointer");
+    VS_CHECK_ARG(n_frames > 0 && frame_elems > 0 && n_windows > 0 && rows > 0, "vs_gather_timeline: sizes must be positive");
+    VS_CHECK_ARG(seq_len >= 1, "vs_gather_timeline: seq_len >= 1");
+    VS_CHECK_ARG(step == 1 || step == -1, "vs_gather_timeline: step must be +1 or -1 (got %d)", step);
+    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "vs_gather_timeline: bad out_dtype");
+    VS_CHECK_ARG(rows < 65536, "vs_gather_timeline: at most 65535 rows per launch");
+    // the vector form needs whole 4-element groups per frame and aligned vectors: frame starts are multiples of `frame_elems` from the bases
+    const int vec = frame_elems % 4 == 0 && (uintptr_t)frames % 16 == 0 && (uintptr_t)out % (out_dtype == VS_F32 ? 16 : 8) == 0;
+    const int64_t total = (int64_t)seq_len * frame_elems;
+    int64_t gx = vs_cdiv(total, vec ? 1024 : 256);
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(gather_timeline_kernel, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, frames, n_frames, frame_elems,
+                       (const int*)first, n_windows, step, (const int*)item_idx, seq_len, out, out_dtype, vec, (int*)bad);
+    VS_CHECK_LAUNCH("vs_gather_timeline");
+    return VS_OK;
+}
 
 extern "C" int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int views_per_object, int H, int W, int C, const int32_t* desc, int64_t rows,
                                 int seq_len, void* out, int out_dtype, int32_t* bad, void* stream) {

@@ -1931,6 +1931,31 @@ def chairs_gather(frames_u8, desc, seq_len, out_dtype=torch.float32, validate=Tr
     return out
 
 
+def gather_timeline(frames, first, item_idx, seq_len, step, out_dtype=torch.float32, validate=True):
+    """frames fp32 [n_frames, frame_elems] on the device, first int32 [n_windows] (frame at position 0 of every window), item_idx int32
+    [rows] -> [rows, seq_len, frame_elems] in `out_dtype`: out[r, k] = frames[first[item_idx[r]] + k * step], step +1 or -1
+    (vs_gather_timeline, one launch).  validate=True reads back the launch's error word (a host sync) and raises VarsepHipError for an
+    item outside the table or a window that leaves the timeline; validate=False keeps the call free of host syncs."""
+    require_cuda(frames, first, item_idx)
+    if (frames.dtype != torch.float32 or frames.dim() != 2 or first.dtype != torch.int32 or first.dim() != 1
+            or item_idx.dtype != torch.int32 or item_idx.dim() != 1):
+        raise _lib.VarsepHipError('gather_timeline: frames fp32 [n_frames, frame_elems], first int32 [n_windows] and item_idx int32 [rows] expected')
+    frames, first, item_idx = frames.contiguous(), first.contiguous(), item_idx.contiguous()
+    n_frames, frame = frames.shape
+    rows = item_idx.numel()
+    out = torch.empty((rows, max(int(seq_len), 0), frame), dtype=out_dtype, device=frames.device)
+    bad = torch.zeros((1,), dtype=torch.int32, device=frames.device) if validate else None
+    e0 = _pb()
+    check(_lib.load_library().vs_gather_timeline(frames.data_ptr(), n_frames, frame, first.data_ptr(), first.numel(), int(step), item_idx.data_ptr(),
+                                                 rows, int(seq_len), out.data_ptr(), _lib.code_of(out_dtype), _ptr(bad), stream_ptr()),
+          'vs_gather_timeline')
+    _pe(e0, 'vs_gather_timeline', nbytes=float(out.numel() * (4 + out.element_size())))
+    if validate and int(bad.item()):
+        raise _lib.VarsepHipError('gather_timeline: an item index is outside [0, %d) or a window leaves the %d frames of the timeline'
+                                  % (first.numel(), n_frames))
+    return out
+
+
 _MIXING = {'concat': 0, 'mul': 1}
 
 
