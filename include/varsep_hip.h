@@ -454,7 +454,8 @@ int vs_adam_step_increment(int32_t* step, void* stream);
  *                         shadow copies are written as `shadow_dtype` (VS_BF16 | VS_F16).  scale_state NULL = plain vs_adam_multi.
  * vs_adam_step_increment_scaled : the step count does not advance on a skipped step.
  * vs_loss_scale_update  : GradScaler.update(): S *= backoff and tracker = 0 on overflow, else tracker += 1 and S *= growth every
- *                         `growth_interval` clean steps; clears found_inf.                                                        */
+ *                         `growth_interval` clean steps -- only while the grown S is finite (the tracker restarts either way);
+ *                         clears found_inf.                                                                                       */
 int vs_check_finite_multi(int n_tensors, const void* const* grads, const int32_t* grad_dtype, const int64_t* numel, float* found_inf,
                           void* stream);
 int vs_adam_multi_scaled(int n_tensors, float* const* params, const void* const* grads, const int32_t* grad_dtype, float* const* exp_avg,

@@ -151,8 +151,12 @@ __global__ void loss_scale_update_kernel(float* state, float growth, float backo
         state[3] += 1.f;
     } else {
         const float t = state[2] + 1.f;
-        if (t >= (float)interval) { state[0] *= growth; state[2] = 0.f; }
-        else state[2] = t;
+        if (t >= (float)interval) {
+            // GradScaler grows only to a finite scale (a scale of inf would make every later step an overflow step); the tracker restarts either way
+            const float grown = state[0] * growth;
+            if ((__float_as_uint(grown) & 0x7f800000u) != 0x7f800000u) state[0] = grown;
+            state[2] = 0.f;
+        } else state[2] = t;
     }
     state[1] = 0.f;
 }
