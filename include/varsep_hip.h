@@ -378,6 +378,20 @@ int vs_frame_metrics_multi(const float* pred, const float* targets, int64_t batc
 /* x [n, channels, hw] (fp32 or a 16-bit type, widened to fp32) -> out [n, hw, channels] uint8 = (uint8)(x * 255.f): one fp32 multiply,
  * truncation toward zero (torch's `x.mul(255).byte()` for x in [0, 1]); values outside [0, 255] after the multiply saturate, NaN -> 0. */
 int vs_frames_to_u8_nhwc(const void* x, int x_dtype, int64_t n, int channels, int64_t hw, uint8_t* out, void* stream);
+/* The metrics of the SST evaluation script (test/sst/test.py:57-71).  pred, target [rows, T, H, W] fp32 are the NORMALISED forecasts and
+ * targets of `rows` windows; consts [n_days, 4] fp32 = (mu_norm, std_norm, mu_clim, std_clim) per day; day0 [rows] int32 = the day of each
+ * window's first target frame; zone [rows] int32 indexes zone_range [n_zones, 2] fp32 = (min, max).  The script multiplies [10, 1, 1]
+ * per-day constants into [1, 10, 1, H, W] frames, so every frame t meets the constants of every day c = day0 .. day0 + T - 1:
+ *   x'(t, c) = (x(t) * std_norm[c] + mu_norm[c]) * std_clim[c] + mu_clim[c]
+ *   mse [rows, T]:     mse[r, t]     = mean over c, H, W of (pred' - target')^2
+ *   ssim [rows, T, T]: ssim[r, t, c] = mean SSIM (11 x 11 Gaussian of `sigma`, valid windows, c1 = k1^2, c2 = k2^2: max_val 1) of
+ *                                      (x' - min) / (max - min); the diagonal ssim[r, t, t] pairs each frame with its own day.
+ * One workgroup per (row, t), one filter pass; either output may be NULL.  A row with day0 < 0, day0 + T > n_days or a zone outside
+ * [0, n_zones) reads no constants, writes zeros and sets *bad = 1 (bad may be NULL).  T <= 16; planes from 11 x 11 up to ~80 x 80
+ * (VS_ERR_UNSUPPORTED beyond).                                                                                                          */
+int vs_sst_frame_metrics(const float* pred, const float* target, int64_t rows, int T, int H, int W, const float* consts, int64_t n_days,
+                         const int32_t* day0, const int32_t* zone, const float* zone_range, int64_t n_zones, float k1, float k2, float sigma,
+                         float* mse, float* ssim, int32_t* bad, void* stream);
 
 /* Decoder input of the auto-encoding pair and of every rollout step in one launch (mlp_encdec.py:43-48 mixing applied at
  * model.py:74-83): z [B, 1+n, Cz] = mix(s [B, Cs], [t_rand [B, Ct] ; t_codes [B, n, Ct]]), mixing 0 = concat (Cz = Cs + Ct),

@@ -168,6 +168,7 @@ SIGNATURES = {
     'vs_moving_mnist_place': (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     'vs_frame_metrics_multi': (_i32, [_vp, _vp, _i64, _i32, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     'vs_frames_to_u8_nhwc': (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp]),
+    'vs_sst_frame_metrics': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     'vs_conv3_img16_supported': (_i32, [_i32] * 6),
     'vs_conv3_img16_splits': (_i32, [_i32] * 3),
     'vs_conv3_img16_packed_elems': (_sz, [_i32, _i32]),

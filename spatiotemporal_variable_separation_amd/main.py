@@ -23,7 +23,7 @@ def load_dataset(args, device=None):
     """`--data_dir synthetic` needs nothing.  The WaveEq sets (main.py:91-102 of the reference) are this package's own HBM-resident
     datasets (data/wave_eq.py: batches gathered on the device); Moving MNIST is generated on the device (data/moving_mnist.py); the
     3D Chairs views are decoded once and gathered on the device (data/chairs.py); the TaxiBJ frames live in HBM and a batch is gathered
-    through the window table (data/taxibj.py).  Nothing here imports the reference package."""
+    through the window table (data/taxibj.py); the normalised SST days of all zones likewise (data/sst.py).  Nothing here imports the reference package."""
     if args.data_dir == 'synthetic':
         return SyntheticSequences(args.data, args.nt_cond, args.nt_pred, length=args.synthetic_len,
                                   seed=args.seed or 1234, n_wave_points=args.n_wave_points)
@@ -43,10 +43,13 @@ def load_dataset(args, device=None):
     if args.data == 'taxibj' and device is not None and torch.device(device).type == 'cuda':
         from .data.taxibj import TaxiBJ                             # main.py:82-86 of the reference; frames resident in HBM
         return TaxiBJ.make_datasets(args.data_dir, len_closeness=args.nt_cond + args.nt_pred, nt_cond=args.nt_cond, device=device)[0]
+    if args.data == 'sst' and device is not None and torch.device(device).type == 'cuda':
+        from .data.sst import SST                                   # main.py:87-89 of the reference; normalised days resident in HBM
+        return SST(args.data_dir, args.nt_cond, args.nt_pred, True, zones=args.zones, device=device)
     raise NotImplementedError(
-        'dataset %r: only the synthetic batches (--data_dir synthetic), the WaveEq sets, Moving MNIST, the 3D Chairs and TaxiBJ are built '
-        'into this package; the SST loader of the reference is a host-side file reader (netCDF4) outside the '
-        'MI355X hot path -- wrap it in any torch Dataset yielding (cond, target) and call train() directly' % args.data)
+        'dataset %r: only the synthetic batches (--data_dir synthetic), the WaveEq sets, Moving MNIST, the 3D Chairs, TaxiBJ and SST are '
+        'built into this package, each on an MI355X device -- wrap anything else in a torch Dataset yielding (cond, target) and call '
+        'train() directly' % args.data)
 
 
 def main(argv=None):

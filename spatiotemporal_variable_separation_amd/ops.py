@@ -2156,6 +2156,35 @@ def frame_metrics_multi(pred, targets, max_val=1.0, k1=0.01, k2=0.03, sigma=1.5,
     return mse, ssim
 
 
+def sst_frame_metrics(pred, target, consts, day0, zone, zone_range, k1=0.01, k2=0.03, sigma=1.5, validate=True):
+    """The metrics of the SST evaluation script (test/sst/test.py:57-71) in one launch (vs_sst_frame_metrics).  pred, target fp32
+    [rows, T, H, W]: normalised forecasts and targets; consts fp32 [n_days, 4] = (mu_norm, std_norm, mu_clim, std_clim); day0, zone int32
+    [rows]: day of the first target frame, position in zone_range fp32 [n_zones, 2] = (min, max) -> (mse [rows, T], ssim [rows, T, T]),
+    where ssim[r, t, c] pairs frame t with the constants of day day0 + c.  validate=True reads back the launch's error word (a host sync)
+    and raises VarsepHipError for a row whose days leave `consts` or whose zone is out of range (such a row is written as zeros);
+    validate=False keeps the call free of host syncs."""
+    require_cuda(pred, target, consts, day0, zone, zone_range)
+    if (pred.dtype != torch.float32 or target.dtype != torch.float32 or pred.dim() != 4 or pred.shape != target.shape
+            or consts.dtype != torch.float32 or consts.dim() != 2 or consts.shape[1] != 4
+            or zone_range.dtype != torch.float32 or zone_range.dim() != 2 or zone_range.shape[1] != 2
+            or day0.dtype != torch.int32 or zone.dtype != torch.int32 or day0.shape != (pred.shape[0],) or zone.shape != (pred.shape[0],)):
+        raise _lib.VarsepHipError('sst_frame_metrics: pred / target fp32 [rows, T, H, W], consts fp32 [n_days, 4], day0 / zone int32 [rows] and '
+                                  'zone_range fp32 [n_zones, 2] expected')
+    pred, target, consts, day0, zone, zone_range = (x.contiguous() for x in (pred, target, consts, day0, zone, zone_range))
+    rows, T, H, W = pred.shape
+    mse = torch.empty((rows, T), dtype=torch.float32, device=pred.device)
+    ssim = torch.empty((rows, T, T), dtype=torch.float32, device=pred.device)
+    bad = torch.zeros((1,), dtype=torch.int32, device=pred.device) if validate else None
+    check(_lib.load_library().vs_sst_frame_metrics(pred.data_ptr(), target.data_ptr(), rows, T, H, W, consts.data_ptr(), consts.shape[0],
+                                                   day0.data_ptr(), zone.data_ptr(), zone_range.data_ptr(), zone_range.shape[0], float(k1),
+                                                   float(k2), float(sigma), mse.data_ptr(), ssim.data_ptr(), _ptr(bad), stream_ptr()),
+          'vs_sst_frame_metrics')
+    if validate and int(bad.item()):
+        raise _lib.VarsepHipError('sst_frame_metrics: a row names days outside the %d of `consts` or a zone outside [0, %d)'
+                                  % (consts.shape[0], zone_range.shape[0]))
+    return mse, ssim
+
+
 def moving_mnist_place(digits, positions, desc, seq_len, frame_size, out_dtype=torch.float32, validate=True):
     """Videos [V, seq_len, 1, F, F] with the digits `desc[v, 1 + i]` at `positions[t, desc[v, 0], i]` (vs_moving_mnist_place).
     digits uint8 [N, h, w], positions int32 [T >= seq_len, n_seq, nd, 2], desc int32 [V, 1 + nd], all on the device.

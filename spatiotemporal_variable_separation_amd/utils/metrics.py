@@ -1,5 +1,6 @@
 """Evaluation metrics of the reference's test scripts on the device (reference: var_sep/test/utils.py:19-24 `_ssim_wrapper`,
-var_sep/utils/ssim.py:81-149 `ssim_loss`, var_sep/test/mnist/test.py:136-142 mse / psnr / ssim per sample)."""
+var_sep/utils/ssim.py:81-149 `ssim_loss`, var_sep/test/mnist/test.py:136-142 mse / psnr / ssim per sample,
+var_sep/test/sst/test.py:57-71 the SST script's MSE / SSIM in original units)."""
 import torch
 
 from .. import ops
@@ -38,3 +39,17 @@ def frame_metrics(pred, target):
     """{'mse', 'psnr', 'ssim'} per sample as test/mnist/test.py:136-142 computes them from [B, nt, C, H, W] predictions."""
     mse, ssim = ops.frame_metrics(pred, target, max_val=1.0)
     return {'mse': mse.mean(2).mean(1), 'psnr': (10 * torch.log10(1 / mse)).mean(2).mean(1), 'ssim': ssim.mean(2).mean(1)}
+
+
+def sst_metrics(pred, target, consts, day0, zone, zone_range, validate=True):
+    """(mse [B, nt], ssim [B, nt, nt]) of test/sst/test.py:57-71 from NORMALISED forecasts and targets [B, nt, 1, H, W] (or [B, nt, H, W]).
+    The script multiplies its [nt, 1, 1] per-day constants into [1, nt, 1, H, W] frames; broadcasting turns the channel axis into a second
+    day axis, so every frame t is de-normalised with the constants of every target day c: `mse` averages over c as well, and `ssim[b, t, c]`
+    is the SSIM of that pair after the rescale to the zone's (min, max).  The paper's numbers are means over all pairs; the diagonal
+    `ssim[:, t, t]` is the pairing of each frame with its own day.  consts / day0 / zone / zone_range as `data.sst.SST` holds and yields
+    them; one launch (ops.sst_frame_metrics), no [B, nt, nt, H, W] tensor."""
+    if pred.dim() == 5:
+        if pred.shape[2] != 1:
+            raise ValueError('sst_metrics: single-channel frames expected (got %s)' % (tuple(pred.shape),))
+        pred, target = pred[:, :, 0], target[:, :, 0]
+    return ops.sst_frame_metrics(pred.float(), target.float(), consts, day0, zone, zone_range, validate=validate)
