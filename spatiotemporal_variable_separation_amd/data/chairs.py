@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._lib import VarsepHipError
+from .device import DeviceSet, optional_module, require_gpu
 
 MAX_DECODE_WORKERS = 16          # a fixed cap: the machine's CPU count says nothing about the share this process may use
 
@@ -95,11 +95,7 @@ def read_png_rgb8(path):
 
 
 def _pil_image():
-    try:
-        from PIL import Image
-        return Image
-    except ImportError:
-        return None
+    return optional_module('PIL.Image')
 
 
 def read_frame(path, size=64, image_module=None):
@@ -120,11 +116,10 @@ def read_frame(path, size=64, image_module=None):
     return arr
 
 
-class Chairs:
+class Chairs(DeviceSet):
     """`Chairs(train, data_root, nt_cond, seq_len, image_size)` (chairs.py:23-67) with the split's views on `device`."""
 
     max_length = 62
-    device_resident = True
 
     def __init__(self, train, data_root, nt_cond, seq_len=15, image_size=64, device=None):
         self.train, self.nt_cond = train, nt_cond
@@ -135,10 +130,7 @@ class Chairs:
         if image_size != 64:                             # chairs.py:31
             raise ValueError('the rendered chairs are 64 x 64 images')
         self.seq_len, self.image_size = seq_len, image_size
-        device = torch.device(device if device is not None else 'cuda')
-        if device.type != 'cuda':
-            raise VarsepHipError('the HBM-resident Chairs set needs an MI355X device; there is no CPU fallback')
-        self.device = device
+        self.device = device = require_gpu('Chairs', device)
         self.data_root = os.path.join(data_root, 'rendered_chairs')
         self.sequences = sorted(os.listdir(self.data_root))
         self.sequences.remove('all_chair_names.mat')
@@ -203,7 +195,3 @@ class Chairs:
             item_idx = item_idx.cpu().tolist()
         x = self.gather(self.descriptors(item_idx), out_dtype)
         return x[:, :self.nt_cond], x[:, self.nt_cond:]
-
-    def __getitem__(self, index):
-        cond, target = self.batch([int(index)])
-        return cond[0], target[0]

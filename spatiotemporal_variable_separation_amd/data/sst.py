@@ -18,8 +18,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
-from .._lib import VarsepHipError
+from .device import TimelineSet, read_optional, require_gpu
 
 VAR_NAMES = ('thetao', 'daily_mean', 'daily_std')
 NC_NAME = 'data_{}.nc'
@@ -29,29 +28,16 @@ CONVERSION_HINT = ("import netCDF4, numpy as np; v = netCDF4.Dataset('{nc}', 'r'
                    "np.savez('{npz}', thetao=v['thetao'][:].data, daily_mean=v['daily_mean'][:].data, daily_std=v['daily_std'][:].data)")
 
 
-def _netcdf4():
-    try:
-        import netCDF4
-        return netCDF4
-    except ImportError:
-        return None
-
-
 def extract_data(data_dir, zone):
     """{name: array} of one zone: `data_{zone}.nc` through netCDF4 when that module imports and the file exists -- the raw `.data` of the
     masked arrays, as sst.py:24-29 takes it -- else `data_{zone}.npz` with the same three arrays under the same names."""
-    nc_path = os.path.join(data_dir, NC_NAME.format(zone))
-    npz_path = os.path.join(data_dir, NPZ_NAME.format(zone))
-    netCDF4 = _netcdf4()
-    if netCDF4 is not None and os.path.isfile(nc_path):
-        loaded_file = netCDF4.Dataset(nc_path, 'r')
+    def read_nc(netCDF4, path):
+        loaded_file = netCDF4.Dataset(path, 'r')
         return {var: np.asarray(loaded_file.variables[var][:].data) for var in VAR_NAMES}
-    if os.path.isfile(npz_path):
-        with np.load(npz_path) as z:
-            return {var: z[var] for var in VAR_NAMES}
-    why = 'is missing' if not os.path.isfile(nc_path) else 'cannot be read: netCDF4 does not import here'
-    raise ValueError('%s %s, and there is no %s.  Where netCDF4 exists, convert each zone with\n%s'
-                     % (nc_path, why, npz_path, CONVERSION_HINT.format(nc=NC_NAME.format(zone), npz=NPZ_NAME.format(zone))))
+
+    return read_optional('netCDF4', os.path.join(data_dir, NC_NAME.format(zone)), os.path.join(data_dir, NPZ_NAME.format(zone)),
+                         read_nc, lambda z: {var: z[var] for var in VAR_NAMES}, 'zone',
+                         CONVERSION_HINT.format(nc=NC_NAME.format(zone), npz=NPZ_NAME.format(zone)))
 
 
 def build_zones(data_dir, zones):
@@ -112,47 +98,30 @@ def item_table(n_zones, L, nt_cond, nt_pred, train):
     return table.astype(np.int32), len_
 
 
-class SST:
+class SST(TimelineSet):
     """One half (train or test) of the SST windows of `zones`, with the reference's signature plus `device`.  Items are
     (cond [nt_cond, 1, 64, 64], target [nt_pred, 1, 64, 64]) as sst.py:83-99 yields them.  `consts` [Z * L, 4] and `zone_range` [Z, 2]
     (see build_zones) are on the device beside `frames`; with eval=True a batch carries, per row, the index into `consts` of its first
     target day and the position of its zone in `zone_range`."""
 
-    device_resident = True
     step = 1
     var_names = list(VAR_NAMES)
 
     def __init__(self, data_dir, nt_cond, nt_pred, train, zones=range(1, 30), eval=False, device=None):
-        device = torch.device(device if device is not None else 'cuda')
-        if device.type != 'cuda':
-            raise VarsepHipError('the HBM-resident SST set needs an MI355X device; there is no CPU fallback')
+        device = require_gpu('SST', device)
         self.data_dir, self.zones, self.train, self.eval = data_dir, list(zones), train, eval
-        self.nt_cond, self.nt_pred, self.zone_size = nt_cond, nt_pred, ZONE_SIZE
+        self.nt_pred, self.zone_size = nt_pred, ZONE_SIZE
         frames, consts, zone_range, self.L = build_zones(data_dir, self.zones)
         first, self.len_ = item_table(len(self.zones), self.L, nt_cond, nt_pred, train)
-        self.frame_shape = (1, ZONE_SIZE, ZONE_SIZE) if frames.shape[1] == ZONE_SIZE * ZONE_SIZE else (frames.shape[1],)
-        self.frames = torch.from_numpy(frames).to(device)
+        super().__init__(torch.from_numpy(frames).to(device), torch.from_numpy(first).to(device), nt_cond + nt_pred, nt_cond,
+                         (1, ZONE_SIZE, ZONE_SIZE) if frames.shape[1] == ZONE_SIZE * ZONE_SIZE else (frames.shape[1],))
         self.consts = torch.from_numpy(consts).to(device)
         self.zone_range = torch.from_numpy(zone_range).to(device)
-        self.first = torch.from_numpy(first).to(device)
-
-    def __len__(self):
-        return len(self.zones) * self.len_
 
     def batch(self, item_idx, out_dtype=torch.float32):
-        """item_idx: list of ints, range-checked here (IndexError), or an int32 device tensor [B], which goes to the kernel as it is and is
-        checked there -> (cond [B, nt_cond, 1, 64, 64], target [B, nt_pred, 1, 64, 64]), one launch; with eval=True also (day0 [B], zone [B])
-        int32 on the device."""
-        on_device = isinstance(item_idx, torch.Tensor)
-        if not on_device:
-            idx = np.asarray(list(item_idx), dtype=np.int64).reshape(-1)
-            if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self):
-                raise IndexError('an item index is outside the %d windows of the set' % len(self))
-            item_idx = torch.from_numpy(idx.astype(np.int32)).to(self.frames.device, non_blocking=True)
-        seq_len = self.nt_cond + self.nt_pred
-        x = ops.gather_timeline(self.frames, self.first, item_idx, seq_len, self.step, out_dtype, validate=on_device)
-        x = x.view((x.shape[0], seq_len) + self.frame_shape)
-        cond, target = x[:, :self.nt_cond], x[:, self.nt_cond:]
+        """As TimelineSet.batch; with eval=True also (day0 [B], zone [B]) int32 on the device."""
+        item_idx, validate = self._device_index(item_idx)
+        cond, target = self._gather(item_idx, validate, out_dtype)
         if not self.eval:
             return cond, target
         day0 = self.first[item_idx.long()] + self.nt_cond
@@ -163,8 +132,7 @@ class SST:
         """(cond, target), and with eval=True the reference's seven values: the constants of the target days as [nt_pred, 1, 1] device
         tensors and the zone's name (sst.py:91-99)."""
         if not self.eval:
-            cond, target = self.batch([int(index)])
-            return cond[0], target[0]
+            return super().__getitem__(index)
         cond, target, day0, zone = self.batch([int(index)])
         d0 = int(day0[0])
         mu_norm, std_norm, mu_clim, std_clim = (self.consts[d0:d0 + self.nt_pred, k].reshape(-1, 1, 1) for k in range(4))

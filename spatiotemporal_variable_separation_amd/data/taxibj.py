@@ -18,8 +18,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
-from .._lib import VarsepHipError
+from .device import TimelineSet, read_optional, require_gpu
 
 YEARS = (13, 14, 15, 16)
 H5_NAME = 'BJ{}_M32x32_T30_InOut.h5'
@@ -50,32 +49,20 @@ class MinMaxNormalization:
         return 1. * X * (self._max - self._min) + self._min
 
 
-def _h5py():
-    try:
-        import h5py
-        return h5py
-    except ImportError:
-        return None
+def _read_h5(h5py, path):
+    f = h5py.File(path, 'r')
+    data = f['data'][()]
+    timestamps = f['date'][()]
+    f.close()
+    return data, timestamps
 
 
 def load_stdata(data_dir, year):
     """(data [N, flows, 32, 32], timestamps [N] of bytes or str) of one year: the .h5 file through h5py when that module imports and the
     file exists (taxibj.py:103-108), else the .npz file with the same two arrays under the keys `data` and `date`."""
-    h5_path = os.path.join(data_dir, H5_NAME.format(year))
-    npz_path = os.path.join(data_dir, NPZ_NAME.format(year))
-    h5py = _h5py()
-    if h5py is not None and os.path.isfile(h5_path):
-        f = h5py.File(h5_path, 'r')
-        data = f['data'][()]
-        timestamps = f['date'][()]
-        f.close()
-    elif os.path.isfile(npz_path):
-        with np.load(npz_path) as z:
-            data, timestamps = z['data'], z['date']
-    else:
-        why = 'is missing' if not os.path.isfile(h5_path) else 'cannot be read: h5py does not import here'
-        raise ValueError('%s %s, and there is no %s.  Where h5py exists, convert each year with\n%s'
-                         % (h5_path, why, npz_path, CONVERSION_HINT.format(h5=H5_NAME.format(year), npz=NPZ_NAME.format(year))))
+    data, timestamps = read_optional('h5py', os.path.join(data_dir, H5_NAME.format(year)), os.path.join(data_dir, NPZ_NAME.format(year)),
+                                     _read_h5, lambda z: (z['data'], z['date']), 'year',
+                                     CONVERSION_HINT.format(h5=H5_NAME.format(year), npz=NPZ_NAME.format(year)))
     data = np.asarray(data)
     timestamps = list(np.asarray(timestamps).tolist())
     if len(data) != len(timestamps):
@@ -174,24 +161,21 @@ def build_windows(data_dir, T=48, nb_flow=2, len_closeness=None, len_test=48 * 7
     return frames, first.astype(np.int32), n_train, mmn
 
 
-class TaxiBJ:
+class TaxiBJ(TimelineSet):
     """One half (train or test) of the TaxiBJ windows: `frames` fp32 [F, elems] on the device (shared by both halves), `first` its own
     int32 window table on the device.  Items are (cond [nt_cond, flows, 32, 32], target [len_closeness - nt_cond, ...]), newest frame
     first, as taxibj.py:263-265 yields them."""
 
-    device_resident = True
     step = -1
 
     def __init__(self, frames, first, nt_cond, len_closeness, mmn, frame_shape):
-        self.frames, self.first = frames, first
-        self.nt_cond, self.len_closeness, self.mmn, self.frame_shape = nt_cond, len_closeness, mmn, tuple(frame_shape)
+        super().__init__(frames, first, len_closeness, nt_cond, frame_shape)
+        self.len_closeness, self.mmn = len_closeness, mmn
 
     @classmethod
     def make_datasets(cls, data_dir, T=48, nb_flow=2, len_closeness=None, len_test=48 * 7 * 4, nt_cond=4, device=None):
         """-> (train, test), as taxibj.py:217-261, on `device`."""
-        device = torch.device(device if device is not None else 'cuda')
-        if device.type != 'cuda':
-            raise VarsepHipError('the HBM-resident TaxiBJ set needs an MI355X device; there is no CPU fallback')
+        device = require_gpu('TaxiBJ', device)
         frames, first, n_train, mmn = build_windows(data_dir, T, nb_flow, len_closeness, len_test)
         if not 0 <= nt_cond <= len_closeness:
             raise ValueError('nt_cond %d exceeds the %d frames of an item' % (nt_cond, len_closeness))
@@ -199,23 +183,3 @@ class TaxiBJ:
         frames = torch.from_numpy(frames).to(device)
         halves = [torch.from_numpy(np.ascontiguousarray(part)).to(device) for part in (first[:n_train], first[n_train:])]
         return tuple(cls(frames, part, nt_cond, int(len_closeness), mmn, shape) for part in halves)
-
-    def __len__(self):
-        return self.first.numel()
-
-    def batch(self, item_idx, out_dtype=torch.float32):
-        """item_idx: list of ints, range-checked here (IndexError), or an int32 device tensor [B], which goes to the kernel as it is and is
-        checked there -> (cond [B, nt_cond, flows, 32, 32], target [B, len_closeness - nt_cond, flows, 32, 32]), one launch."""
-        on_device = isinstance(item_idx, torch.Tensor)
-        if not on_device:
-            idx = np.asarray(list(item_idx), dtype=np.int64).reshape(-1)
-            if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self):
-                raise IndexError('an item index is outside the %d windows of the set' % len(self))
-            item_idx = torch.from_numpy(idx.astype(np.int32)).to(self.frames.device, non_blocking=True)
-        x = ops.gather_timeline(self.frames, self.first, item_idx, self.len_closeness, self.step, out_dtype, validate=on_device)
-        x = x.view((x.shape[0], self.len_closeness) + self.frame_shape)
-        return x[:, :self.nt_cond], x[:, self.nt_cond:]
-
-    def __getitem__(self, index):
-        cond, target = self.batch([int(index)])
-        return cond[0], target[0]

@@ -7,7 +7,7 @@ ONE gather launch (`vs_gather_windows`) driven by the sampler's item indices.  I
 normalisation and the pixel subset of `WaveEqPartial` follow the reference line by line -- including its two quirks: the
 train/test split reads the first integer of the file's FULL PATH (wave_eq.py:25-26, 43-46), and `__len__` counts
 windows with the frame HEIGHT where `__getitem__` uses the sequence length (wave_eq.py:62-65) -- so that a seeded sampler
-visits the same windows in the same order.  `DeviceBatchLoader` replaces `DataLoader(dataset, shuffle=True)` (main.py:113):
+visits the same windows in the same order.  `DeviceBatchLoader` (data/device.py) replaces `DataLoader(dataset, shuffle=True)` (main.py:113):
 the index stream comes from torch's own RandomSampler / BatchSampler, only the 4-byte indices cross PCIe.
 """
 import os
@@ -15,10 +15,9 @@ import re
 
 import numpy as np
 import torch
-from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
 
 from .. import ops
-from .._lib import VarsepHipError
+from .device import DeviceSet, require_gpu
 
 
 def extract_id(string):
@@ -26,17 +25,12 @@ def extract_id(string):
     return int(re.findall(r'\d+', string)[0])
 
 
-class WaveEq:
+class WaveEq(DeviceSet):
     """`WaveEq(data_dir, nt_cond, seq_len, train, downsample)` (wave_eq.py:29-72) with the data on `device`."""
-
-    device_resident = True
 
     def __init__(self, data_dir, nt_cond, seq_len, train, downsample, device=None):
         self.nt_cond, self.seq_len, self.train, self.downsample = nt_cond, seq_len, train, downsample
-        device = torch.device(device if device is not None else 'cuda')
-        if device.type != 'cuda':
-            raise VarsepHipError('the HBM-resident WaveEq set needs an MI355X device; there is no CPU fallback '
-                                 '(tests use oracle/wave_data_ref.py for CPU results)')
+        device = require_gpu('WaveEq', device, hint=' (tests use oracle/wave_data_ref.py for CPU results)')
         base_path = os.path.join(data_dir, 'data')
         files = [os.path.join(base_path, f) for f in os.listdir(base_path)]
         max_seq = int(0.8 * len(files))
@@ -78,10 +72,6 @@ class WaveEq:
         x = x.view((x.shape[0], self.seq_len, 1) + tuple(tail))
         return x[:, :self.nt_cond], x[:, self.nt_cond:]
 
-    def __getitem__(self, idx):
-        cond, target = self.batch([int(idx)])
-        return cond[0], target[0]
-
 
 class WaveEqPartial(WaveEq):
     """`WaveEqPartial(..., n_pixels)` (wave_eq.py:75-90): every frame reduced to n_pixels fixed (row, column) positions."""
@@ -100,25 +90,3 @@ class WaveEqPartial(WaveEq):
             raise IndexError('pixel table addresses positions outside the %dx%d frames' % (H, W))
         self._pixels = torch.from_numpy((rows * W + cols).astype(np.int32)).to(self.all_data.device)
 
-
-class DeviceBatchLoader:
-    """`DataLoader(dataset, batch_size, shuffle=True)` of main.py:113 for a device-resident set: same sampler classes (so the
-    same seeded index stream and the same ragged last batch), batches gathered by one launch instead of worker processes."""
-
-    def __init__(self, dataset, batch_size, shuffle=True, drop_last=False, sampler=None, generator=None, out_dtype=torch.float32):
-        assert getattr(dataset, 'device_resident', False), 'DeviceBatchLoader serves HBM-resident datasets'
-        self.dataset, self.batch_size, self.drop_last, self.out_dtype = dataset, batch_size, drop_last, out_dtype
-        if sampler is None:
-            sampler = RandomSampler(dataset, generator=generator) if shuffle else SequentialSampler(dataset)
-        self.sampler, self.generator = sampler, generator
-        self.batch_sampler = BatchSampler(sampler, batch_size, drop_last)
-
-    def __len__(self):
-        return len(self.batch_sampler)
-
-    def __iter__(self):
-        # a DataLoader iterator draws its base seed from the RNG before the sampler draws its own (torch/utils/data/dataloader.py,
-        # _BaseDataLoaderIter.__init__); consume the same draw so that a seeded epoch visits the same items
-        torch.empty((), dtype=torch.int64).random_(generator=self.generator)
-        for items in self.batch_sampler:
-            yield self.dataset.batch(items, self.out_dtype)

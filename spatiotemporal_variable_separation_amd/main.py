@@ -27,23 +27,24 @@ def load_dataset(args, device=None):
     if args.data_dir == 'synthetic':
         return SyntheticSequences(args.data, args.nt_cond, args.nt_pred, length=args.synthetic_len,
                                   seed=args.seed or 1234, n_wave_points=args.n_wave_points)
-    if args.data in ('wave', 'wave_partial') and device is not None and torch.device(device).type == 'cuda':
+    on_gpu = device is not None and torch.device(device).type == 'cuda'
+    if args.data in ('wave', 'wave_partial') and on_gpu:
         from .data.wave_eq import WaveEq, WaveEqPartial
         if args.data == 'wave':
             return WaveEq(args.data_dir, args.nt_cond, args.nt_cond + args.nt_pred, True, args.downsample, device=device)
         return WaveEqPartial(args.data_dir, args.nt_cond, args.nt_cond + args.nt_pred, True, args.downsample, args.n_wave_points,
                              device=device)
-    if args.data == 'mnist' and device is not None and torch.device(device).type == 'cuda':
+    if args.data == 'mnist' and on_gpu:
         from .data.moving_mnist import MovingMNIST                  # sequences generated on the device (data/moving_mnist.py)
         return MovingMNIST.make_dataset(args.data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, True,
                                         device=device, seed=args.seed)
-    if args.data == 'chairs' and device is not None and torch.device(device).type == 'cuda':
+    if args.data == 'chairs' and on_gpu:
         from .data.chairs import Chairs                             # main.py:77-79 of the reference; views resident in HBM
         return Chairs(True, args.data_dir, args.nt_cond, seq_len=args.nt_cond + args.nt_pred, device=device)
-    if args.data == 'taxibj' and device is not None and torch.device(device).type == 'cuda':
+    if args.data == 'taxibj' and on_gpu:
         from .data.taxibj import TaxiBJ                             # main.py:82-86 of the reference; frames resident in HBM
         return TaxiBJ.make_datasets(args.data_dir, len_closeness=args.nt_cond + args.nt_pred, nt_cond=args.nt_cond, device=device)[0]
-    if args.data == 'sst' and device is not None and torch.device(device).type == 'cuda':
+    if args.data == 'sst' and on_gpu:
         from .data.sst import SST                                   # main.py:87-89 of the reference; normalised days resident in HBM
         return SST(args.data_dir, args.nt_cond, args.nt_pred, True, zones=args.zones, device=device)
     raise NotImplementedError(
@@ -107,7 +108,7 @@ def main(argv=None):
         epoch_len = int(os.environ['VARSEP_MMNIST_EPOCH_LEN']) if os.environ.get('VARSEP_MMNIST_EPOCH_LEN') else None   # default 200000 (reference)
         train_loader = DeviceMovingLoader(train_set, args.batch_size, world=world, epoch_len=epoch_len)
     elif getattr(train_set, 'device_resident', False):
-        from .data.wave_eq import DeviceBatchLoader                # same sampler stream as the DataLoader below, one gather launch per batch
+        from .data.device import DeviceBatchLoader                 # same sampler stream as the DataLoader below, one gather launch per batch
         train_loader = DeviceBatchLoader(train_set, args.batch_size, shuffle=sampler is None, sampler=sampler)
     else:
         train_loader = DataLoader(train_set, batch_size=args.batch_size, pin_memory=True, shuffle=sampler is None,

@@ -8,15 +8,11 @@ the forecast is scored against the drawn object seen along the test video's view
 content and ground-truth videos of a batch come from one gather launch, the metrics run on the device (vs_frame_metrics_multi) and every
 saved array is converted to uint8 on the device (vs_frames_to_u8_nhwc).  There is no CPU mode: --device is required.
 """
-import os
-
 import numpy as np
 import torch
 
 from ...data.chairs import Chairs
-from ...utils.helper import load_json
-from ..mnist.test_disentanglement import best_of_permutations
-from ..utils import add_precision_flag, base_parser, load_model, print_results, seed_all, setup_device, to_host_u8
+from ..utils import add_precision_flag, base_parser, load_model, load_xp_config, run_content_swap, seed_all, setup_device
 
 
 class SwapDataset(Chairs):
@@ -51,22 +47,26 @@ class SwapDataset(Chairs):
         content, gt = v[:B], v[B:].unsqueeze(1)
         return content[:, :self.nt_cond], content[:, self.nt_cond:], gt[:, :, :self.nt_cond], gt[:, :, self.nt_cond:]
 
-    def __getitem__(self, index):
-        return tuple(t[0] for t in self.batch([int(index)]))
-
 
 def load_dataset(args, train=False, device='cuda'):
     return Chairs(train, args.data_dir, args.nt_cond, seq_len=args.nt_cond + args.nt_pred, device=device)
 
 
+def swap_batches(test_dataset, swap_dataset, batch_size):
+    """(x_cond, x_gt_swap, x_swap_cond, x_swap_target) per batch.  Both of the reference's loaders are sequential with the same batch size
+    over sets of the same length: batch k of either holds items [k * batch_size, (k + 1) * batch_size), the last one ragged in both."""
+    for start in range(0, len(test_dataset), batch_size):
+        items = range(start, min(start + batch_size, len(test_dataset)))
+        # reference quirk: the swap item's own target frames (`x_target`) are never used
+        x_cond, _, _, x_gt_swap = swap_dataset.batch(items)
+        x_swap_cond, x_swap_target = test_dataset.batch(items)
+        yield x_cond, x_gt_swap, x_swap_cond, x_swap_target
+
+
 def main(args):
     device = setup_device(args)
     seed_all(args.test_seed)
-    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
-    xp_config.device = device
-    xp_config.data_dir = args.data_dir
-    xp_config.xp_dir = args.xp_dir
-    xp_config.nt_pred = args.nt_pred
+    xp_config = load_xp_config(args, device, args.nt_pred)
     xp_config.n_object = 1           # reference quirk: forced to 1 whatever params.json says (one "permutation" is scored)
 
     print('Loading data...')
@@ -78,51 +78,14 @@ def main(args):
 
     print('Generating samples...')
     torch.set_grad_enabled(False)
-    nt_test = xp_config.nt_cond + args.nt_pred
-    gt_swap, content_swap, cond_swap, target_swap = [], [], [], []
-    results = {'mse': [], 'psnr': [], 'ssim': []}
-    # both of the reference's loaders are sequential with the same batch size over sets of the same length: batch k of either holds
-    # items [k * batch_size, (k + 1) * batch_size), the last one ragged in both
-    for start in range(0, len(test_dataset), args.batch_size):
-        items = range(start, min(start + args.batch_size, len(test_dataset)))
-        # reference quirk: the swap item's own target frames (`x_target`) are never used
-        x_cond, _, _, x_gt_swap = swap_dataset.batch(items)
-        x_swap_cond, x_swap_target = test_dataset.batch(items)
-
-        # Extraction of S
-        _, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
-
-        # Content swap (reference quirk kept: `cond_swap_test` holds the content video's conditioning frames `x_cond`, not the swap
-        # video's `x_swap_cond`)
-        cond_swap.append(to_host_u8(x_cond))
-        target_swap.append(to_host_u8(x_swap_target))
-        x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
-        x_swap_pred = x_swap_pred[:, xp_config.nt_cond:].float().contiguous()
-        content_swap.append(to_host_u8(x_swap_pred))
-        # reference quirk: `gt_swap` is `x_gt_swap[:, 0]`, the first (and, with n_object = 1, only) candidate
-        gt_swap.append(to_host_u8(x_gt_swap[:, 0]))
-
-        # Pixelwise quantitative eval: P = 1 candidate per sample, so the best-of-permutations min / max are the values themselves
-        metrics_batch = best_of_permutations(x_swap_pred, x_gt_swap.float())
-        for name in results:
-            results[name].append(metrics_batch[name].cpu())
-
-    results = print_results(results)
-
-    np.savez_compressed(os.path.join(args.xp_dir, 'results_swap.npz'), **results)
-    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap_gt.npz'), gt_swap=torch.cat(gt_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap_test.npz'), content_swap=torch.cat(content_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'cond_swap_test.npz'), cond_swap=torch.cat(cond_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'target_swap_test.npz'), target_swap=torch.cat(target_swap).numpy())
-    return results
+    # P = 1 candidate per sample: the best-of-permutations min / max are the values themselves, `gt_swap` the only candidate
+    return run_content_swap(args.xp_dir, sep_net, xp_config.nt_cond, xp_config.nt_cond + args.nt_pred,
+                            swap_batches(test_dataset, swap_dataset, args.batch_size))
 
 
 def build_parser():
-    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (3D Warehouse Chairs content swap testing)', batch_size=16)
-    p.add_argument('--test_seed', type=int, metavar='SEED', default=1,
-                   help='Manual seed.')
-    add_precision_flag(p)
-    return p
+    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (3D Warehouse Chairs content swap testing)', batch_size=16, test_seed=True)
+    return add_precision_flag(p)
 
 
 if __name__ == '__main__':

@@ -13,9 +13,8 @@ import numpy as np
 import torch
 
 from ...data.moving_mnist import MovingMNIST
-from ...utils.helper import load_json
 from ...utils.metrics import frame_metrics
-from ..utils import add_precision_flag, base_parser, load_model, print_results, seed_all, setup_device, to_host_u8
+from ..utils import add_precision_flag, base_parser, load_model, load_xp_config, print_results, seed_all, setup_device, to_host_u8
 
 
 def load_dataset(args, train=False, device='cuda'):
@@ -38,11 +37,7 @@ def test_batches(test_dataset, batch_size):
 def main(args):
     device = setup_device(args)
     seed_all(args.test_seed)
-    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
-    xp_config.device = device
-    xp_config.data_dir = args.data_dir
-    xp_config.xp_dir = args.xp_dir
-    xp_config.nt_pred = args.nt_pred
+    xp_config = load_xp_config(args, device, args.nt_pred)
 
     print('Loading data...')
     test_dataset = load_dataset(xp_config, train=False, device=device)
@@ -102,11 +97,8 @@ def main(args):
 
 
 def build_parser():
-    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST testing)', batch_size=16)
-    p.add_argument('--test_seed', type=int, metavar='SEED', default=1,
-                   help='Manual seed.')
-    add_precision_flag(p)
-    return p
+    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST testing)', batch_size=16, test_seed=True)
+    return add_precision_flag(p)
 
 
 if __name__ == '__main__':

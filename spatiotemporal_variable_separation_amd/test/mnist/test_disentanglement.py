@@ -11,7 +11,6 @@ Two limits of the reference are lifted, and the results are the reference's wher
   * with n_object >= 3 the reference fails at `view(-1, n_object, ...)` because it renders n! permutations; here all n! are scored.
 """
 import itertools
-import math
 import os
 
 import numpy as np
@@ -19,8 +18,7 @@ import torch
 
 from ... import ops
 from ...data.moving_mnist import read_mnist_images
-from ...utils.helper import load_json
-from ..utils import add_precision_flag, base_parser, load_model, print_results, seed_all, setup_device, to_host_u8
+from ..utils import add_precision_flag, base_parser, load_model, load_xp_config, run_content_swap, seed_all, setup_device
 from .test import load_dataset, test_batches
 
 
@@ -69,24 +67,22 @@ class SwapDataset:
         return v[:, 0, :self.nt_cond], v[:, 0, self.nt_cond:], v[:, 1:, :self.nt_cond], v[:, 1:, self.nt_cond:]
 
 
-def best_of_permutations(pred, gt_swap):
-    """Per sample: min over the permutations of the MSE, max of the PSNR and of the SSIM (test_disentanglement.py:153-166).
-    pred [B, T, C, H, W], gt_swap [B, P, T, C, H, W]."""
-    mse, ssim = ops.frame_metrics_multi(pred, gt_swap, max_val=1.0)       # [B, P, T, C]
-    m = mse.mean(3).mean(2)
-    psnr = (10 * torch.log10(1 / mse)).mean(3).mean(2)
-    s = ssim.mean(3).mean(2)
-    return {'mse': m.min(1)[0], 'psnr': psnr.max(1)[0], 'ssim': s.max(1)[0]}
+def swap_batches(test_dataset, swap_dataset, batch_size):
+    """(x_cond, x_gt_swap, x_swap_cond, x_swap_target) per test batch.  The swap loader is sequential with the same batch size: batch k
+    holds items [k * batch_size, (k + 1) * batch_size), trimmed to the test batch (the reference fails on a ragged last batch, see the
+    module docstring)."""
+    swap_start = 0
+    for x_swap_cond, x_swap_target in test_batches(test_dataset, batch_size):
+        bsz = len(x_swap_cond)
+        x_cond, _, _, x_gt_swap = swap_dataset.batch(range(swap_start, swap_start + bsz))
+        swap_start += batch_size
+        yield x_cond, x_gt_swap, x_swap_cond, x_swap_target
 
 
 def main(args):
     device = setup_device(args)
     seed_all(args.test_seed)
-    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
-    xp_config.device = device
-    xp_config.data_dir = args.data_dir
-    xp_config.xp_dir = args.xp_dir
-    xp_config.nt_pred = args.nt_pred
+    xp_config = load_xp_config(args, device, args.nt_pred)
 
     print('Loading data...')
     test_dataset = load_dataset(xp_config, train=False, device=device)
@@ -97,52 +93,15 @@ def main(args):
 
     print('Generating samples...')
     torch.set_grad_enabled(False)
-    nt_test = xp_config.nt_cond + args.nt_pred
-    gt_swap, content_swap, cond_swap, target_swap = [], [], [], []
-    results = {'mse': [], 'psnr': [], 'ssim': []}
-    swap_start = 0
-    for batch in test_batches(test_dataset, args.batch_size):
-        # the swap loader is sequential with the same batch size: batch k holds items [k * batch_size, (k + 1) * batch_size)
-        x_swap_cond, x_swap_target = batch
-        bsz = len(x_swap_cond)
-        if swap_start + bsz > len(swap_dataset):
-            raise StopIteration('the swap set (%d items) is exhausted' % len(swap_dataset))
-        # trimmed to the test batch (the reference fails on a ragged last batch, see the module docstring)
-        x_cond, x_target, _, x_gt_swap = swap_dataset.batch(range(swap_start, swap_start + bsz))
-        swap_start += args.batch_size
-
-        # Extraction of S
-        _, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
-
-        # Content swap (reference quirk kept: `cond_swap_test` holds the S video's conditioning frames)
-        cond_swap.append(to_host_u8(x_cond))
-        target_swap.append(to_host_u8(x_swap_target))
-        x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
-        x_swap_pred = x_swap_pred[:, xp_config.nt_cond:].float().contiguous()
-        content_swap.append(to_host_u8(x_swap_pred))
-        gt_swap.append(to_host_u8(x_gt_swap[:, 0]))
-
-        # Pixelwise quantitative eval: every permutation scored, best per sample
-        metrics_batch = best_of_permutations(x_swap_pred, x_gt_swap.float())
-        for name in results:
-            results[name].append(metrics_batch[name].cpu())
-
-    results = print_results(results)
-
-    np.savez_compressed(os.path.join(args.xp_dir, 'results_swap.npz'), **results)
-    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap_gt.npz'), gt_swap=torch.cat(gt_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap_test.npz'), content_swap=torch.cat(content_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'cond_swap_test.npz'), cond_swap=torch.cat(cond_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'target_swap_test.npz'), target_swap=torch.cat(target_swap).numpy())
-    return results
+    if test_dataset.data.shape[0] > len(swap_dataset):
+        raise StopIteration('the swap set (%d items) is exhausted' % len(swap_dataset))
+    return run_content_swap(args.xp_dir, sep_net, xp_config.nt_cond, xp_config.nt_cond + args.nt_pred,
+                            swap_batches(test_dataset, swap_dataset, args.batch_size))
 
 
 def build_parser():
-    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST content swap testing)', batch_size=16)
-    p.add_argument('--test_seed', type=int, metavar='SEED', default=1,
-                   help='Manual seed.')
-    add_precision_flag(p)
-    return p
+    p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST content swap testing)', batch_size=16, test_seed=True)
+    return add_precision_flag(p)
 
 
 if __name__ == '__main__':

@@ -13,16 +13,11 @@ zone's min / max of the rescale are those of the z-scored data while the frames 
 paper's numbers, so all of it is reproduced (utils/metrics.py: sst_metrics, one `vs_sst_frame_metrics` launch per batch).  There is no CPU
 mode: --device is required.
 """
-import os
-
 import numpy as np
-import torch
 
 from ...data.sst import SST
-from ...data.wave_eq import DeviceBatchLoader
-from ...utils.helper import load_json
 from ...utils.metrics import sst_metrics
-from ..utils import add_precision_flag, base_parser, load_model, setup_device
+from ..utils import add_precision_flag, base_parser, forecast_metrics, load_model, load_xp_config, setup_device
 
 
 def load_dataset(args, train=False, zones=range(17, 21)):
@@ -31,33 +26,13 @@ def load_dataset(args, train=False, zones=range(17, 21)):
 
 def compute_mse_ssim(args, batch_size, test_set, sep_net):
     """Per-window MSE [B, T] and SSIM [B, T, T] per batch (test/sst/test.py:41-76), computed on the device."""
-    all_mse = []
-    all_ssim = []
-    loader = DeviceBatchLoader(test_set, batch_size, shuffle=False)
-    torch.set_grad_enabled(False)
-    for cond, target, day0, zone in loader:
-        if args.offset:
-            forecasts = sep_net.get_forecast(cond, target.size(1) + args.nt_cond)[0]
-            forecasts = forecasts[:, args.nt_cond:]
-        else:
-            forecasts = sep_net.get_forecast(cond, target.size(1))[0]
-
-        forecasts = forecasts.float().reshape(target.shape)
-        mse, ssim = sst_metrics(forecasts, target, test_set.consts, day0, zone, test_set.zone_range)
-
-        all_mse.append(mse.cpu().numpy())
-        all_ssim.append(ssim.cpu().numpy())
-
-    return all_mse, all_ssim
+    return forecast_metrics(args, batch_size, test_set, sep_net,
+                            lambda f, t, day0, zone: sst_metrics(f, t, test_set.consts, day0, zone, test_set.zone_range))
 
 
 def main(args):
     device = setup_device(args)
-    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
-    xp_config.device = device
-    xp_config.data_dir = args.data_dir
-    xp_config.xp_dir = args.xp_dir
-    xp_config.nt_pred = 10          # the reference evaluates at t+10 whatever the training horizon
+    xp_config = load_xp_config(args, device, 10)         # the reference evaluates at t+10 whatever the training horizon
     args.nt_pred = 10
 
     test_set = load_dataset(xp_config, train=False)
@@ -75,8 +50,7 @@ def main(args):
 
 def build_parser():
     p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST testing)', batch_size=256, nt_pred=False)
-    add_precision_flag(p)
-    return p
+    return add_precision_flag(p)
 
 
 if __name__ == '__main__':

@@ -1,12 +1,14 @@
 """Helpers shared by the evaluation scripts (reference: test/utils.py:8-24)."""
 import argparse
+import os
 
 import numpy as np
 import torch
 
 from .. import functional as VF
 from .. import ops
-from ..utils.helper import load_sep_net
+from ..data.device import DeviceBatchLoader
+from ..utils.helper import load_json, load_sep_net
 from ..utils.metrics import _ssim_wrapper  # noqa: F401  (test/utils.py:19-24, on the device)
 
 NO_CPU_MODE = 'the MI355X-native path has no CPU mode: pass --device N'
@@ -34,14 +36,25 @@ def setup_device(args):
     return device
 
 
+def load_xp_config(args, device, nt_pred):
+    """The `params.json` of `args.xp_dir` with the run's own device, directories and horizon (test/mnist/test.py:66-70)."""
+    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
+    xp_config.device = device
+    xp_config.data_dir = args.data_dir
+    xp_config.xp_dir = args.xp_dir
+    xp_config.nt_pred = nt_pred
+    return xp_config
+
+
 def add_precision_flag(p):
-    """Additive flag (not in the reference): fp32 is the reference's arithmetic, bf16 selects the 16-bit kernels."""
+    """Additive flag (not in the reference): fp32 is the reference's arithmetic, bf16 selects the 16-bit kernels.  Returns `p`."""
     p.add_argument('--precision', type=str, choices=['fp32', 'bf16'], default='fp32',
                    help='Compute precision of the forward pass (fp32: the reference\'s arithmetic; bf16: 16-bit MFMA kernels).')
+    return p
 
 
-def base_parser(prog, batch_size, nt_pred=True):
-    """--data_dir --xp_dir --epoch --batch_size [--nt_pred] --device (+ --precision) with the reference's defaults."""
+def base_parser(prog, batch_size, nt_pred=True, test_seed=False):
+    """--data_dir --xp_dir --epoch --batch_size [--nt_pred] --device [--test_seed] with the reference's defaults."""
     p = argparse.ArgumentParser(prog=prog)
     p.add_argument('--data_dir', type=str, metavar='DIR', required=True,
                    help='Directory where the dataset is saved.')
@@ -56,6 +69,9 @@ def base_parser(prog, batch_size, nt_pred=True):
                        help='Total of frames to predict.')
     p.add_argument('--device', type=int, metavar='DEVICE', default=None,
                    help='GPU where the model should be placed when testing (required: there is no CPU mode)')
+    if test_seed:
+        p.add_argument('--test_seed', type=int, metavar='SEED', default=1,
+                       help='Manual seed.')
     return p
 
 
@@ -83,3 +99,86 @@ def seed_all(seed):
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
+
+
+def forecast_targets(sep_net, cond, n_target, cfg):
+    """Forecast of the `n_target` frames after `cond`.  With `cfg.offset` the model forecasts from the first conditioning frame on, and
+    the conditioning frames are cut off (test/wave/test.py:43-47)."""
+    if cfg.offset:
+        forecasts = sep_net.get_forecast(cond, n_target + cfg.nt_cond)[0]
+        return forecasts[:, cfg.nt_cond:]
+    return sep_net.get_forecast(cond, n_target)[0]
+
+
+def forecast_metrics(cfg, batch_size, test_set, sep_net, metrics):
+    """One list per value of `metrics(forecasts, target, *rest)`, holding that value of every sequential batch (cond, target, *rest) of
+    the HBM-resident `test_set` as a NumPy array; `forecasts` is fp32 in the shape of `target`."""
+    out = None
+    loader = DeviceBatchLoader(test_set, batch_size, shuffle=False)
+    torch.set_grad_enabled(False)
+    for cond, target, *rest in loader:
+        forecasts = forecast_targets(sep_net, cond, target.size(1), cfg).float().reshape(target.shape)
+        values = metrics(forecasts, target, *rest)
+        out = out or [[] for _ in values]
+        for parts, value in zip(out, values):
+            parts.append(value.cpu().numpy())
+    return out
+
+
+def horizon_mse_main(args, horizon, load_dataset, compute_mse):
+    """`main` of the scripts that print the mean MSE of the test windows at a fixed horizon (test/wave/test.py:61-90); returns [N, T(, 1)]."""
+    device = setup_device(args)
+    xp_config = load_xp_config(args, device, horizon)     # the reference evaluates at this horizon whatever the training horizon
+    args.nt_pred = horizon
+
+    test_set = load_dataset(xp_config)
+    sep_net = load_model(xp_config, args.epoch)
+
+    all_mse = compute_mse(xp_config, args.batch_size, test_set, sep_net)
+    mse_array = np.concatenate(all_mse, axis=0)
+    print(f'MSE at t+{horizon}: {np.mean(mse_array.mean(axis=0)[:horizon])}')
+    return mse_array
+
+
+def best_of_permutations(pred, gt_swap):
+    """Per sample: min over the permutations of the MSE, max of the PSNR and of the SSIM (test_disentanglement.py:153-166).
+    pred [B, T, C, H, W], gt_swap [B, P, T, C, H, W]."""
+    mse, ssim = ops.frame_metrics_multi(pred, gt_swap, max_val=1.0)       # [B, P, T, C]
+    m = mse.mean(3).mean(2)
+    psnr = (10 * torch.log10(1 / mse)).mean(3).mean(2)
+    s = ssim.mean(3).mean(2)
+    return {'mse': m.min(1)[0], 'psnr': psnr.max(1)[0], 'ssim': s.max(1)[0]}
+
+
+def run_content_swap(xp_dir, sep_net, nt_cond, nt_test, batches):
+    """The loop and the five files both content-swap scripts share (test/mnist/test_disentanglement.py:118-223).  `batches` yields
+    (x_cond, x_gt_swap, x_swap_cond, x_swap_target): S is extracted from `x_cond`, drives a forecast from `x_swap_cond`, and the forecast
+    is scored against every candidate of `x_gt_swap` [B, P, ...], best per sample.  Reference quirks kept: `cond_swap_test` holds the S
+    video's conditioning frames `x_cond`, not `x_swap_cond`; `gt_swap` is the first candidate."""
+    gt_swap, content_swap, cond_swap, target_swap = [], [], [], []
+    results = {'mse': [], 'psnr': [], 'ssim': []}
+    for x_cond, x_gt_swap, x_swap_cond, x_swap_target in batches:
+        # Extraction of S
+        _, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
+
+        # Content swap
+        cond_swap.append(to_host_u8(x_cond))
+        target_swap.append(to_host_u8(x_swap_target))
+        x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
+        x_swap_pred = x_swap_pred[:, nt_cond:].float().contiguous()
+        content_swap.append(to_host_u8(x_swap_pred))
+        gt_swap.append(to_host_u8(x_gt_swap[:, 0]))
+
+        # Pixelwise quantitative eval: every candidate scored, best per sample
+        metrics_batch = best_of_permutations(x_swap_pred, x_gt_swap.float())
+        for name in results:
+            results[name].append(metrics_batch[name].cpu())
+
+    results = print_results(results)
+
+    np.savez_compressed(os.path.join(xp_dir, 'results_swap.npz'), **results)
+    np.savez_compressed(os.path.join(xp_dir, 'content_swap_gt.npz'), gt_swap=torch.cat(gt_swap).numpy())
+    np.savez_compressed(os.path.join(xp_dir, 'content_swap_test.npz'), content_swap=torch.cat(content_swap).numpy())
+    np.savez_compressed(os.path.join(xp_dir, 'cond_swap_test.npz'), cond_swap=torch.cat(cond_swap).numpy())
+    np.savez_compressed(os.path.join(xp_dir, 'target_swap_test.npz'), target_swap=torch.cat(target_swap).numpy())
+    return results

@@ -5,14 +5,8 @@
 Forecasts 40 frames of every test window (`wave`: full frames, `wave_partial`: the pixel subset) from the HBM-resident WaveEq sets and
 prints the mean MSE over the horizon.  There is no CPU mode: --device is required.
 """
-import os
-
-import numpy as np
-import torch
-
-from ...data.wave_eq import DeviceBatchLoader, WaveEq, WaveEqPartial
-from ...utils.helper import load_json
-from ..utils import add_precision_flag, base_parser, load_model, setup_device
+from ...data.wave_eq import WaveEq, WaveEqPartial
+from ..utils import add_precision_flag, base_parser, forecast_metrics, horizon_mse_main
 
 
 def load_dataset(args, train=False):
@@ -24,50 +18,18 @@ def load_dataset(args, train=False):
 
 def compute_mse(args, batch_size, test_set, sep_net):
     """Per-frame MSE of every test window: [B, T] per batch for `wave`, [B, T, 1] for `wave_partial` (test/wave/test.py:38-58)."""
-    all_mse = []
-    loader = DeviceBatchLoader(test_set, batch_size, shuffle=False)
-    torch.set_grad_enabled(False)
-    for cond, target in loader:
-        if args.offset:
-            forecasts = sep_net.get_forecast(cond, target.size(1) + args.nt_cond)[0]
-            forecasts = forecasts[:, args.nt_cond:]
-        else:
-            forecasts = sep_net.get_forecast(cond, target.size(1))[0]
-
-        forecasts = forecasts.float().reshape(target.shape)
-
-        if args.data == 'wave':
-            mse = (forecasts - target).pow(2).mean(dim=-1).mean(dim=-1).mean(dim=-1)
-        else:
-            mse = (forecasts - target).pow(2).mean(dim=-1)
-
-        all_mse.append(mse.cpu().numpy())
-
-    return all_mse
+    if args.data == 'wave':
+        return forecast_metrics(args, batch_size, test_set, sep_net, lambda f, t: [(f - t).pow(2).mean(dim=-1).mean(dim=-1).mean(dim=-1)])[0]
+    return forecast_metrics(args, batch_size, test_set, sep_net, lambda f, t: [(f - t).pow(2).mean(dim=-1)])[0]
 
 
 def main(args):
-    device = setup_device(args)
-    xp_config = load_json(os.path.join(args.xp_dir, 'params.json'))
-    xp_config.device = device
-    xp_config.data_dir = args.data_dir
-    xp_config.xp_dir = args.xp_dir
-    xp_config.nt_pred = 40          # the reference evaluates at t+40 whatever the training horizon
-    args.nt_pred = 40
-
-    test_set = load_dataset(xp_config, train=False)
-    sep_net = load_model(xp_config, args.epoch)
-
-    all_mse = compute_mse(xp_config, args.batch_size, test_set, sep_net)
-    mse_array = np.concatenate(all_mse, axis=0)
-    print(f'MSE at t+40: {np.mean(mse_array.mean(axis=0)[:40])}')
-    return mse_array
+    return horizon_mse_main(args, 40, load_dataset, compute_mse)
 
 
 def build_parser():
     p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST testing)', batch_size=256, nt_pred=False)
-    add_precision_flag(p)
-    return p
+    return add_precision_flag(p)
 
 
 if __name__ == '__main__':

@@ -1,5 +1,9 @@
-"""Helpers to replay tests/golden/*.npz (vectors produced by the reference, see oracle/make_golden.py)."""
+"""Helpers to replay tests/golden/*.npz (vectors produced by the reference, see oracle/make_golden.py), and what the fixture inputs
+(tests/*_inputs.py) share: per-item checksums and stand-in modules."""
 import os
+import sys
+import types
+import zlib
 
 import numpy as np
 import torch
@@ -12,6 +16,27 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 def load_golden(name):
     with np.load(os.path.join(GOLDEN_DIR, name + '.npz')) as z:
         return {k: z[k] for k in z.files}
+
+
+def item_crcs(items):
+    """uint32 [n]: zlib.crc32 of every item's fp32 bytes (cond then target = the item's frames in order)."""
+    items = np.ascontiguousarray(items, dtype=np.float32)
+    return np.array([zlib.crc32(x.tobytes()) for x in items], dtype=np.uint32)
+
+
+def install_standin(name, **attrs):
+    """Put a minimal stand-in module `name` with the attributes `attrs` into sys.modules and return it.  Undo with remove_standin(name)."""
+    mod = types.ModuleType(name)
+    mod.__version__ = '0.0-standin'
+    for key, value in attrs.items():
+        setattr(mod, key, value)
+    sys.modules[name] = mod
+    return mod
+
+
+def remove_standin(name):
+    if getattr(sys.modules.get(name), '__version__', '') == '0.0-standin':
+        del sys.modules[name]
 
 
 def rel_err(a, b):

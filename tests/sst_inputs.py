@@ -8,11 +8,10 @@ leave 11 windows per zone (44 for the evaluation's zones 17-20), 2 + 2 days leav
 """
 import functools
 import os
-import sys
-import types
-import zlib
 
 import numpy as np
+
+from golden_util import install_standin, item_crcs, remove_standin  # noqa: F401  (item_crcs: used through this module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, 'golden', 'sst')
@@ -95,28 +94,17 @@ def install_fake_netcdf4(zone_arrays=None):
         def close(self):
             pass
 
-    mod = types.ModuleType('netCDF4')
-    mod.Dataset = Dataset
-    mod.__version__ = '0.0-standin'
-    sys.modules['netCDF4'] = mod
-    return mod
+    return install_standin('netCDF4', Dataset=Dataset)
 
 
 def remove_fake_netcdf4():
-    if getattr(sys.modules.get('netCDF4'), '__version__', '') == '0.0-standin':
-        del sys.modules['netCDF4']
+    remove_standin('netCDF4')
 
 
 def assemble(frames, first, items, seq_len):
     """fp32 [n, seq_len, 1, 64, 64] of the windows `items` from the host arrays: position k is day first + k."""
     rows = np.asarray(first)[np.asarray(items)].astype(np.int64)[:, None] + np.arange(seq_len)[None]
     return np.asarray(frames)[rows].reshape(len(rows), seq_len, 1, SIZE, SIZE)
-
-
-def item_crcs(items):
-    """uint32 [n]: zlib.crc32 of every item's fp32 bytes (cond then target = the item's days in order)."""
-    items = np.ascontiguousarray(items, dtype=np.float32)
-    return np.array([zlib.crc32(x.tobytes()) for x in items], dtype=np.uint32)
 
 
 def whole_item_key(call, index):

@@ -15,11 +15,10 @@ Timestamps are bytes for the years 13 and 14 and str for 15 and 16 in the .npz t
 import datetime
 import functools
 import os
-import sys
-import types
-import zlib
 
 import numpy as np
+
+from golden_util import install_standin, item_crcs, remove_standin  # noqa: F401  (item_crcs: used through this module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, 'golden', 'taxibj')
@@ -105,28 +104,17 @@ def install_fake_h5py(year_arrays=None):
         def __exit__(self, *exc):
             self.close()
 
-    mod = types.ModuleType('h5py')
-    mod.File = File
-    mod.__version__ = '0.0-standin'
-    sys.modules['h5py'] = mod
-    return mod
+    return install_standin('h5py', File=File)
 
 
 def remove_fake_h5py():
-    if getattr(sys.modules.get('h5py'), '__version__', '') == '0.0-standin':
-        del sys.modules['h5py']
+    remove_standin('h5py')
 
 
 def assemble(frames, first, items, len_closeness):
     """fp32 [n, len_closeness, 2, 32, 32] of the windows `items` from the host arrays of `build_windows`: position k is frame first - k."""
     rows = np.asarray(first)[np.asarray(items)].astype(np.int64)[:, None] - np.arange(len_closeness)[None]
     return np.asarray(frames)[rows].reshape(len(rows), len_closeness, 2, 32, 32)
-
-
-def item_crcs(items):
-    """uint32 [n]: zlib.crc32 of every item's fp32 bytes (cond then target = the item's frames in order)."""
-    items = np.ascontiguousarray(items, dtype=np.float32)
-    return np.array([zlib.crc32(x.tobytes()) for x in items], dtype=np.uint32)
 
 
 def whole_item_key(call, half, index):

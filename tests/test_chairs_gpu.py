@@ -4,30 +4,21 @@ content-swap CLI (test/chairs/test_disentanglement.py) against the reference's o
 import json
 import os
 import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import chairs_inputs as I
+from cli_util import check_training_run, close, run_module, write_xp
 from eval_cli_inputs import parse_results
 from golden_util import GOLDEN_DIR
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = 'spatiotemporal_variable_separation_amd'
 
 DATA_ARRAYS = {'content_swap_gt.npz', 'cond_swap_test.npz', 'target_swap_test.npz'}
 MODEL_ARRAYS = {'content_swap_test.npz'}
 OUTPUTS = ['results_swap.npz', 'content_swap_gt.npz', 'content_swap_test.npz', 'cond_swap_test.npz', 'target_swap_test.npz']
-
-
-def _close(a, b, rel=1e-3, floor=1e-5):
-    """The rule of tests/test_eval_cli_gpu.py: rel <= 1e-3; `floor` absorbs values near zero."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all(np.abs(a - b) <= rel * np.abs(b) + floor))
 
 
 @pytest.fixture(scope='module')
@@ -183,7 +174,7 @@ def test_device_loader_visits_the_dataloader_items(tree):
     draws its base seed, then its RandomSampler draws the permutation."""
     from torch.utils.data import BatchSampler, RandomSampler
     from spatiotemporal_variable_separation_amd.data.chairs import Chairs
-    from spatiotemporal_variable_separation_amd.data.wave_eq import DeviceBatchLoader
+    from spatiotemporal_variable_separation_amd.data.device import DeviceBatchLoader
     frames = I.split_frames(True)
     ds = Chairs(True, tree, 2, seq_len=4, device='cuda')
     torch.manual_seed(17)
@@ -201,16 +192,10 @@ def test_device_loader_visits_the_dataloader_items(tree):
 
 
 # --------------------------------------------------------------------------------------------------------------------- the CLI
-def _run(module, args, timeout=900):
-    r = subprocess.run([sys.executable, '-m', module] + args, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
-
-
 def _check_cli(case, xp, tree):
     golden = os.path.join(GOLDEN_DIR, case)
-    out = _run('%s.test.chairs.test_disentanglement' % PKG, ['--xp_dir', xp, '--data_dir', tree, '--nt_pred', str(I.RUN['nt_pred']),
-                                                               '--batch_size', str(I.RUN['batch_size']), '--device', '0'])
+    out = run_module('test.chairs.test_disentanglement', ['--xp_dir', xp, '--data_dir', tree, '--nt_pred', str(I.RUN['nt_pred']),
+                                                          '--batch_size', str(I.RUN['batch_size']), '--device', '0'], timeout=900)
     with open(os.path.join(golden, 'printed.json')) as f:
         want = json.load(f)
     got = parse_results(out)
@@ -229,8 +214,8 @@ def _check_cli(case, xp, tree):
                 assert d.max() <= 1 and np.count_nonzero(d) <= 1e-3 * d.size, (name, key, int(d.max()), np.count_nonzero(d))
             else:
                 print(case, name, key, 'max rel', float(np.max(np.abs(g - w) / np.abs(w))))
-                assert _close(g, w), (name, key, np.abs(g - w).max())
-    assert set(got) == {'mse', 'psnr', 'ssim'} and all(_close(got[k], want[k]) for k in want), (got, want)
+                assert close(g, w), (name, key, np.abs(g - w).max())
+    assert set(got) == {'mse', 'psnr', 'ssim'} and all(close(got[k], want[k]) for k in want), (got, want)
 
 
 def test_chairs_cli_matches_reference(tree, tmp_path):
@@ -245,14 +230,7 @@ def test_chairs_cli_matches_reference(tree, tmp_path):
 def test_chairs_cli_matches_reference_resnet(tree, tmp_path):
     """The recipe's encoder: the `chairs_resnet` network (ResNet18 + DCGAN decoder) with the det_fill weights the fixture was made with,
     saved by this package's own `save`."""
-    from oracle.detdata import det_fill
-    from oracle.golden_configs import CONFIGS
-    from spatiotemporal_variable_separation_amd.networks.factory import build_sep_net
-    from spatiotemporal_variable_separation_amd.utils.helper import save
-    cfg = CONFIGS['chairs_resnet']
-    xp = str(tmp_path / 'xp')
-    save(xp, det_fill(build_sep_net(cfg), salt=cfg['salt']))
-    shutil.copy(os.path.join(GOLDEN_DIR, 'eval_cli_chairs_resnet', 'params.json'), xp)
+    xp = write_xp('chairs_resnet', str(tmp_path / 'xp'), os.path.join(GOLDEN_DIR, 'eval_cli_chairs_resnet', 'params.json'))
     _check_cli('eval_cli_chairs_resnet', xp, tree)
 
 
@@ -260,17 +238,9 @@ def test_chairs_cli_matches_reference_resnet(tree, tmp_path):
 def test_main_trains_on_a_chairs_tree(tree, tmp_path):
     """`main --data chairs --data_dir <tree>` in a fresh process, recorded-graph default: 310 train items in batches of 64 (a ragged last
     batch), finite losses, the four checkpoint files."""
-    import re
-    cmd = [sys.executable, '-m', '%s.main' % PKG, '--xp_dir', str(tmp_path), '--data_dir', tree, '--device', '0', '--epochs', '1',
-           '--batch_size', '64', '--num_workers', '0', '--seed', '3', '--log_interval', '1', '--chkpt_interval', '1',
-           '--data', 'chairs', '--architecture', 'resnet', '--decoder_architecture', 'dcgan', '--nt_cond', '2', '--nt_pred', '2', '--offset', '2',
-           '--dec_hidden_size', '8', '--res_hidden_size', '16', '--code_size_s', '12', '--code_size_t', '6', '--lamb_ae', '1', '--lamb_s', '1',
-           '--precision', 'bf16']
-    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'recorded hipGraph' in r.stdout and 'frames/s' in r.stdout, r.stdout[-2000:]
-    losses = [float(v) for v in re.findall(r'total (\S+)', r.stdout)]
-    assert len(losses) >= 5 and all(np.isfinite(v) for v in losses), r.stdout[-2000:]
-    for stem in ('ov_Et', 'ov_Es', 'decoder', 't_resnet'):
-        assert (tmp_path / f'{stem}.pt').exists() and (tmp_path / f'{stem}_1.pt').exists()
-    assert (tmp_path / 'params.json').exists()
+    args = ['--xp_dir', str(tmp_path), '--data_dir', tree, '--device', '0', '--epochs', '1',
+            '--batch_size', '64', '--num_workers', '0', '--seed', '3', '--log_interval', '1', '--chkpt_interval', '1',
+            '--data', 'chairs', '--architecture', 'resnet', '--decoder_architecture', 'dcgan', '--nt_cond', '2', '--nt_pred', '2', '--offset', '2',
+            '--dec_hidden_size', '8', '--res_hidden_size', '16', '--code_size_s', '12', '--code_size_t', '6', '--lamb_ae', '1', '--lamb_s', '1',
+            '--precision', 'bf16']
+    check_training_run(run_module('main', args, timeout=900), tmp_path, min_losses=5)

@@ -36,7 +36,7 @@ def _dataset(wave_dir, kind, train):
 @pytest.mark.parametrize('kind', ['full', 'partial'])
 def test_device_loader_reproduces_reference_batches(wave_dir, kind, train):
     from oracle.wave_data_ref import FIXTURE as f
-    from spatiotemporal_variable_separation_amd.data.wave_eq import DeviceBatchLoader
+    from spatiotemporal_variable_separation_amd.data.device import DeviceBatchLoader
     ds = _dataset(wave_dir, kind, train)
     assert ds.all_data.is_cuda
     got = replay(ds, f['seed'], f['batch_size'], lambda d, bs: DeviceBatchLoader(d, bs, shuffle=True))
@@ -81,7 +81,7 @@ def test_device_loader_sequential_drop_last_and_external_sampler(wave_dir):
     """Loader plumbing around the gather: sequential order, drop_last, and a caller-supplied sampler (what main() passes under
     torchrun: a DistributedSampler over the item indices)."""
     from torch.utils.data.distributed import DistributedSampler
-    from spatiotemporal_variable_separation_amd.data.wave_eq import DeviceBatchLoader
+    from spatiotemporal_variable_separation_amd.data.device import DeviceBatchLoader
     ds = _dataset(wave_dir, 'full', True)
     n = len(ds)
     seq = list(DeviceBatchLoader(ds, 4, shuffle=False))

@@ -4,32 +4,23 @@ the reference's own outputs on the same inputs (tests/golden/eval_cli_*, written
 import json
 import os
 import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import eval_cli_inputs as I
+from cli_util import close, run_module
 from golden_util import GOLDEN_DIR
 from oracle.wave_data_ref import fixture_dir, sorted_listdir
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = 'spatiotemporal_variable_separation_amd'
 
 DATA_ARRAYS = {'gt.npz', 'cond.npz', 'cond_swap.npz', 'target_swap.npz', 'content_swap_gt.npz', 'cond_swap_test.npz', 'target_swap_test.npz'}
 MODEL_ARRAYS = {'predictions.npz', 'content_swap.npz', 'content_swap_test.npz'}
 OUTPUTS = {'test': ['results.npz', 'predictions.npz', 'gt.npz', 'cond.npz', 'content_swap.npz', 'cond_swap.npz', 'target_swap.npz'],
            'test_disentanglement': ['results_swap.npz', 'content_swap_gt.npz', 'content_swap_test.npz', 'cond_swap_test.npz',
                                     'target_swap_test.npz']}
-
-
-def _close(a, b, rel=1e-3, floor=1e-5):
-    """rel <= 1e-3; `floor` absorbs values near zero (the mean SSIM of an untrained model is ~1e-3, a sum of terms of both signs)."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all(np.abs(a - b) <= rel * np.abs(b) + floor))
 
 
 @pytest.fixture(scope='module')
@@ -43,24 +34,18 @@ def inputs():
         shutil.rmtree(base, ignore_errors=True)
 
 
-def _run(module, args, timeout=600):
-    r = subprocess.run([sys.executable, '-m', module] + args, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
-
-
 # ------------------------------------------------------------------------------------------------------------------- the CLIs
 @pytest.mark.parametrize('script', ['test', 'test_disentanglement'])
 def test_mnist_cli_matches_reference(script, inputs, tmp_path):
     xp = str(tmp_path / 'xp')
     shutil.copytree(os.path.join(GOLDEN_DIR, 'ckpt_dcgan_tiny'), xp)
     shutil.copy(os.path.join(GOLDEN_DIR, 'eval_cli_mnist', 'params.json'), xp)
-    out = _run('%s.test.mnist.%s' % (PKG, script), ['--xp_dir', xp, '--data_dir', inputs['mnist'], '--nt_pred', str(I.MNIST_RUN['nt_pred']),
-                                                    '--batch_size', str(I.MNIST_RUN['batch_size'][script]), '--device', '0'])
+    out = run_module('test.mnist.%s' % script, ['--xp_dir', xp, '--data_dir', inputs['mnist'], '--nt_pred', str(I.MNIST_RUN['nt_pred']),
+                                                  '--batch_size', str(I.MNIST_RUN['batch_size'][script]), '--device', '0'])
     with open(os.path.join(GOLDEN_DIR, 'eval_cli_mnist', 'printed.json')) as f:
         want = json.load(f)[script]
     got = I.parse_results(out)
-    assert set(got) == {'mse', 'psnr', 'ssim'} and all(_close(got[k], want[k]) for k in want), (got, want)
+    assert set(got) == {'mse', 'psnr', 'ssim'} and all(close(got[k], want[k]) for k in want), (got, want)
     for name in OUTPUTS[script]:
         with np.load(os.path.join(xp, name)) as z_got, np.load(os.path.join(GOLDEN_DIR, 'eval_cli_mnist', name)) as z_want:
             assert sorted(z_got.files) == sorted(z_want.files), name
@@ -73,19 +58,19 @@ def test_mnist_cli_matches_reference(script, inputs, tmp_path):
                     d = np.abs(g.astype(np.int16) - w.astype(np.int16))
                     assert d.max() <= 1 and np.count_nonzero(d) <= 1e-3 * d.size, (name, key, int(d.max()), np.count_nonzero(d))
                 else:
-                    assert _close(g, w), (name, key, np.abs(g - w).max())
+                    assert close(g, w), (name, key, np.abs(g - w).max())
 
 
 @pytest.mark.parametrize('kind', ['wave', 'wave_partial'])
 def test_wave_cli_matches_reference(kind, inputs, tmp_path):
     xp = str(tmp_path / 'xp')
     shutil.copytree(os.path.join(GOLDEN_DIR, 'eval_cli_' + kind), xp)
-    out = _run('%s.test.wave.test' % PKG, ['--xp_dir', xp, '--data_dir', inputs['wave'], '--batch_size', str(I.WAVE_RUN['batch_size']),
-                                            '--device', '0'])
+    out = run_module('test.wave.test', ['--xp_dir', xp, '--data_dir', inputs['wave'], '--batch_size', str(I.WAVE_RUN['batch_size']),
+                                       '--device', '0'])
     with open(os.path.join(GOLDEN_DIR, 'eval_cli_' + kind, 'printed.json')) as f:
         want = json.load(f)
     got = I.parse_results(out)
-    assert 'mse_t40' in got and _close(got['mse_t40'], want['mse_t40'], floor=0), (got, want)
+    assert 'mse_t40' in got and close(got['mse_t40'], want['mse_t40'], floor=0), (got, want)
 
 
 @pytest.mark.parametrize('kind', ['wave', 'wave_partial'])
@@ -106,7 +91,7 @@ def test_wave_mse_arrays_match_reference(kind, inputs):
     with np.load(os.path.join(xp, 'mse.npz')) as z:
         want = z['mse']
     assert mse.shape == want.shape == ((len(test_set),) + ((40,) if kind == 'wave' else (40, 1)))
-    assert _close(mse, want, floor=0), np.abs(mse / want - 1).max()
+    assert close(mse, want, floor=0), np.abs(mse / want - 1).max()
 
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels

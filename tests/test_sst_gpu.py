@@ -5,8 +5,6 @@ synthetic zones of tests/sst_inputs.py)."""
 import functools
 import json
 import os
-import re
-import shutil
 import subprocess
 import sys
 
@@ -15,16 +13,9 @@ import pytest
 import torch
 
 import sst_inputs as I
+from cli_util import PKG, ROOT, check_training_run, close, write_xp
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = 'spatiotemporal_variable_separation_amd'
-
-
-def _within(a, b, floor, rel=1e-3):
-    """|a - b| <= rel |b| + floor, element-wise.  floor 1e-5 is the rule of the evaluation CLIs (tests/test_eval_cli_gpu.py)."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all(np.abs(a - b) <= rel * np.abs(b) + floor))
 
 
 @pytest.fixture(scope='module')
@@ -98,7 +89,7 @@ def test_every_item_matches_the_reference(tree, golden, call):
 
 def test_device_loader_serves_a_ragged_last_batch(tree, golden):
     from spatiotemporal_variable_separation_amd.data.sst import SST
-    from spatiotemporal_variable_separation_amd.data.wave_eq import DeviceBatchLoader
+    from spatiotemporal_variable_separation_amd.data.device import DeviceBatchLoader
     kw = I.CALLS['test']
     ds = SST(tree, kw['nt_cond'], kw['nt_pred'], False, zones=kw['zones'], eval=True, device='cuda')
     batches = list(DeviceBatchLoader(ds, 16, shuffle=False))
@@ -167,9 +158,9 @@ def test_sst_frame_metrics_matches_fp64(shape, T, rows):
     e_fused = float(np.abs(ssim - c['ssim64']).max())
     print('H x W', shape, 'T', T, 'rows', rows, 'E_unfused', c['e_unfused'], 'E_fused', e_fused, 'largest relative MSE error',
           float(np.abs(mse / c['mse64'] - 1).max()), 'SSIM from', float(c['ssim64'].min()), 'to', float(c['ssim64'].max()))
-    assert np.isfinite(c['ssim64']).all() and c['e_unfused'] > 0 and _within(c['mse_u'], c['mse64'], 1e-5)      # the yardstick itself
-    assert _within(mse, c['mse64'], 1e-5)
-    assert _within(ssim, c['ssim64'], 4 * c['e_unfused'])
+    assert np.isfinite(c['ssim64']).all() and c['e_unfused'] > 0 and close(c['mse_u'], c['mse64'], floor=1e-5)      # the yardstick itself
+    assert close(mse, c['mse64'], floor=1e-5)
+    assert close(ssim, c['ssim64'], floor=4 * c['e_unfused'])
     m5, s5 = sst_metrics(pred[:, :, None], target[:, :, None], consts, day0, zone, zone_range)               # [B, T, 1, H, W] frames
     assert np.array_equal(m5.cpu().numpy(), mse) and np.array_equal(s5.cpu().numpy(), ssim)
 
@@ -180,7 +171,7 @@ def test_sst_frame_metrics_sixteen_days():
     c = _case(64, 64, 16, 2)
     pred, target, consts, day0, zone, zone_range = c['dev']
     mse, ssim = ops.sst_frame_metrics(pred, target, consts, day0, zone, zone_range)
-    assert _within(mse.cpu().numpy(), c['mse64'], 1e-5) and _within(ssim.cpu().numpy(), c['ssim64'], 4 * c['e_unfused'])
+    assert close(mse.cpu().numpy(), c['mse64'], floor=1e-5) and close(ssim.cpu().numpy(), c['ssim64'], floor=4 * c['e_unfused'])
     big = torch.zeros((1, 17, 11, 11)).cuda()
     with pytest.raises(_lib.VarsepHipError, match='vs_sst_frame_metrics'):
         ops.sst_frame_metrics(big, big, torch.ones((20, 4)).cuda(), day0[:1], zone[:1], zone_range)
@@ -203,7 +194,7 @@ def test_sst_frame_metrics_flags_bad_rows():
         mse, ssim = mse.cpu().numpy(), ssim.cpu().numpy()
         keep = [r for r in range(rows) if r != row]
         assert not mse[row].any() and not ssim[row].any(), (row, which, value)
-        assert _within(mse[keep], c['mse64'][keep], 1e-5) and _within(ssim[keep], c['ssim64'][keep], 4 * c['e_unfused']), (row, which, value)
+        assert close(mse[keep], c['mse64'][keep], floor=1e-5) and close(ssim[keep], c['ssim64'][keep], floor=4 * c['e_unfused']), (row, which, value)
     for bad in [dict(pred=pred.cpu()), dict(pred=pred.double()), dict(pred=pred[:, :2]), dict(consts=consts[:, :3].contiguous()),
                 dict(day0=day0.long()), dict(zone=zone[:2]), dict(zone_range=zone_range.double()), dict(zone=zone.long())]:
         a = dict(pred=pred, target=target, consts=consts, day0=day0, zone=zone, zone_range=zone_range)
@@ -247,28 +238,20 @@ def test_sst_frame_metrics_argument_checks():
     # identity constants and range (0, 1): the plain frame metrics of the planes, for every day
     from spatiotemporal_variable_separation_amd import ops
     m, s = ops.frame_metrics(pred, target, max_val=1.0)
-    assert int(bad.item()) == 0 and _within(mse.cpu().numpy(), m.cpu().numpy(), 1e-5)
-    assert _within(ssim.cpu().numpy(), s[:, :, None].expand(rows, T, T).cpu().numpy(), 1e-5)
+    assert int(bad.item()) == 0 and close(mse.cpu().numpy(), m.cpu().numpy(), floor=1e-5)
+    assert close(ssim.cpu().numpy(), s[:, :, None].expand(rows, T, T).cpu().numpy(), floor=1e-5)
     # either output alone
     mse.fill_(7.0)
     assert call(ssim=None) == 0 and call(mse=None) == 0
     torch.cuda.synchronize()
-    assert _within(mse.cpu().numpy(), m.cpu().numpy(), 1e-5)
+    assert close(mse.cpu().numpy(), m.cpu().numpy(), floor=1e-5)
 
 
 # --------------------------------------------------------------------------------------------------------------------- the CLI
 @pytest.fixture(scope='module')
 def xp(tmp_path_factory):
     """The `sst_skip` network with the det_fill weights the fixture was made with, saved by this package's own `save`."""
-    from oracle.detdata import det_fill
-    from oracle.golden_configs import CONFIGS
-    from spatiotemporal_variable_separation_amd.networks.factory import build_sep_net
-    from spatiotemporal_variable_separation_amd.utils.helper import save
-    cfg = CONFIGS['sst_skip']
-    path = str(tmp_path_factory.mktemp('sst_xp'))
-    save(path, det_fill(build_sep_net(cfg), salt=cfg['salt']))
-    shutil.copy(os.path.join(I.GOLDEN, 'eval_cli', 'params.json'), path)
-    return path
+    return write_xp('sst_skip', str(tmp_path_factory.mktemp('sst_xp')), os.path.join(I.GOLDEN, 'eval_cli', 'params.json'))
 
 
 RUN_CLI = ('import sys, numpy as np\n'
@@ -311,13 +294,13 @@ def test_sst_cli_arrays_match_the_reference(cli_runs, reference_metrics, batch_s
     assert mse.shape == (I.N_TEST, 10) and ssim.shape == (I.N_TEST, 10, 10) and 0 < printed['E'] <= 1e-4
     print('batch', batch_size, 'largest relative MSE difference', float(np.abs(mse / metrics['mse'] - 1).max()), 'largest SSIM difference',
           float(np.abs(ssim - metrics['ssim']).max()), 'to fp64', float(np.abs(ssim - metrics['ssim_fp64']).max()), 'E', printed['E'])
-    assert _within(mse, metrics['mse'], 1e-5)
-    assert _within(ssim, metrics['ssim'], 4 * printed['E'])
+    assert close(mse, metrics['mse'], floor=1e-5)
+    assert close(ssim, metrics['ssim'], floor=4 * printed['E'])
 
 
 def test_sst_cli_batch_sizes_agree(cli_runs, reference_metrics):
     E = reference_metrics[1]['E']
-    assert _within(cli_runs[1][1], cli_runs[16][1], 1e-5) and _within(cli_runs[1][2], cli_runs[16][2], 4 * E)
+    assert close(cli_runs[1][1], cli_runs[16][1], floor=1e-5) and close(cli_runs[1][2], cli_runs[16][2], floor=4 * E)
 
 
 def test_sst_cli_prints_the_reference_lines(cli_runs, reference_metrics):
@@ -348,9 +331,4 @@ def test_main_trains_on_an_sst_tree(tmp_path):
            '--code_size_t', '8', '--lamb_ae', '1', '--lamb_s', '100', '--lamb_t', '5e-6', '--precision', 'bf16']
     r = subprocess.run(['timeout', '-k', '10', '300'] + cmd, cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'recorded hipGraph' in r.stdout and 'frames/s' in r.stdout, r.stdout[-2000:]
-    losses = [float(v) for v in re.findall(r'total (\S+)', r.stdout)]
-    assert len(losses) >= 2 and all(np.isfinite(v) for v in losses), r.stdout[-2000:]
-    for stem in ('ov_Et', 'ov_Es', 'decoder', 't_resnet'):
-        assert (xp_dir / f'{stem}.pt').exists() and (xp_dir / f'{stem}_1.pt').exists()
-    assert (xp_dir / 'params.json').exists()
+    check_training_run(r.stdout, xp_dir, min_losses=2)

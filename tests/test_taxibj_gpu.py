@@ -3,27 +3,16 @@ the evaluation CLI (test/taxibj/test.py) against the reference's own items and p
 written by tests/make_golden_taxibj.py from the synthetic years of tests/taxibj_inputs.py)."""
 import json
 import os
-import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import taxibj_inputs as I
+from cli_util import check_training_run, close, run_module, write_xp
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = 'spatiotemporal_variable_separation_amd'
 F = 40                                                   # frames of the kernel tests' timeline
-
-
-def _close(a, b, rel=1e-3, floor=1e-5):
-    """The rule of the evaluation CLIs (tests/test_eval_cli_gpu.py, tests/test_chairs_gpu.py): |a - b| <= 1e-3 |b| + 1e-5."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all(np.abs(a - b) <= rel * np.abs(b) + floor))
 
 
 @pytest.fixture(scope='module')
@@ -200,7 +189,7 @@ def test_device_loader_visits_the_dataloader_items(tree):
     draws its base seed, then its RandomSampler draws the permutation."""
     from torch.utils.data import BatchSampler, RandomSampler
     from spatiotemporal_variable_separation_amd.data.taxibj import TaxiBJ, build_windows
-    from spatiotemporal_variable_separation_amd.data.wave_eq import DeviceBatchLoader
+    from spatiotemporal_variable_separation_amd.data.device import DeviceBatchLoader
     frames, first, n_train, _ = build_windows(tree, len_closeness=8)
     ds = TaxiBJ.make_datasets(tree, len_closeness=8, nt_cond=4, device='cuda')[0]
     assert len(ds) == n_train == 192
@@ -221,28 +210,18 @@ def test_device_loader_visits_the_dataloader_items(tree):
 @pytest.fixture(scope='module')
 def xp(tmp_path_factory):
     """The `vgg32_tiny` network with the det_fill weights the fixture was made with, saved by this package's own `save`."""
-    from oracle.detdata import det_fill
-    from oracle.golden_configs import CONFIGS
-    from spatiotemporal_variable_separation_amd.networks.factory import build_sep_net
-    from spatiotemporal_variable_separation_amd.utils.helper import save
-    cfg = CONFIGS['vgg32_tiny']
-    path = str(tmp_path_factory.mktemp('taxibj_xp'))
-    save(path, det_fill(build_sep_net(cfg), salt=cfg['salt']))
-    shutil.copy(os.path.join(I.GOLDEN, 'eval_cli', 'params.json'), path)
-    return path
+    return write_xp('vgg32_tiny', str(tmp_path_factory.mktemp('taxibj_xp')), os.path.join(I.GOLDEN, 'eval_cli', 'params.json'))
 
 
 def test_taxibj_cli_prints_the_reference_mse(tree, xp):
-    r = subprocess.run([sys.executable, '-m', '%s.test.taxibj.test' % PKG, '--xp_dir', xp, '--data_dir', tree, '--batch_size', '200',
-                        '--device', '0', '--precision', 'fp32'], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    lines = [q for q in r.stdout.splitlines() if q.startswith('MSE at t+4:')]
-    assert len(lines) == 1, r.stdout[-2000:]
+    stdout = run_module('test.taxibj.test', ['--xp_dir', xp, '--data_dir', tree, '--batch_size', '200', '--device', '0', '--precision', 'fp32'])
+    lines = [q for q in stdout.splitlines() if q.startswith('MSE at t+4:')]
+    assert len(lines) == 1, stdout[-2000:]
     got = float(lines[0].split(':', 1)[1])
     with open(os.path.join(I.GOLDEN, 'eval_cli', 'printed.json')) as f:
         want = json.load(f)['mse_t4']
     print('printed', got, 'reference', want)
-    assert _close(got, want), (got, want)
+    assert close(got, want), (got, want)
 
 
 def test_taxibj_mse_array_matches_reference(tree, xp):
@@ -261,22 +240,15 @@ def test_taxibj_mse_array_matches_reference(tree, xp):
         want = z['mse']
     assert len(test_set) == I.N_TEST and mse.shape == want.shape == (I.N_TEST, 4)
     print('max relative difference', float(np.abs(mse / want - 1).max()), 'smallest reference value', float(want.min()))
-    assert _close(mse, want), np.abs(mse / want - 1).max()
+    assert close(mse, want), np.abs(mse / want - 1).max()
 
 
 # ---------------------------------------------------------------------------------------------------------------------- training
 def test_main_trains_on_a_taxibj_tree(tree, tmp_path):
     """`main --data taxibj --data_dir <tree>` in a fresh process, recorded-graph default: with 2 + 2 frames per item the train half holds
     212 windows, in batches of 64 (a ragged last batch of 20); finite losses, the four checkpoint files."""
-    cmd = [sys.executable, '-m', '%s.main' % PKG, '--xp_dir', str(tmp_path), '--data_dir', tree, '--device', '0', '--epochs', '1',
-           '--batch_size', '64', '--num_workers', '0', '--seed', '3', '--log_interval', '1', '--chkpt_interval', '1',
-           '--data', 'taxibj', '--architecture', 'vgg', '--nt_cond', '2', '--nt_pred', '2', '--offset', '2', '--enc_hidden_size', '8',
-           '--dec_hidden_size', '8', '--res_hidden_size', '16', '--code_size_s', '12', '--code_size_t', '6', '--precision', 'bf16']
-    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'recorded hipGraph' in r.stdout and 'frames/s' in r.stdout, r.stdout[-2000:]
-    losses = [float(v) for v in re.findall(r'total (\S+)', r.stdout)]
-    assert len(losses) >= 4 and all(np.isfinite(v) for v in losses), r.stdout[-2000:]
-    for stem in ('ov_Et', 'ov_Es', 'decoder', 't_resnet'):
-        assert (tmp_path / f'{stem}.pt').exists() and (tmp_path / f'{stem}_1.pt').exists()
-    assert (tmp_path / 'params.json').exists()
+    args = ['--xp_dir', str(tmp_path), '--data_dir', tree, '--device', '0', '--epochs', '1',
+            '--batch_size', '64', '--num_workers', '0', '--seed', '3', '--log_interval', '1', '--chkpt_interval', '1',
+            '--data', 'taxibj', '--architecture', 'vgg', '--nt_cond', '2', '--nt_pred', '2', '--offset', '2', '--enc_hidden_size', '8',
+            '--dec_hidden_size', '8', '--res_hidden_size', '16', '--code_size_s', '12', '--code_size_t', '6', '--precision', 'bf16']
+    check_training_run(run_module('main', args), tmp_path, min_losses=4)
