@@ -1,4 +1,7 @@
 """Thin tensor-level wrappers over the C ABI (include/varsep_hip.h).  No autograd here; see functional.py."""
+import collections
+import os
+
 import torch
 
 from . import _lib
@@ -365,7 +368,6 @@ def _probe_rollout_exchange(code, B, C, H, nb, device):
     property holds on this device / runtime: keep the 210 ns hops) or leaves the error word raised: then every launch of this process uses
     the agent-scope stores (385 ns hops, any placement).  A mid-run change of the dispatch order is still caught by the epoch tags -> the
     guard word -> skipped optimizer steps -> train.recover_exchange."""
-    import os
     import sys
     key = (device.index, code, B, C, H, nb)
     if key in _XL_PROBED or torch.cuda.is_current_stream_capturing():
@@ -535,6 +537,22 @@ def _conv_out_hw(H, W, k, stride, pad, transposed):
     return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
 
 
+_ConvGeom = collections.namedtuple('_ConvGeom', 'B Cin H W Cout k kw OH OW')
+
+
+def _conv_geom(x_shape, w_shape, stride, pad, transposed):
+    """The geometry of a (transposed) convolution call from its input and weight shapes, computed once per call."""
+    B, Cin, H, W = x_shape
+    k, kw = w_shape[2], w_shape[3]
+    OH, OW = _conv_out_hw(H, W, k, stride, pad, transposed)
+    return _ConvGeom(B, Cin, H, W, w_shape[1] if transposed else w_shape[0], k, kw, OH, OW)
+
+
+def _wgrad_dest(into, out, w_shape, device):
+    """Where a weight gradient goes: the pending gradient it is added to, the tensor that receives it, or a fresh fp32 tensor."""
+    return into if into is not None else (out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=device))
+
+
 def conv_pack_weight(w_master, dtype, stride, pad, out=None):
     """fp32 master weight [D0, D1, k, k] -> packed operand of the transposed-form contractions (compute dtype)."""
     require_cuda(w_master)
@@ -550,7 +568,6 @@ def conv_pack_weight(w_master, dtype, stride, pad, out=None):
 
 def _conv_workspace(x_dtype_code, B, Cin, H, W, Cout, k, stride, pad, device):
     """Transient column-matrix + split-K workspace of a convolution (VS_CONV_COLS=0: none -> gather inside the MFMA loop)."""
-    import os
     if os.environ.get('VS_CONV_COLS') == '0':
         return None
     nbytes = _lib.load_library().vs_conv_workspace_bytes(x_dtype_code, B, Cin, H, W, Cout, k, k, stride, pad)
@@ -624,7 +641,7 @@ def conv_thin_wgrad(big, thin, w_shape, k, stride, sc, sm, flip, into=None, out=
     B, C, H, W = big.shape
     M = thin.shape[1]
     lib = _lib.load_library()
-    dw = into if into is not None else (out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=big.device))
+    dw = _wgrad_dest(into, out, w_shape, big.device)
     ws = _workspace(lib.vs_conv_thin_wgrad_workspace_bytes(B, C, H, W, M, k), big.device)
     e0 = _pb()
     check(lib.vs_conv_thin_wgrad(dtype_code(big), big.data_ptr(), thin.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(into), dw.data_ptr(), sc, sm, flip,
@@ -646,6 +663,37 @@ def _conv_full(x_shape, k, stride, pad, transposed):
     return not transposed and pad == 0 and x_shape[2] == k and x_shape[3] == k
 
 
+def _conv_route(op, code, g, stride, pad, transposed):
+    """The plain route of conv_fwd / conv_dgrad / conv_wgrad (`op`) with operands of type `code`: the first that holds of 'gemm_1x1', 'gemm_full',
+    'thin', 'band_wgrad' (the weight gradient only) and 'cols', as (route, thin plan or None).  No side effects."""
+    x_shape = (g.B, g.Cin, g.H, g.W)
+    if _convt_1x1(x_shape, g.k, stride, pad, transposed):
+        return 'gemm_1x1', None
+    if _conv_full(x_shape, g.k, stride, pad, transposed) and g.kw == g.k:
+        return 'gemm_full', None
+    thin = _thin_plan(op, code, g.B, g.Cin, g.H, g.W, g.Cout, g.OH, g.OW, g.k, stride, pad, transposed) if g.kw == g.k else None
+    if thin is not None:
+        return 'thin', thin
+    if op == 'wgrad' and not transposed and (g.k, stride, pad) == (3, 1, 1) and _wgrad_band_serves(code, g.B, g.Cin, g.H, g.W, g.Cout):
+        return 'band_wgrad', None
+    return 'cols', None
+
+
+def _thin_conv(op, g, thin, big, w, bias, out_dtype, stride):
+    """conv_fwd (big = x) / conv_dgrad (big = dy) on the thin kernel its plan names."""
+    if thin[0] == 'expand':
+        shape = (g.B, g.Cout, g.OH, g.OW) if op == 'fwd' else (g.B, g.Cin, g.H, g.W)
+        return conv_thin_expand(big, w, bias, shape, out_dtype, g.k, stride, *thin[5:], role=op)
+    return conv_thin_reduce(big, w, bias, g.Cout, out_dtype, g.k, stride, *thin[5:], role=op)
+
+
+def _pe_cols(e0, op, g, transposed, tensors):
+    """The profile entry of a column-matrix launch: its name, algorithmic FLOPs and the bytes of the three tensors it reads and writes."""
+    work = g.B * g.Cin * g.H * g.W * g.Cout * g.k * g.k if transposed else g.B * g.Cout * g.OH * g.OW * g.Cin * g.k * g.k
+    _pe(e0, 'vs_conv%s_cols:%s<%s>' % ('T' if transposed else '', op, _DT[dtype_code(tensors[0])]), flops=2.0 * work,
+        nbytes=float(sum(t.numel() * t.element_size() for t in tensors)))
+
+
 # ---- fp32 results from the 16-bit row-band kernels (VARSEP_FP32_SPLIT=1) ---------------------------------------------------------------------
 # The row-band kernels take 16-bit operands, so the fp32 parity tests (1e-3 against the reference's fixture) ran the column-matrix route and
 # never touched the kernels bench.py times.  A convolution is bilinear: with x = x0 + x1 + x2 and w = w0 + w1 + w2 (three bf16 pieces each: the
@@ -658,7 +706,6 @@ _SPLIT_TERMS = ((0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1))
 
 
 def fp32_split_enabled():
-    import os
     return os.environ.get('VARSEP_FP32_SPLIT', '0') == '1'
 
 
@@ -671,72 +718,121 @@ def _split16(t):
     return parts
 
 
-def _conv3_split(x, w, bias, flip, role):
-    """fp32 Conv2d k3 s1 p1 (flip: its input gradient, w [Cout, Cin, 3, 3] applied transposed) through six bf16 row-band launches."""
-    Cout = w.shape[1] if flip else w.shape[0]
-    xs = _split16(x)
-    few = conv3_img16_supported(xs[0], Cout)         # the SST integrator's few 16 x 16 maps: the few-maps kernel (same weight pre-pack)
-    if not few and not conv3_band_supported(xs[0], Cout):
-        return None
-    ws = [conv3_img16_pack_weight(p.float().contiguous(), torch.bfloat16, flip) for p in _split16(w)]
+def _split_route(op, g, fp32, stride, pad, transposed):
+    """The fp32-split candidates of a call in the order they are tried -- the MFMA family of its geometry, then the thin kernels -- or none (not
+    fp32 operands and result, or no VARSEP_FP32_SPLIT=1).  A candidate whose 16-bit kernel does not serve the shape falls to the next one, the
+    last to the plain route."""
+    if not (fp32 and fp32_split_enabled()):
+        return ()
+    family = ()
+    if (g.k, g.kw, stride, pad) == (3, 3, 1, 1) and not transposed:
+        family = ('conv3',)
+    elif (g.k, g.kw, stride, pad) == (4, 4, 2, 1):
+        # Conv2d forward and ConvTranspose2d input gradient gather the large map on its parity planes, the other two scatter (tap kernel)
+        family = ('k4s2',) if op == 'wgrad' else ('gather',) if transposed == (op == 'dgrad') else ('tap',)
+    return family + (('thin',) if g.k == g.kw else ())
+
+
+def _split_sum(term, bias):
+    """The six products term(i, j, bias) summed out of place (forward, input gradient): y = the first term, which takes the bias, then y.add_(t)."""
     y = None
     for i, j in _SPLIT_TERMS:
-        if few:
-            t = slab_sum(conv3_img16(xs[i], ws[j], Cout, role=role), bias if y is None else None, torch.float32)
-        else:
-            t = conv3_band(xs[i], ws[j], bias if y is None else None, Cout, torch.float32, role=role)
+        t = term(i, j, bias if y is None else None)
         y = t if y is None else y.add_(t)
     return y
 
 
-def _k4s2_split_gather(big, w, bias, role):
-    """fp32 k4 s2 p1 gather (Conv2d forward on x / ConvTranspose2d input gradient on dy; w [M, K, 4, 4]) through six launches of the 16-bit
-    parity-plane row-band kernel."""
-    M = w.shape[0]
-    bs = _split16(big)
-    if not conv_k4s2_gather_supported(bs[0], M):
-        return None
-    planes = [space_to_depth2(b) for b in bs]
-    ws = [conv_k4s2_pack_weight(p.float().contiguous(), torch.bfloat16) for p in _split16(w)]
-    y = None
-    for i, j in _SPLIT_TERMS:
-        t = conv_k4s2_gather(planes[i], ws[j], bias if y is None else None, M, torch.float32, role=role)
-        y = t if y is None else y.add_(t)
-    return y
-
-
-def _tap_split(x, w, bias, role):
-    """fp32 k4 s2 p1 SCATTER (ConvTranspose2d forward of x with w [Cin, Cout, 4, 4]; the input gradient of a Conv2d k4 s2 p1 is the same operation
-    on dy with its weight read as [in = Cout, out = Cin]) through six launches of the 16-bit tap kernel with fp32 output."""
-    Cout = w.shape[1]
-    xs = _split16(x)
-    if not convt_tap_supported(xs[0], Cout, 1):
-        return None
-    ws = [convt_tap_pack_weight(p.float().contiguous(), torch.bfloat16) for p in _split16(w)]
-    B, Cin, H, W = x.shape
-    lib = _lib.load_library()
-    y = None
-    for i, j in _SPLIT_TERMS:
-        t = torch.empty((B, Cout, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-        e0 = _pb()
-        check(lib.vs_convt_k4s2_tap_fwd_f32(_lib.BF16, xs[i].data_ptr(), ws[j].data_ptr(), _ptr(bias) if y is None else None, t.data_ptr(), B, Cin, H, W, Cout,
-                                            stream_ptr()), 'vs_convt_k4s2_tap_fwd_f32')
-        _pe(e0, 'vs_convT_tap:%s<bf16>' % role, flops=2.0 * B * H * W * Cin * Cout * 16, nbytes=float(xs[i].numel() * 2 + t.numel() * 4))
-        y = t if y is None else y.add_(t)
-    return y
-
-
-def _k4s2_split_wgrad(small, big, w_shape, into, out):
-    M = w_shape[0]
-    bs = _split16(big)
-    if not conv_k4s2_supported(bs[0], M):
-        return None
-    planes = [space_to_depth2(b) for b in bs]
-    ss = _split16(small)
+def _split_chain(term, into, out):
+    """The six products term(i, j, into, out) of a weight gradient, summed by the launches themselves: the first goes to `into` / `out` / a fresh
+    tensor, every later one is added to that."""
     dw = None
     for i, j in _SPLIT_TERMS:
-        dw = conv_k4s2_wgrad(ss[j], planes[i], w_shape, into=into if dw is None else dw, out=out if dw is None else None)
+        dw = term(i, j, into if dw is None else dw, out if dw is None else None)
     return dw
+
+
+def _tap_f32(x, w_tap, bias, Cout, role):
+    """ConvTranspose2d k4 s2 p1 of 16-bit x through the tap kernel with fp32 output (the Conv2d input gradient is the same operation on dy)."""
+    B, Cin, H, W = x.shape
+    t = torch.empty((B, Cout, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+    e0 = _pb()
+    check(_lib.load_library().vs_convt_k4s2_tap_fwd_f32(_lib.BF16, x.data_ptr(), w_tap.data_ptr(), _ptr(bias), t.data_ptr(), B, Cin, H, W, Cout, stream_ptr()),
+          'vs_convt_k4s2_tap_fwd_f32')
+    _pe(e0, 'vs_convT_tap:%s<bf16>' % role, flops=2.0 * B * H * W * Cin * Cout * 16, nbytes=float(x.numel() * 2 + t.numel() * 4))
+    return t
+
+
+def _conv_split(op, g, big, w, bias, fp32, stride, pad, transposed):
+    """fp32 conv_fwd (big = x) / conv_dgrad (big = dy, no bias) as six launches of a 16-bit kernel on the pieces (bs[i], ws[j]); None when no
+    split candidate serves the call.  M: the channels of the result."""
+    M = g.Cout if op == 'fwd' else g.Cin
+    for name in _split_route(op, g, fp32, stride, pad, transposed):
+        if name == 'thin':
+            # the thin-channel edge layers (first encoder / last decoder convolution): the same six products on the VALU kernels
+            thin = _thin_plan(op, BF16, g.B, g.Cin, g.H, g.W, g.Cout, g.OH, g.OW, g.k, stride, pad, transposed)
+            if thin is None:
+                continue
+            bs, ws = _split16(big), _split16(w)
+            term = lambda i, j, b: _thin_conv(op, g, thin, bs[i], ws[j], b, torch.float32, stride)
+        elif name == 'conv3':
+            # Conv2d k3 s1 p1 (its input gradient: w [Cout, Cin, 3, 3] applied flipped) on the row-band kernel
+            bs = _split16(big)
+            few = conv3_img16_supported(bs[0], M)            # the SST integrator's few 16 x 16 maps: the few-maps kernel (same weight pre-pack)
+            if not few and not conv3_band_supported(bs[0], M):
+                continue
+            ws = [conv3_img16_pack_weight(p.float().contiguous(), torch.bfloat16, op == 'dgrad') for p in _split16(w)]
+            if few:
+                term = lambda i, j, b: slab_sum(conv3_img16(bs[i], ws[j], M, role=op), b, torch.float32)
+            else:
+                term = lambda i, j, b: conv3_band(bs[i], ws[j], b, M, torch.float32, role=op)
+        elif name == 'gather':
+            # k4 s2 p1 gather (Conv2d forward on x / ConvTranspose2d input gradient on dy; w [M, K, 4, 4]) on the parity planes
+            bs = _split16(big)
+            if not conv_k4s2_gather_supported(bs[0], M):
+                continue
+            planes = [space_to_depth2(b) for b in bs]
+            ws = [conv_k4s2_pack_weight(p.float().contiguous(), torch.bfloat16) for p in _split16(w)]
+            term = lambda i, j, b: conv_k4s2_gather(planes[i], ws[j], b, M, torch.float32, role=op)
+        else:
+            # k4 s2 p1 SCATTER (ConvTranspose2d forward of x with w [Cin, Cout, 4, 4]; the input gradient of a Conv2d is the same operation on
+            # dy with its weight [Cout, Cin, 4, 4] read as [in = Cout, out = Cin]) on the tap kernel
+            bs = _split16(big)
+            if not convt_tap_supported(bs[0], M, 1):
+                continue
+            ws = [convt_tap_pack_weight(p.float().contiguous(), torch.bfloat16) for p in _split16(w)]
+            term = lambda i, j, b: _tap_f32(bs[i], ws[j], b, M, op)
+        return _split_sum(term, bias)
+    return None
+
+
+def _wgrad_split(g, dy, x, w_shape, stride, pad, transposed, into, out):
+    """fp32 conv_wgrad as six launches of a 16-bit kernel, accumulated by the kernels' own finishing pass (`into`); None when no split
+    candidate serves the call.  dW is bilinear in (dy, x): the same six products."""
+    for name in _split_route('wgrad', g, x.dtype == torch.float32, stride, pad, transposed):
+        if name == 'conv3':
+            xs = _split16(x)
+            if not conv3_wgrad_band_supported(xs[0], g.Cout):
+                continue
+            ds = _split16(dy)
+            term = lambda i, j, into_, out_: conv_wgrad(ds[j], xs[i], w_shape, stride, pad, transposed, into=into_, out=out_)
+        elif name == 'k4s2':
+            # k4 s2 p1: the LARGE map (x of a Conv2d, dy of a ConvTranspose2d) on its parity planes, the small one as it is
+            big, small = (dy, x) if transposed else (x, dy)
+            bs = _split16(big)
+            if not conv_k4s2_supported(bs[0], w_shape[0]):
+                continue
+            planes = [space_to_depth2(b) for b in bs]
+            ss = _split16(small)
+            term = lambda i, j, into_, out_: conv_k4s2_wgrad(ss[j], planes[i], w_shape, into=into_, out=out_)
+        else:
+            thin = _thin_plan('wgrad', BF16, g.B, g.Cin, g.H, g.W, g.Cout, g.OH, g.OW, g.k, stride, pad, transposed)
+            if thin is None:
+                continue
+            big, small = (dy, x) if thin[0] == 'wgrad_big_dy' else (x, dy)
+            bs, ss = _split16(big), _split16(small)
+            term = lambda i, j, into_, out_: conv_thin_wgrad(bs[i], ss[j], w_shape, g.k, stride, *thin[5:], into=into_, out=out_)
+        return _split_chain(term, into, out)
+    return None
 
 
 def conv_fwd(x, w, bias, stride, pad, transposed, out_dtype, w_packed=None):
@@ -744,70 +840,33 @@ def conv_fwd(x, w, bias, stride, pad, transposed, out_dtype, w_packed=None):
     The transposed form consumes `w_packed` (conv_pack_weight); it is built on the fly from `w` when not given."""
     require_cuda(x, w, bias)
     assert x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype
-    if (x.dtype == torch.float32 and out_dtype == torch.float32 and not transposed and tuple(w.shape[2:]) == (3, 3) and stride == 1 and pad == 1
-            and fp32_split_enabled()):
-        y = _conv3_split(x, w, bias, False, 'fwd')
-        if y is not None:
-            return y
-    if (x.dtype == torch.float32 and out_dtype == torch.float32 and not transposed and tuple(w.shape[2:]) == (4, 4) and stride == 2 and pad == 1
-            and fp32_split_enabled()):
-        y = _k4s2_split_gather(x, w, bias, 'fwd')
-        if y is not None:
-            return y
-    if (x.dtype == torch.float32 and out_dtype == torch.float32 and transposed and tuple(w.shape[2:]) == (4, 4) and stride == 2 and pad == 1
-            and fp32_split_enabled()):
-        y = _tap_split(x, w, bias, 'fwd')
-        if y is not None:
-            return y
-    if x.dtype == torch.float32 and out_dtype == torch.float32 and w.shape[2] == w.shape[3] and fp32_split_enabled():
-        # the thin-channel edge layers (first encoder / last decoder convolution): the same six products on the VALU kernels
-        B_, Cin_, H_, W_ = x.shape
-        k_ = w.shape[2]
-        Cout_ = w.shape[1] if transposed else w.shape[0]
-        OH_, OW_ = _conv_out_hw(H_, W_, k_, stride, pad, transposed)
-        thin = _thin_plan('fwd', BF16, B_, Cin_, H_, W_, Cout_, OH_, OW_, k_, stride, pad, transposed)
-        if thin is not None:
-            xs, ws, y = _split16(x), _split16(w), None
-            for i, j in _SPLIT_TERMS:
-                b_ = bias if y is None else None
-                t = (conv_thin_expand(xs[i], ws[j], b_, (B_, Cout_, OH_, OW_), torch.float32, k_, stride, *thin[5:]) if thin[0] == 'expand'
-                     else conv_thin_reduce(xs[i], ws[j], b_, Cout_, torch.float32, k_, stride, *thin[5:]))
-                y = t if y is None else y.add_(t)
-            return y
-    if transposed:
-        if w_packed is None:
-            w_packed = conv_pack_weight(w.float().contiguous(), x.dtype, stride, pad)
-        w_arg = w_packed
-    else:
-        w_arg = w
-    B, Cin, H, W = x.shape
-    k = w.shape[2]
-    Cout = w.shape[1] if transposed else w.shape[0]
-    OH, OW = _conv_out_hw(H, W, k, stride, pad, transposed)
-    if _convt_1x1(x.shape, k, stride, pad, transposed):
+    g = _conv_geom(x.shape, w.shape, stride, pad, transposed)
+    y = _conv_split('fwd', g, x, w, bias, x.dtype == torch.float32 and out_dtype == torch.float32, stride, pad, transposed)
+    if y is not None:
+        return y
+    if transposed and w_packed is None:
+        w_packed = conv_pack_weight(w.float().contiguous(), x.dtype, stride, pad)
+    route, thin = _conv_route('fwd', dtype_code(x), g, stride, pad, transposed)
+    B, Cin, H, W, Cout, k, kw, OH, OW = g
+    if route == 'gemm_1x1':
         # y[b][(co, ky, kx)] = sum_ci x[b][ci] w[ci][(co, ky, kx)] + bias[co]
-        n = Cout * k * w.shape[3]
-        brep = bias.repeat_interleave(k * w.shape[3]) if bias is not None else None
+        n = Cout * k * kw
+        brep = bias.repeat_interleave(k * kw) if bias is not None else None
         y = gemm(x.view(B, Cin), LAYOUT_R, w.view(Cin, n), LAYOUT_S, B, n, Cin, out_dtype=out_dtype, bias=brep)
-        return y.view(B, Cout, k, w.shape[3])
-    if _conv_full(x.shape, k, stride, pad, transposed) and w.shape[3] == k:
+        return y.view(B, Cout, k, kw)
+    if route == 'gemm_full':
         n = Cin * k * k
         return gemm(x.view(B, n), LAYOUT_R, w.view(Cout, n), LAYOUT_R, B, Cout, n, out_dtype=out_dtype, bias=bias).view(B, Cout, 1, 1)
-    thin = _thin_plan('fwd', dtype_code(x), B, Cin, H, W, Cout, OH, OW, k, stride, pad, transposed) if w.shape[2] == w.shape[3] else None
-    if thin is not None:
-        if thin[0] == 'expand':
-            return conv_thin_expand(x, w, bias, (B, Cout, OH, OW), out_dtype, k, stride, *thin[5:])
-        return conv_thin_reduce(x, w, bias, Cout, out_dtype, k, stride, *thin[5:])
+    if route == 'thin':
+        return _thin_conv('fwd', g, thin, x, w, bias, out_dtype, stride)
     y = torch.empty((B, Cout, OH, OW), dtype=out_dtype, device=x.device)
     lib = _lib.load_library()
     fn = lib.vs_conv_transpose2d_fwd if transposed else lib.vs_conv2d_fwd
     ws = _conv_workspace(dtype_code(x), B, Cin, H, W, Cout, k, stride, pad, x.device)
     e0 = _pb()
-    check(fn(dtype_code(x), x.data_ptr(), w_arg.data_ptr(), _ptr(bias), y.data_ptr(), dtype_code(y), B, Cin, H, W, Cout, k, k,
+    check(fn(dtype_code(x), x.data_ptr(), (w_packed if transposed else w).data_ptr(), _ptr(bias), y.data_ptr(), dtype_code(y), B, Cin, H, W, Cout, k, k,
              stride, pad, _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr()), 'vs_conv_fwd')
-    _pe(e0, 'vs_conv%s_cols:fwd<%s>' % ('T' if transposed else '', _DT[dtype_code(x)]),
-        flops=2.0 * B * Cout * OH * OW * Cin * k * k if not transposed else 2.0 * B * Cin * H * W * Cout * k * k,
-        nbytes=float(x.numel() * x.element_size() + w.numel() * w.element_size() + y.numel() * y.element_size()))
+    _pe_cols(e0, 'fwd', g, transposed, (x, w, y))
     return y
 
 
@@ -816,91 +875,76 @@ def conv_dgrad(dy, w, x_shape, stride, pad, transposed, out_dtype, w_packed=None
     matrix instead of gathering dy a second time."""
     require_cuda(dy, w)
     assert dy.is_contiguous() and w.is_contiguous() and dy.dtype == w.dtype
-    if (dy.dtype == torch.float32 and out_dtype == torch.float32 and not transposed and tuple(w.shape[2:]) == (3, 3) and stride == 1 and pad == 1
-            and fp32_split_enabled()):
-        dx = _conv3_split(dy, w, None, True, 'dgrad')
-        if dx is not None:
-            return dx
-    if (dy.dtype == torch.float32 and out_dtype == torch.float32 and transposed and tuple(w.shape[2:]) == (4, 4) and stride == 2 and pad == 1
-            and fp32_split_enabled()):
-        dx = _k4s2_split_gather(dy, w, None, 'dgrad')
-        if dx is not None:
-            return dx
-    if (dy.dtype == torch.float32 and out_dtype == torch.float32 and not transposed and tuple(w.shape[2:]) == (4, 4) and stride == 2 and pad == 1
-            and fp32_split_enabled()):
-        dx = _tap_split(dy, w, None, 'dgrad')        # w [Cout, Cin, 4, 4] read as a ConvTranspose2d weight [in = Cout, out = Cin]
-        if dx is not None:
-            return dx
-    if dy.dtype == torch.float32 and out_dtype == torch.float32 and w.shape[2] == w.shape[3] and fp32_split_enabled():
-        B_, Cin_, H_, W_ = x_shape
-        k_ = w.shape[2]
-        Cout_ = w.shape[1] if transposed else w.shape[0]
-        thin = _thin_plan('dgrad', BF16, B_, Cin_, H_, W_, Cout_, dy.shape[2], dy.shape[3], k_, stride, pad, transposed)
-        if thin is not None:
-            ds, ws, dx = _split16(dy), _split16(w), None
-            for i, j in _SPLIT_TERMS:
-                t = conv_thin_expand(ds[i], ws[j], None, (B_, Cin_, H_, W_), torch.float32, k_, stride, *thin[5:], role='dgrad')
-                dx = t if dx is None else dx.add_(t)
-            return dx
-    if not transposed:
-        if w_packed is None:
-            w_packed = conv_pack_weight(w.float().contiguous(), dy.dtype, stride, pad)
-        w_arg = w_packed
-    else:
-        w_arg = w
-    B, Cin, H, W = x_shape
-    k = w.shape[2]
-    Cout = w.shape[1] if transposed else w.shape[0]
-    if _convt_1x1(x_shape, k, stride, pad, transposed):
+    g = _conv_geom(x_shape, w.shape, stride, pad, transposed)
+    assert tuple(dy.shape[2:]) == (g.OH, g.OW), (tuple(dy.shape), g)
+    dx = _conv_split('dgrad', g, dy, w, None, dy.dtype == torch.float32 and out_dtype == torch.float32, stride, pad, transposed)
+    if dx is not None:
+        return dx
+    if not transposed and w_packed is None:
+        w_packed = conv_pack_weight(w.float().contiguous(), dy.dtype, stride, pad)
+    route, thin = _conv_route('dgrad', dtype_code(dy), g, stride, pad, transposed)
+    B, Cin, H, W, Cout, k, kw, OH, OW = g
+    if route == 'gemm_1x1':
         # dx[b][ci] = sum_j dy[b][j] w[ci][j], j = (co, ky, kx)
-        n = Cout * k * w.shape[3]
+        n = Cout * k * kw
         return gemm(dy.view(B, n), LAYOUT_R, w.view(Cin, n), LAYOUT_R, B, Cin, n, out_dtype=out_dtype).view(B, Cin, 1, 1)
-    if _conv_full(x_shape, k, stride, pad, transposed) and w.shape[3] == k:
+    if route == 'gemm_full':
         # dx[b][j] = sum_co dy[b][co] w[co][j]
         n = Cin * k * k
         return gemm(dy.view(B, Cout), LAYOUT_R, w.view(Cout, n), LAYOUT_S, B, n, Cout, out_dtype=out_dtype).view(B, Cin, k, k)
-    thin = (_thin_plan('dgrad', dtype_code(dy), B, Cin, H, W, Cout, dy.shape[2], dy.shape[3], k, stride, pad, transposed)
-            if w.shape[2] == w.shape[3] else None)
-    if thin is not None:
-        return conv_thin_expand(dy, w, None, (B, Cin, H, W), out_dtype, k, stride, *thin[5:], role='dgrad')
+    if route == 'thin':
+        return _thin_conv('dgrad', g, thin, dy, w, None, out_dtype, stride)
     dx = torch.empty((B, Cin, H, W), dtype=out_dtype, device=dy.device)
     lib = _lib.load_library()
     fn = lib.vs_conv_transpose2d_dgrad if transposed else lib.vs_conv2d_dgrad
     ws = _conv_workspace(dtype_code(dy), B, Cin, H, W, Cout, k, stride, pad, dy.device)
     e0 = _pb()
     extra = (int(bool(cols_from_wgrad)),) if transposed else ()
-    check(fn(dtype_code(dy), dy.data_ptr(), w_arg.data_ptr(), dx.data_ptr(), dtype_code(dx), B, Cin, H, W, Cout, k, k, stride, pad,
+    check(fn(dtype_code(dy), dy.data_ptr(), (w if transposed else w_packed).data_ptr(), dx.data_ptr(), dtype_code(dx), B, Cin, H, W, Cout, k, k, stride, pad,
              _ptr(ws), ws.numel() if ws is not None else 0, *extra, stream_ptr()), 'vs_conv_dgrad')
-    OH, OW = dy.shape[2], dy.shape[3]
-    _pe(e0, 'vs_conv%s_cols:dgrad<%s>' % ('T' if transposed else '', _DT[dtype_code(dy)]),
-        flops=2.0 * B * Cout * OH * OW * Cin * k * k if not transposed else 2.0 * B * Cin * H * W * Cout * k * k,
-        nbytes=float(dy.numel() * dy.element_size() + w.numel() * w.element_size() + dx.numel() * dx.element_size()))
+    _pe_cols(e0, 'dgrad', g, transposed, (dy, w, dx))
     return dx
+
+
+def _wgrad_band_serves(code, B, Cin, H, W, Cout):
+    """Whether the row-band kernel serves the weight gradient of Conv2d k3 s1 p1 on 16-bit maps [B, Cin, H, W].  VS_CONV_WGRAD_BAND=0: never."""
+    if os.environ.get('VS_CONV_WGRAD_BAND') == '0' or code == F32 or (Cin * Cout * 9) % 4 != 0:
+        return False
+    return bool(_lib.load_library().vs_conv3_wgrad_band_supported(code, B, Cin, H, W, Cout))
 
 
 def conv3_wgrad_band_supported(x, Cout, dtype_code_of=None):
     """Whether the weight gradient of Conv2d k3 s1 p1 with input `x` takes the row-band kernel (no column matrix).  VS_CONV_WGRAD_BAND=0: never.
     (`x` may be a meta tensor that only carries the shape; then `dtype_code_of` is the operand type code.)"""
-    import os
-    if os.environ.get('VS_CONV_WGRAD_BAND') == '0' or x.dtype == torch.float32 or x.dim() != 4:
+    if x.dtype == torch.float32 or x.dim() != 4:
         return False
-    B, Cin, H, W = x.shape
-    if (Cin * Cout * 9) % 4 != 0:
-        return False
-    return bool(_lib.load_library().vs_conv3_wgrad_band_supported(dtype_code_of if dtype_code_of is not None else dtype_code(x), B, Cin, H, W, Cout))
+    return _wgrad_band_serves(dtype_code_of if dtype_code_of is not None else dtype_code(x), *x.shape, Cout)
 
 
-def _slab_reduce(slabs, nslabs, w_shape, into, dw):
+def _slab_reduce(slabs, nslabs, w_shape, into, dw, finish='vs_conv3_wgrad_band_finish'):
     """dw = sum of `nslabs` fp32 partial gradients (+ the pending gradient `into`); two passes when a small weight has many slabs."""
     lib = _lib.load_library()
     src, n = slabs, nslabs
     if nslabs > 24:
         # many slabs of a small weight: a first pass in 16 groups (every workgroup adds <= nslabs / 16 coalesced slabs), then the 16 partials
-        src = torch.empty((16,) + tuple(w_shape), dtype=torch.float32, device=slabs.device)
-        check(lib.vs_slab_sum_grouped(slabs.data_ptr(), nslabs, 16, src.data_ptr(), dw.numel(), stream_ptr()), 'vs_slab_sum_grouped')
+        src = torch.empty((16,) + tuple(slabs.shape[1:]), dtype=torch.float32, device=slabs.device)
+        check(lib.vs_slab_sum_grouped(slabs.data_ptr(), nslabs, 16, src.data_ptr(), slabs.numel() // nslabs, stream_ptr()), 'vs_slab_sum_grouped')
         n = -(-nslabs // (-(-nslabs // 16)))          # groups that received slabs: ceil(nslabs / per)
-    # the slabs are laid out [tap][Cout][Cin] (coalesced stores in the kernel): the last pass transposes into the weight's [Cout][Cin][3][3]
-    check(lib.vs_conv3_wgrad_band_finish(src.data_ptr(), n, _ptr(into), dw.data_ptr(), w_shape[0], w_shape[1], stream_ptr()), 'vs_conv3_wgrad_band_finish')
+    # the slabs are laid out [tap][Cout][Cin] (coalesced stores in the kernel): the last pass transposes into the weight's own layout
+    check(getattr(lib, finish)(src.data_ptr(), n, _ptr(into), dw.data_ptr(), w_shape[0], w_shape[1], stream_ptr()), finish)
+
+
+def _wgrad_band(launch, code, B, Cin, H, W, w_shape, into, dw, operand_bytes):
+    """3x3 on maps of width 4 .. 64: row bands in LDS, no column matrix; `launch(lib, slabs pointer)` leaves partial gradients in slabs, one
+    (or two) launches add them into dw."""
+    lib = _lib.load_library()
+    nslabs = lib.vs_conv3_wgrad_band_slabs(B, Cin, H, W, w_shape[0])
+    slabs = torch.empty((nslabs,) + tuple(w_shape), dtype=torch.float32, device=dw.device)
+    e0 = _pb()
+    launch(lib, slabs.data_ptr())
+    _slab_reduce(slabs, nslabs, w_shape, into, dw)
+    _pe(e0, 'vs_conv3_wgrad_band<%s>' % _DT[code], flops=2.0 * B * w_shape[0] * H * W * Cin * 9, nbytes=float(operand_bytes + slabs.numel() * 8))
+    return dw
 
 
 def conv3_wgrad_band_pieces(pairs, w_shape, into=None):
@@ -915,21 +959,14 @@ def conv3_wgrad_band_pieces(pairs, w_shape, into=None):
     if (W == 8 and mp % 4 != 0) or (W == 4 and mp % 16 != 0) or n > 64 or any(p[0].shape != dz0.shape or p[1].shape != x0.shape or not p[0].is_contiguous() or not p[1].is_contiguous()
                      or p[0].dtype != x0.dtype or p[1].dtype != x0.dtype for p in pairs):
         return None
-    if not conv3_wgrad_band_supported(torch.empty((n * mp, Cin, H, W), dtype=x0.dtype, device='meta'), Cout, dtype_code_of=dtype_code(x0)):
+    if not _wgrad_band_serves(dtype_code(x0), n * mp, Cin, H, W, Cout):
         return None
-    lib = _lib.load_library()
-    B = n * mp
-    nslabs = lib.vs_conv3_wgrad_band_slabs(B, Cin, H, W, Cout)
-    slabs = torch.empty((nslabs,) + tuple(w_shape), dtype=torch.float32, device=x0.device)
-    dw = into if into is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x0.device)
     xs = (ctypes.c_void_p * n)(*[p[1].data_ptr() for p in pairs])
     dzs = (ctypes.c_void_p * n)(*[p[0].data_ptr() for p in pairs])
-    e0 = _pb()
-    check(lib.vs_conv3_wgrad_band_pieces(dtype_code(x0), n, xs, dzs, mp, slabs.data_ptr(), Cin, H, W, Cout, stream_ptr()), 'vs_conv3_wgrad_band_pieces')
-    _slab_reduce(slabs, nslabs, w_shape, into, dw)
-    _pe(e0, 'vs_conv3_wgrad_band<%s>' % _DT[dtype_code(x0)], flops=2.0 * B * Cout * H * W * Cin * 9,
-        nbytes=float(n * (dz0.numel() + x0.numel()) * x0.element_size() + slabs.numel() * 8))
-    return dw
+    return _wgrad_band(lambda lib, slabs: check(lib.vs_conv3_wgrad_band_pieces(dtype_code(x0), n, xs, dzs, mp, slabs, Cin, H, W, Cout, stream_ptr()),
+                                                'vs_conv3_wgrad_band_pieces'),
+                       dtype_code(x0), n * mp, Cin, H, W, w_shape, into, _wgrad_dest(into, None, w_shape, x0.device),
+                       n * (dz0.numel() + x0.numel()) * x0.element_size())
 
 
 def conv_wgrad(dy, x, w_shape, stride, pad, transposed, into=None, out=None):
@@ -937,76 +974,45 @@ def conv_wgrad(dy, x, w_shape, stride, pad, transposed, into=None, out=None):
     (in the GEMM / split-K epilogue) instead of a fresh tensor; `out`: an fp32 tensor that receives it."""
     require_cuda(dy, x)
     assert dy.is_contiguous() and x.is_contiguous() and dy.dtype == x.dtype
-    B, Cin, H, W = x.shape
-    k = w_shape[2]
-    Cout = w_shape[1] if transposed else w_shape[0]
-    OH, OW = dy.shape[2], dy.shape[3]
+    g = _conv_geom(x.shape, w_shape, stride, pad, transposed)
+    assert tuple(dy.shape[2:]) == (g.OH, g.OW), (tuple(dy.shape), g)
     if into is not None:
         assert into.dtype == torch.float32 and into.is_contiguous() and tuple(into.shape) == tuple(w_shape)
     if out is not None:
         assert into is None and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(w_shape)
-    if (x.dtype == torch.float32 and not transposed and tuple(w_shape[2:]) == (3, 3) and stride == 1 and pad == 1 and fp32_split_enabled()):
-        xs = _split16(x)
-        if conv3_wgrad_band_supported(xs[0], Cout):
-            # dW is bilinear in (dy, x): the same six products, accumulated by the band kernel's own finishing pass (`into`)
-            ds = _split16(dy)
-            dw = None
-            for i, j in _SPLIT_TERMS:
-                dw = conv_wgrad(ds[j], xs[i], w_shape, stride, pad, transposed, into=into if dw is None else dw, out=out if dw is None else None)
-            return dw
-    if x.dtype == torch.float32 and tuple(w_shape[2:]) == (4, 4) and stride == 2 and pad == 1 and fp32_split_enabled():
-        # k4 s2 p1: the LARGE map (x of a Conv2d, dy of a ConvTranspose2d) on its parity planes, the small one as it is
-        dw = _k4s2_split_wgrad(x, dy, w_shape, into, out) if transposed else _k4s2_split_wgrad(dy, x, w_shape, into, out)
-        if dw is not None:
-            return dw
-    if x.dtype == torch.float32 and w_shape[2] == w_shape[3] and fp32_split_enabled():
-        thin = _thin_plan('wgrad', BF16, B, Cin, H, W, Cout, OH, OW, k, stride, pad, transposed)
-        if thin is not None:
-            big, small = (dy, x) if thin[0] == 'wgrad_big_dy' else (x, dy)
-            bs, ss, dw = _split16(big), _split16(small), None
-            for i, j in _SPLIT_TERMS:
-                dw = conv_thin_wgrad(bs[i], ss[j], w_shape, k, stride, *thin[5:], into=into if dw is None else dw, out=out if dw is None else None)
-            return dw
-    if _convt_1x1(x.shape, k, stride, pad, transposed):
-        # dW[ci][j] (+)= sum_b x[b][ci] dy[b][j]
-        n = Cout * k * w_shape[3]
-        dw = into if into is not None else (out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device))
-        gemm(x.view(B, Cin), LAYOUT_S, dy.view(B, n), LAYOUT_S, Cin, n, B, out=dw.view(Cin, n), accumulate=into is not None)
+    dw = _wgrad_split(g, dy, x, w_shape, stride, pad, transposed, into, out)
+    if dw is not None:
         return dw
-    if _conv_full(x.shape, k, stride, pad, transposed) and w_shape[3] == k:
-        # dW[co][j] (+)= sum_b dy[b][co] x[b][j]
-        n = Cin * k * k
-        dw = into if into is not None else (out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device))
-        gemm(dy.view(B, Cout), LAYOUT_S, x.view(B, n), LAYOUT_S, Cout, n, B, out=dw.view(Cout, n), accumulate=into is not None)
-        return dw
-    thin = _thin_plan('wgrad', dtype_code(x), B, Cin, H, W, Cout, OH, OW, k, stride, pad, transposed) if w_shape[2] == w_shape[3] else None
-    if thin is not None:
+    route, thin = _conv_route('wgrad', dtype_code(x), g, stride, pad, transposed)
+    B, Cin, H, W, Cout, k, kw, OH, OW = g
+    if route == 'thin':
         big, small = (dy, x) if thin[0] == 'wgrad_big_dy' else (x, dy)
         return conv_thin_wgrad(big, small, w_shape, k, stride, *thin[5:], into=into, out=out)
-    dw = into if into is not None else (out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device))
-    lib = _lib.load_library()
-    if not transposed and k == 3 and stride == 1 and pad == 1 and conv3_wgrad_band_supported(x, Cout):
-        # 3x3 on maps of width 16 / 32 / 64: row bands in LDS, no column matrix; partial gradients in slabs, one launch adds them
-        nslabs = lib.vs_conv3_wgrad_band_slabs(B, Cin, H, W, Cout)
-        slabs = torch.empty((nslabs,) + tuple(w_shape), dtype=torch.float32, device=x.device)
+    dw = _wgrad_dest(into, out, w_shape, x.device)
+    if route == 'gemm_1x1':
+        # dW[ci][j] (+)= sum_b x[b][ci] dy[b][j]
+        n = Cout * k * kw
+        gemm(x.view(B, Cin), LAYOUT_S, dy.view(B, n), LAYOUT_S, Cin, n, B, out=dw.view(Cin, n), accumulate=into is not None)
+    elif route == 'gemm_full':
+        # dW[co][j] (+)= sum_b dy[b][co] x[b][j]
+        n = Cin * k * k
+        gemm(dy.view(B, Cout), LAYOUT_S, x.view(B, n), LAYOUT_S, Cout, n, B, out=dw.view(Cout, n), accumulate=into is not None)
+    elif route == 'band_wgrad':
+        _wgrad_band(lambda lib, slabs: check(lib.vs_conv3_wgrad_band(dtype_code(x), x.data_ptr(), dy.data_ptr(), slabs, B, Cin, H, W, Cout, stream_ptr()),
+                                             'vs_conv3_wgrad_band'),
+                    dtype_code(x), B, Cin, H, W, w_shape, into, dw, (dy.numel() + x.numel()) * x.element_size())
+    else:
+        lib = _lib.load_library()
+        ws = _conv_workspace(dtype_code(x), B, Cin, H, W, Cout, k, stride, pad, x.device)
+        if ws is None:
+            pix_h, pix_w = (H, W) if transposed else (OH, OW)
+            ws_bytes = lib.vs_conv_wgrad_workspace_bytes(B, Cin, pix_h, pix_w, Cout, k, k)
+            ws = _workspace(ws_bytes, x.device) if ws_bytes else None
+        fn = lib.vs_conv_transpose2d_wgrad_acc if transposed else lib.vs_conv2d_wgrad_acc
         e0 = _pb()
-        check(lib.vs_conv3_wgrad_band(dtype_code(x), x.data_ptr(), dy.data_ptr(), slabs.data_ptr(), B, Cin, H, W, Cout, stream_ptr()), 'vs_conv3_wgrad_band')
-        _slab_reduce(slabs, nslabs, w_shape, into, dw)
-        _pe(e0, 'vs_conv3_wgrad_band<%s>' % _DT[dtype_code(x)], flops=2.0 * B * Cout * OH * OW * Cin * 9,
-            nbytes=float(dy.numel() * dy.element_size() + x.numel() * x.element_size() + slabs.numel() * 8))
-        return dw
-    pix_h, pix_w = (H, W) if transposed else (OH, OW)
-    ws = _conv_workspace(dtype_code(x), B, Cin, H, W, Cout, k, stride, pad, x.device)
-    if ws is None:
-        ws_bytes = lib.vs_conv_wgrad_workspace_bytes(B, Cin, pix_h, pix_w, Cout, k, k)
-        ws = _workspace(ws_bytes, x.device) if ws_bytes else None
-    fn = lib.vs_conv_transpose2d_wgrad_acc if transposed else lib.vs_conv2d_wgrad_acc
-    e0 = _pb()
-    check(fn(dtype_code(x), dy.data_ptr(), x.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, k, k, stride, pad, _ptr(ws),
-             ws.numel() if ws is not None else 0, 1 if into is not None else 0, stream_ptr()), 'vs_conv_wgrad')
-    _pe(e0, 'vs_conv%s_cols:wgrad<%s>' % ('T' if transposed else '', _DT[dtype_code(x)]),
-        flops=2.0 * B * Cout * OH * OW * Cin * k * k if not transposed else 2.0 * B * Cin * H * W * Cout * k * k,
-        nbytes=float(dy.numel() * dy.element_size() + x.numel() * x.element_size() + dw.numel() * 4))
+        check(fn(dtype_code(x), dy.data_ptr(), x.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, k, k, stride, pad, _ptr(ws),
+                 ws.numel() if ws is not None else 0, 1 if into is not None else 0, stream_ptr()), 'vs_conv_wgrad')
+        _pe_cols(e0, 'wgrad', g, transposed, (dy, x, dw))
     return dw
 
 
@@ -1015,14 +1021,10 @@ def conv_k4s2_supported(big, M):
     """Whether the gather-type operations of a k4 s2 p1 (transposed) convolution on the LARGE map `big` [B, C, H, W] -- Conv2d forward /
     weight gradient (big = the input, M = Cout), ConvTranspose2d input / weight gradient (big = the output gradient, M = Cin) -- run on
     the parity planes of `big` with the row-band kernels (no column matrix)."""
-    if big.dtype == torch.float32 or big.dim() != 4:
+    if not conv_k4s2_gather_supported(big, M):
         return False
     B, C, H, W = big.shape
-    lib = _lib.load_library()
-    code = dtype_code(big)
-    if C % 16 != 0 or not lib.vs_space_to_depth2_supported(code, B, C, H, W):       # (the plane pre-packs hold whole 64-channel phases)
-        return False
-    return bool(lib.vs_conv3_band_supported(code, B, 4 * C, H // 2, W // 2, M)) and bool(lib.vs_conv3_wgrad_band_supported(code, B, 4 * C, H // 2, W // 2, M))
+    return bool(_lib.load_library().vs_conv3_wgrad_band_supported(dtype_code(big), B, 4 * C, H // 2, W // 2, M))
 
 
 def conv_k4s2_gather_supported(big, M):
@@ -1033,7 +1035,7 @@ def conv_k4s2_gather_supported(big, M):
     B, C, H, W = big.shape
     lib = _lib.load_library()
     code = dtype_code(big)
-    return (C % 16 == 0 and bool(lib.vs_space_to_depth2_supported(code, B, C, H, W))
+    return (C % 16 == 0 and bool(lib.vs_space_to_depth2_supported(code, B, C, H, W))       # (the plane pre-packs hold whole 64-channel phases)
             and bool(lib.vs_conv3_band_supported(code, B, 4 * C, H // 2, W // 2, M)))
 
 
@@ -1086,7 +1088,7 @@ def conv_k4s2_wgrad(small, planes, w_shape, into=None, out=None):
     K = planes.shape[1] // 4
     assert tuple(w_shape) == (M, K, 4, 4), (tuple(w_shape), M, K)
     lib = _lib.load_library()
-    dw = into if into is not None else (out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=small.device))
+    dw = _wgrad_dest(into, out, w_shape, small.device)
     assert dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == tuple(w_shape)
     nslabs = lib.vs_conv_k4s2_wgrad_band_slabs(B, K, H, W, M)
     n3 = M * 4 * K * 9
@@ -1094,12 +1096,7 @@ def conv_k4s2_wgrad(small, planes, w_shape, into=None, out=None):
     e0 = _pb()
     check(lib.vs_conv_k4s2_wgrad_band(dtype_code(planes), planes.data_ptr(), small.data_ptr(), slabs.data_ptr(), B, K, H, W, M, stream_ptr()),
           'vs_conv_k4s2_wgrad_band')
-    src, n = slabs, nslabs
-    if nslabs > 24:
-        src = torch.empty((16, n3), dtype=torch.float32, device=small.device)
-        check(lib.vs_slab_sum_grouped(slabs.data_ptr(), nslabs, 16, src.data_ptr(), n3, stream_ptr()), 'vs_slab_sum_grouped')
-        n = -(-nslabs // (-(-nslabs // 16)))
-    check(lib.vs_conv_k4s2_wgrad_finish(src.data_ptr(), n, _ptr(into), dw.data_ptr(), M, K, stream_ptr()), 'vs_conv_k4s2_wgrad_finish')
+    _slab_reduce(slabs, nslabs, w_shape, into, dw, finish='vs_conv_k4s2_wgrad_finish')
     _pe(e0, 'vs_conv_k4s2:wgrad<%s>' % _DT[dtype_code(planes)], flops=2.0 * B * H * W * M * K * 16,
         nbytes=float(small.numel() * small.element_size() + planes.numel() * planes.element_size() + slabs.numel() * 8))
     return dw
@@ -1249,7 +1246,6 @@ def band_bn_mode():
     HBM rate (11-80 us per layer), while the epilogue reduction (32 lanes x 16 channels x 2 sums per wave through cross-lane moves, behind the
     x shift of the result) lengthens every convolution launch -- same-box A/B of the replayed steps: TaxiBJ 8.13 (pass) / 8.33 (table) /
     10.7 ms (atomics), SST 20.22 / 20.67 / 22.9, Moving-MNIST 7.07 / 7.09."""
-    import os
     return os.environ.get('VS_BAND_BN_SUMS', '0')
 
 
@@ -1416,7 +1412,6 @@ def bn_stats_ub(x, eps=1e-5, groups=1):
 
 
 def bn_small_groups_enabled():
-    import os
     return os.environ.get('VS_BN_SMALL_GROUPS', '0') == '1'
 
 
@@ -1585,7 +1580,6 @@ def conv3_img16_bn_supported(B, Cin, Cout, dtype, act='leaky_relu', out_dtype=No
     """Whether conv3_img16_bn_fwd / _bwd serve a Conv2d k3 s1 p1 (Cin -> Cout) -> BatchNorm -> `act` layer on B maps of 16 x 16 with output type
     `out_dtype` (forward).  VS_IMG_BN_SPLITS (default '1'): the input-channel split counts served -- with several
     splits the partial sums cross the chip inside the launch, which costs what the kernel boundary it replaces costs (measured)."""
-    import os
     if dtype == torch.float32:
         return False
     lib = _lib.load_library()

@@ -325,7 +325,7 @@ SPLIT_FULL = [
 def test_full_size_fp32_step_through_the_16bit_kernels(name, families, monkeypatch):
     """VARSEP_FP32_SPLIT=1: every Conv2d k3 s1 p1 of the fp32 step -- forward, input gradient, weight gradient -- and the gather-type
     operations of the k4 s2 p1 family run as six launches of the 16-bit ROW-BAND kernels bench.py times (x and w in three bf16 pieces each,
-    the six leading products, fp32 accumulation and output: ops._conv3_split / _k4s2_split_*) instead of the column-matrix GEMM route.
+    the six leading products, fp32 accumulation and output: ops._conv_split / _wgrad_split) instead of the column-matrix GEMM route.
     The step must meet the SAME bars against the fixture recorded from the reference's own train() as the fp32 step does (1e-3 on losses /
     forecasts / codes, 1e-2 on the conv family's gradients): the kernels of the benched path reproduce the reference's numbers, not only
     their own emulation's -- a factor-2 error in any of their gradients cannot hide behind a 16-bit bound here."""

@@ -991,6 +991,63 @@ def test_conv_thin_kernels_match_fp64(dtype, geom):
         assert torch.equal(dx16.cpu(), dx.cpu().to(dtype))
 
 
+# (geometry, the 16-bit kernel family that serves conv_fwd / conv_dgrad / conv_wgrad under VARSEP_FP32_SPLIT=1, as ops.profile_collect names it;
+# None: no split route serves that op there and the fp32 column-matrix route keeps it).  The smallest shapes that reach each family; the routes
+# are those tests/golden/conv_ops_routes.json records for these shapes.
+SPLIT_GEOMS = [
+    ((2, 64, 32, 32, 96, 3, 1, 1, False), ('vs_conv3_band:fwd', 'vs_conv3_band:dgrad', 'vs_conv3_wgrad_band')),
+    ((8, 64, 16, 16, 33, 3, 1, 1, False), ('vs_conv3_img16:fwd', 'vs_conv3_band:dgrad', 'vs_conv3_wgrad_band')),      # few maps: split slabs + slab sum
+    ((16, 64, 32, 32, 64, 4, 2, 1, False), ('vs_conv_k4s2:fwd', 'vs_convT_tap:dgrad', 'vs_conv_k4s2:wgrad')),
+    ((16, 64, 16, 16, 64, 4, 2, 1, True), ('vs_convT_tap:fwd', 'vs_conv_k4s2:dgrad', 'vs_conv_k4s2:wgrad')),
+    ((3, 5, 64, 64, 64, 4, 2, 1, False), ('vs_conv_thin:fwd', None, 'vs_conv_thin:wgrad')),
+    ((3, 64, 32, 32, 1, 4, 2, 1, True), ('vs_conv_thin:fwd', 'vs_conv_thin:dgrad', 'vs_conv_thin:wgrad')),
+    ((2, 64, 64, 64, 1, 3, 1, 1, False), ('vs_conv_thin:fwd', 'vs_conv_thin:dgrad', 'vs_conv_thin:wgrad')),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('geom,families', SPLIT_GEOMS)
+def test_fp32_split_conv_ops_match_fp64(geom, families, monkeypatch):
+    """VARSEP_FP32_SPLIT=1 op by op: fp32 conv_fwd (with bias), conv_dgrad, conv_wgrad fresh and accumulated into a pending gradient through six
+    launches of a 16-bit kernel family, each against fp64 within the fp32 bound of this file (relative L2 < 1e-5), and that the six launches
+    ran and no column matrix was built."""
+    from spatiotemporal_variable_separation_amd import ops
+    monkeypatch.setenv('VARSEP_FP32_SPLIT', '1')
+    B, Cin, H, W, Cout, k, s, p, tr = geom
+    x = _rand((B, Cin, H, W), 1)
+    wshape = (Cin, Cout, k, k) if tr else (Cout, Cin, k, k)
+    w = _rand(wshape, 2, 0.3)
+    bias = _rand((Cout,), 3)
+    x64, w64 = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    y64 = (F.conv_transpose2d if tr else F.conv2d)(x64, w64, bias.double(), stride=s, padding=p)
+    dy = _rand(tuple(y64.shape), 4)
+    y64.backward(dy.double())
+    g0 = _rand(wshape, 5)
+
+    def rel(a, b):
+        return ((a.cpu().double() - b).norm() / (b.norm() + 1e-30)).item()
+
+    def launches(call):
+        ops.profile_reset(True)
+        r = call()
+        return r, ops.profile_collect()
+    xc, wc, dyc = x.cuda(), w.cuda(), dy.cuda()
+    acc = g0.clone().cuda()
+    runs = (('fwd', families[0], lambda: ops.conv_fwd(xc, wc, bias.cuda(), s, p, tr, torch.float32), lambda r: rel(r, y64.detach())),
+            ('dgrad', families[1], lambda: ops.conv_dgrad(dyc, wc, x.shape, s, p, tr, torch.float32), lambda r: rel(r, x64.grad)),
+            ('wgrad', families[2], lambda: ops.conv_wgrad(dyc, xc, wshape, s, p, tr), lambda r: rel(r, w64.grad)),
+            ('wgrad into', families[2], lambda: ops.conv_wgrad(dyc, xc, wshape, s, p, tr, into=acc), lambda r: rel(r.cpu().double() - g0.double(), w64.grad)))
+    for what, family, call, error in runs:
+        r, prof = launches(call)
+        err = error(r)
+        print('%s %s: relative L2 %.2e, launches %s' % (geom, what, err, {n: v['n'] for n, v in prof.items()}))
+        assert err < 1e-5, f'{what} {geom}: {err:.3e}'
+        if family is not None:
+            assert prof.get(family + '<bf16>', {}).get('n') == 6, (what, geom, sorted(prof))
+            assert not [n for n in prof if n.startswith('vs_conv') and '_cols:' in n], (what, geom, sorted(prof))
+    assert acc.data_ptr() == r.data_ptr()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('shape,groups', [((200, 64, 8, 8), 2), ((24, 512, 4, 4), 8), ((6, 40, 16, 16), 3)])
