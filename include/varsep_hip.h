@@ -360,6 +360,21 @@ int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int views_per_obj
 int vs_gather_timeline(const float* frames, int64_t n_frames, int64_t frame_elems, const int32_t* first, int64_t n_windows, int step,
                        const int32_t* item_idx, int64_t rows, int seq_len, void* out, int out_dtype, int32_t* bad, void* stream);
 
+/* The WaveEq data set simulated on the device (reference: preprocessing/wave/gen_wave.py:37-92 and :121-135; csrc/vs_wave_sim.hip
+ * states the equations, the border rule and torchdiffeq's 3/8-rule tableau).  One workgroup integrates one sequence of frame_size x
+ * frame_size fields (frame_size must be 64: the reference's source disc is fixed to that grid) over T frames: T - 1 Runge-Kutta steps.
+ *   c2     [n_seq]                 fp32   c^2 of every sequence, rounded to fp32 once
+ *   source [n_seq, 3 (T - 1) + 1]  fp32   s(t) at the stage times t_i, t_i + h_i / 3, t_i + 2 h_i / 3 of every step and at t_{T-1},
+ *                                         tabulated by the caller in fp64 and rounded (ops.wave_source_table)
+ *   h      [T - 1]                 fp32   step sizes t[i+1] - t[i] (may be NULL when T == 1)
+ *   init   [n_seq, 2, 64, 64]      fp32   initial (w, w'); NULL = zeros, as the reference starts
+ *   out    [n_seq, T, 64, 64]      fp32   frame i = w after i steps (frame 0 = the initial w)
+ *   minmax [n_seq, 2]              fp32   minimum and maximum of w over all frames of a sequence, before normalisation (may be NULL)
+ * normalise != 0 rewrites every sequence of `out` as (x - min) / (max - min) in fp32 with an IEEE division (what data/wave_eq.py does
+ * to a file on the host).  init and out must be 16-byte aligned.                                                                    */
+int vs_wave_simulate(int n_seq, int T, int frame_size, const float* c2, const float* source, const float* h, const float* init, float* out,
+                     float* minmax, int normalise, void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

@@ -35,7 +35,6 @@ class WaveEq(DeviceSet):
         files = [os.path.join(base_path, f) for f in os.listdir(base_path)]
         max_seq = int(0.8 * len(files))
         files = [f for f in files if (extract_id(f) < max_seq) == bool(train)]
-        self.size = len(files)
         sims = []
         for file in files:
             data = torch.load(file).get('simul')
@@ -46,14 +45,41 @@ class WaveEq(DeviceSet):
             raise ValueError('no simulation files selected in %s' % base_path)
         if any(s.shape != sims[0].shape for s in sims):
             raise ValueError('the simulations must share one [nt, H, W] shape to live in one HBM tensor')
-        self.nt = len(sims[-1])
-        self.full_seq_len = sims[-1][0].size(0)                      # wave_eq.py:62: the frame height, not nt
-        self.frame_shape = tuple(sims[0].shape[1:])
-        self.all_data = torch.stack(sims).reshape(self.size, self.nt, -1).to(device).contiguous()
+        self._install(torch.stack(sims), device)
+
+    def _install(self, sims, device):
+        """sims: the normalised, downsampled simulations of this half of the set, fp32 [size, nt, H, W] on the host or on `device`."""
+        self.size, self.nt = sims.shape[0], sims.shape[1]
+        self.full_seq_len = sims.shape[2]                            # wave_eq.py:62: the frame height, not nt
+        self.frame_shape = tuple(sims.shape[2:])
+        self.all_data = sims.reshape(self.size, self.nt, -1).to(device).contiguous()
         self.windows_per_seq = self.nt + 1 - self.seq_len            # wave_eq.py:69-70
         if self.windows_per_seq < 1:
-            raise ValueError('seq_len %d exceeds the %d frames of a simulation' % (seq_len, self.nt))
+            raise ValueError('seq_len %d exceeds the %d frames of a simulation' % (self.seq_len, self.nt))
         self._pixels = None
+
+    @classmethod
+    def simulated(cls, nt_cond, seq_len, train, downsample, size=300, sim_len=300, seed=42, dt=0.001, device=None, **extra):
+        """The set `gen_wave --size --seq_len sim_len --seed --dt` would write and `cls(data_dir, ...)` would read back, without the files:
+        one vs_wave_simulate launch draws the reference's parameters (preprocessing/wave/gen_wave.py: wave_parameters), simulates every
+        sequence and normalises it with its own minimum and maximum, (x - min) / (max - min) in fp32 as the file route does on the host;
+        sequences below int(0.8 * size) are the training half, the others the test half.  Only the parameter table crosses PCIe."""
+        from ..preprocessing.wave.gen_wave import simulate
+        self = cls.__new__(cls)
+        self.nt_cond, self.seq_len, self.train, self.downsample = nt_cond, seq_len, train, downsample
+        device = require_gpu(cls.__name__, device)
+        sims, _, self.velocities = simulate(size, sim_len, seed, dt, device, normalise=True)
+        max_seq = int(0.8 * size)
+        sims = sims[:max_seq] if train else sims[max_seq:]
+        if sims.shape[0] == 0:
+            raise ValueError('no simulation falls into the %s half of a set of %d' % ('training' if train else 'test', size))
+        self.velocities = self.velocities[:max_seq] if train else self.velocities[max_seq:]
+        self._install(sims[:, ::downsample], device)
+        self._simulated_extra(**extra)
+        return self
+
+    def _simulated_extra(self):
+        pass
 
     def __len__(self):
         return self.size * (self.full_seq_len - self.seq_len + 1)
@@ -79,7 +105,10 @@ class WaveEqPartial(WaveEq):
     def __init__(self, data_dir, nt_cond, seq_len, train, downsample, n_pixels, device=None):
         super().__init__(data_dir, nt_cond, seq_len, train, downsample, device=device)
         pixels = np.load(os.path.join(data_dir, 'pixels', 'pixels.npz'), allow_pickle=True)
-        self.rand_w, self.rand_h = pixels['rand_w'], pixels['rand_h']
+        self._install_pixels(pixels['rand_w'], pixels['rand_h'], n_pixels)
+
+    def _install_pixels(self, rand_w, rand_h, n_pixels):
+        self.rand_w, self.rand_h = rand_w, rand_h
         self.n_wave_points = n_pixels
         H, W = self.frame_shape
         rows = np.asarray(self.rand_w[:n_pixels]).astype(np.int64)
@@ -90,3 +119,13 @@ class WaveEqPartial(WaveEq):
             raise IndexError('pixel table addresses positions outside the %dx%d frames' % (H, W))
         self._pixels = torch.from_numpy((rows * W + cols).astype(np.int32)).to(self.all_data.device)
 
+    @classmethod
+    def simulated(cls, nt_cond, seq_len, train, downsample, n_pixels, size=300, sim_len=300, seed=42, dt=0.001, pixel_seed=42, n_drawn=100,
+                  device=None):
+        """`WaveEq.simulated` reduced to `n_pixels` positions of the table `gen_pixels --number n_drawn --seed pixel_seed` would write."""
+        return super().simulated(nt_cond, seq_len, train, downsample, size=size, sim_len=sim_len, seed=seed, dt=dt, device=device,
+                                 n_pixels=n_pixels, pixel_seed=pixel_seed, n_drawn=n_drawn)
+
+    def _simulated_extra(self, n_pixels, pixel_seed, n_drawn):
+        from ..preprocessing.wave.gen_pixels import draw_pixels
+        self._install_pixels(*draw_pixels(n_drawn, self.frame_shape[0], pixel_seed), n_pixels)

@@ -1,5 +1,6 @@
 """Training entry point: `python -m spatiotemporal_variable_separation_amd.main --xp_dir ... --data_dir ...`
-(reference: main.py:49-162, same flags; `--data_dir synthetic` selects seeded synthetic batches)."""
+(reference: main.py:49-162, same flags; `--data_dir synthetic` selects seeded synthetic batches, `--data_dir simulated` with
+`--data wave` / `wave_partial` the WaveEq set simulated on the device)."""
 import json
 import os
 
@@ -21,7 +22,8 @@ from .train import train
 
 def load_dataset(args, device=None):
     """`--data_dir synthetic` needs nothing.  The WaveEq sets (main.py:91-102 of the reference) are this package's own HBM-resident
-    datasets (data/wave_eq.py: batches gathered on the device); Moving MNIST is generated on the device (data/moving_mnist.py); the
+    datasets (data/wave_eq.py: batches gathered on the device; `--data_dir simulated` builds the paper's set there without files, as
+    preprocessing/wave/gen_wave.py and gen_pixels.py with their defaults would write it); Moving MNIST is generated on the device (data/moving_mnist.py); the
     3D Chairs views are decoded once and gathered on the device (data/chairs.py); the TaxiBJ frames live in HBM and a batch is gathered
     through the window table (data/taxibj.py); the normalised SST days of all zones likewise (data/sst.py).  Nothing here imports the reference package."""
     if args.data_dir == 'synthetic':
@@ -30,6 +32,10 @@ def load_dataset(args, device=None):
     on_gpu = device is not None and torch.device(device).type == 'cuda'
     if args.data in ('wave', 'wave_partial') and on_gpu:
         from .data.wave_eq import WaveEq, WaveEqPartial
+        if args.data_dir == 'simulated':                            # no files: the reference's generator runs on the device (csrc/vs_wave_sim.hip)
+            if args.data == 'wave':
+                return WaveEq.simulated(args.nt_cond, args.nt_cond + args.nt_pred, True, args.downsample, device=device)
+            return WaveEqPartial.simulated(args.nt_cond, args.nt_cond + args.nt_pred, True, args.downsample, args.n_wave_points, device=device)
         if args.data == 'wave':
             return WaveEq(args.data_dir, args.nt_cond, args.nt_cond + args.nt_pred, True, args.downsample, device=device)
         return WaveEqPartial(args.data_dir, args.nt_cond, args.nt_cond + args.nt_pred, True, args.downsample, args.n_wave_points,

@@ -1903,6 +1903,55 @@ def gather_windows(data, item_idx, windows_per_seq, seq_len, pixel_idx=None, out
     return out
 
 
+def wave_source_table(f0, T, dt):
+    """(source fp32 [n_seq, 3 (T - 1) + 1], h fp32 [T - 1]) on the host: the reference's source f0 * exp(-20 t) (gen_wave.py:27-28, 124) at the
+    stage times of torchdiffeq's fixed-grid rk4, rounded as the reference rounds it.  The grid is arange(0, dt * T, dt) in fp32 (computed
+    in double, rounded per element); the stage times t0, t0 + h / 3, t0 + 2 h / 3 are formed in fp32, widened by `.item()`, and the source
+    is evaluated in fp64 and rounded when it meets the fp32 mask; the last entry is the fourth stage of the last step, t[T - 1].  The
+    grid comes from the reference's own call (gen_wave.py:134), on the host: torch rounds its points in a way no closed form restates.
+    Where dt * T / dt rounds up past T the call yields T + 1 points; the first T are used."""
+    import numpy as np
+    t = torch.arange(0, float(dt) * T, float(dt), dtype=torch.float32, device='cpu')[:T].numpy()
+    assert t.size == T
+    h = t[1:] - t[:-1]
+    stages = np.stack([t[:-1], t[:-1] + h * np.float32(1.0 / 3.0), t[:-1] + h * np.float32(2.0 / 3.0)], axis=1).reshape(-1)
+    times = np.concatenate([stages, t[-1:]]).astype(np.float64)
+    f0 = np.asarray(f0, dtype=np.float64).reshape(-1, 1)
+    return (f0 * np.exp(-20.0 * times)[None, :]).astype(np.float32), h
+
+
+def wave_simulate(f0, c, T, dt=0.001, init=None, normalise=False, device=None):
+    """The reference's WaveEq simulations (preprocessing/wave/gen_wave.py) for the source amplitudes `f0` and velocities `c` (sequences of
+    floats), `T` frames `dt` apart, in ONE launch of vs_wave_simulate -> (simul fp32 [n_seq, T, 64, 64], minmax fp32 [n_seq, 2]) on the
+    device.  init: optional fp32 [n_seq, 2, 64, 64] device tensor, the initial (w, w'); None = zeros like the reference.  normalise=True
+    returns every sequence as (x - min) / (max - min); minmax always holds the raw extremes.  Only the parameter tables cross PCIe."""
+    import numpy as np
+    f0 = np.asarray(f0, dtype=np.float64).reshape(-1)
+    c = np.asarray(c, dtype=np.float64).reshape(-1)
+    n_seq, T = f0.size, int(T)
+    if n_seq < 1 or c.size != n_seq or T < 1:
+        raise _lib.VarsepHipError('wave_simulate needs one (f0, c) pair per sequence and T >= 1 (got %d, %d, T = %d)' % (f0.size, c.size, T))
+    device = torch.device(device if device is not None else (init.device if init is not None else 'cuda'))
+    if device.type != 'cuda':
+        raise _lib.VarsepHipError('wave_simulate runs on an MI355X device; there is no CPU fallback (tests use tests/wave_sim_ref.py)')
+    if init is not None:
+        require_cuda(init)
+        assert init.dtype == torch.float32 and init.is_contiguous() and tuple(init.shape) == (n_seq, 2, 64, 64) and init.device == device
+    source, h = wave_source_table(f0, T, dt)
+    c2 = (c * c).astype(np.float32)                                 # gen_wave.py:85: the Python float c**2 meets an fp32 tensor
+    table = torch.from_numpy(np.concatenate([c2, h, source.reshape(-1)])).to(device)
+    c2_d, h_d, source_d = table[:n_seq], table[n_seq:n_seq + T - 1], table[n_seq + T - 1:]
+    with torch.cuda.device(device):
+        simul = torch.empty((n_seq, T, 64, 64), dtype=torch.float32, device=device)
+        minmax = torch.empty((n_seq, 2), dtype=torch.float32, device=device)
+        e0 = _pb()
+        check(_lib.load_library().vs_wave_simulate(n_seq, T, 64, c2_d.data_ptr(), source_d.data_ptr(), h_d.data_ptr() if T > 1 else None,
+                                                   _ptr(init), simul.data_ptr(), minmax.data_ptr(), int(bool(normalise)), stream_ptr()),
+              'vs_wave_simulate')
+        _pe(e0, 'vs_wave_simulate', flops=float(n_seq) * (T - 1) * 4 * 4096 * 30, nbytes=float(simul.numel() * 4 * (3 if normalise else 1)))
+    return simul, minmax
+
+
 def chairs_gather(frames_u8, desc, seq_len, out_dtype=torch.float32, validate=True):
     """frames_u8 uint8 [n_objects, views, H, W, C] on the device, desc int32 [rows, 2] = (object, first view) -> [rows, seq_len, C, H, W]
     in `out_dtype`: frame t of a row is view (first + t) % views, values byte / 255 (vs_chairs_gather, one launch).

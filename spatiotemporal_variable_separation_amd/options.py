@@ -90,7 +90,8 @@ def _build():
     g = p.add_argument_group(title='Dataset', description='Chosen dataset and dataset parameters.')
     g.add_argument('--data', type=str, metavar='DATASET', default='mnist', choices=DATASETS, help='Dataset choice.')
     g.add_argument('--data_dir', type=str, metavar='DIR', required=True,
-                   help='Data directory; the literal `synthetic` selects seeded synthetic batches of the dataset shape.')
+                   help='Data directory; the literal `synthetic` selects seeded synthetic batches of the dataset shape, the literal '
+                        '`simulated` (WaveEq sets only) the WaveEq simulations computed on the device.')
     A('--downsample', type=int, metavar='DOWNSAMPLE', default=2, help='Set the sampling rate for the WaveEq dataset.')
     A('--n_wave_points', type=int, metavar='NUMBER', default=100,
       help='Number of random pixels to select for partial WaveEq (WaveEq-100).')

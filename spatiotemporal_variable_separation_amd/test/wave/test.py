@@ -3,13 +3,18 @@
     python -m spatiotemporal_variable_separation_amd.test.wave.test --xp_dir X --data_dir D --device 0
 
 Forecasts 40 frames of every test window (`wave`: full frames, `wave_partial`: the pixel subset) from the HBM-resident WaveEq sets and
-prints the mean MSE over the horizon.  There is no CPU mode: --device is required.
+prints the mean MSE over the horizon.  `--data_dir simulated` evaluates on the test half of the set simulated on the device (what main.py
+trains on under the same value).  There is no CPU mode: --device is required.
 """
 from ...data.wave_eq import WaveEq, WaveEqPartial
 from ..utils import add_precision_flag, base_parser, forecast_metrics, horizon_mse_main
 
 
 def load_dataset(args, train=False):
+    if args.data_dir == 'simulated':                                # the set main.py trains on under the same value: simulated in HBM, no files
+        if args.data == 'wave':
+            return WaveEq.simulated(args.nt_cond, args.nt_cond + args.nt_pred, train, args.downsample, device=args.device)
+        return WaveEqPartial.simulated(args.nt_cond, args.nt_cond + args.nt_pred, train, args.downsample, args.n_wave_points, device=args.device)
     if args.data == 'wave':
         return WaveEq(args.data_dir, args.nt_cond, args.nt_cond + args.nt_pred, train, args.downsample, device=args.device)
     return WaveEqPartial(args.data_dir, args.nt_cond, args.nt_cond + args.nt_pred, train, args.downsample, args.n_wave_points,
