@@ -375,6 +375,23 @@ int vs_gather_timeline(const float* frames, int64_t n_frames, int64_t frame_elem
 int vs_wave_simulate(int n_seq, int T, int frame_size, const float* c2, const float* source, const float* h, const float* init, float* out,
                      float* minmax, int normalise, void* stream);
 
+/* Crop + two-pass 8-bit resampling with integer coefficient tables: the arithmetic of PIL's ImagingResample for 8 bits per channel,
+ * bit for bit (reference: preprocessing/chairs/gen_chairs.py, `img.crop(box).resize(size, Image.LANCZOS)`; csrc/vs_resample.hip states
+ * the arithmetic and the kernel, ops.lanczos_coeffs builds the tables).
+ *   src [n, H, W, C] uint8, HWC;  out [n, out_h, out_w, C] uint8;  C in 1..4
+ *   box: columns box_x0 .. box_x0 + box_w and rows box_y0 .. box_y0 + box_h of every image, inside the image
+ *   kx [out_w, ksize_x] int32 coefficients with 22 fractional bits, bx [out_w, 2] int32 = (first tap, taps) relative to the box;
+ *   ky [out_h, ksize_y], by [out_h, 2] likewise for the rows.  All four are device arrays.
+ * Horizontal pass over the rows of the box, rounded and clipped to uint8 (kept in LDS), then the vertical pass over that intermediate:
+ *   value = clamp(((1 << 21) + sum pixel * k) >> 22, 0, 255), 32-bit accumulation, arithmetic shift.
+ * The kernel clamps every bound into the box and into ksize: no table contents make it read outside src.  One launch; one workgroup per
+ * image and band of 16 output columns.  Returns VS_ERR_ARG (and launches nothing) for a null pointer, a non-positive size, a box outside
+ * the image, ksize < 1, more workgroups than a grid holds, or a shape whose tables + staging rows + [box_h, 16, C] intermediate exceed
+ * the 160 KiB of LDS (the message names the sizes).  No alignment is required of src or out.                                          */
+int vs_resample_u8(const uint8_t* src, int64_t n, int H, int W, int C, int box_x0, int box_y0, int box_w, int box_h, const int32_t* kx,
+                   const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, int out_w, int out_h, uint8_t* out,
+                   void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

@@ -6,9 +6,15 @@ small fraction of HBM, so here every view of the split is decoded ONCE, kept on 
 as `np.array(Image.open(f))` yields it), and a batch is one gather launch (`vs_chairs_gather`: wrap-around views, / 255, HWC -> CHW)
 driven by a [B, 2] table of (object, first view).  Directory handling, the seeded shuffle, the 85 % split and the decomposition of an
 item index follow the reference line by line, so that a seeded sampler visits the same sequences in the same order.
+
+The 64 x 64 views are the output of the reference's preprocessing/chairs/gen_chairs.py over the original 600 x 600 renders (crop, Lanczos
+resize).  That step runs on the device here (ops.resample_lanczos_u8, PIL's arithmetic bit for bit): preprocessing/chairs/gen_chairs.py
+writes the files, `Chairs.from_raw` fills `frames` from the raw renders without writing any.  PNG decoding stays on the host.
 """
 import os
+import re
 import struct
+import time
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 
@@ -100,7 +106,8 @@ def _pil_image():
 
 def read_frame(path, size=64, image_module=None):
     """uint8 [size, size, 3] of one rendered view: `np.array(Image.open(path))` (chairs.py:58) when PIL imports, the built-in reader
-    otherwise.  A file that is missing or is not a size x size 8-bit RGB image raises ValueError naming it."""
+    otherwise.  A file that is missing or is not a size x size 8-bit RGB image raises ValueError naming it.  size=None accepts an 8-bit
+    RGB image of any size (the raw renders, which the caller checks against its crop box)."""
     if not os.path.isfile(path):
         raise ValueError('%s: missing' % path)
     if image_module is not None:
@@ -111,15 +118,116 @@ def read_frame(path, size=64, image_module=None):
             raise ValueError('%s: %s' % (path, e))
     else:
         arr = read_png_rgb8(path)
-    if arr.dtype != np.uint8 or arr.shape != (size, size, 3):
+    if size is None:
+        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError('%s: an 8-bit RGB image is expected (got %s %s)' % (path, arr.dtype, arr.shape))
+    elif arr.dtype != np.uint8 or arr.shape != (size, size, 3):
         raise ValueError('%s: a %d x %d 8-bit RGB image is expected (got %s %s)' % (path, size, size, arr.dtype, arr.shape))
     return arr
+
+
+def _png_chunk(kind, body):
+    return struct.pack('>I', len(body)) + kind + body + struct.pack('>I', zlib.crc32(kind + body) & 0xffffffff)
+
+
+def write_png_rgb8(path, img):
+    """Writes uint8 [H, W, 3] as a non-interlaced 8-bit RGB PNG with zlib and NumPy only: every row with filter type 2 (Up), one
+    vectorised subtraction.  Used when PIL is not importable; `read_png_rgb8` and PIL read back the same pixels."""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError('%s: uint8 [H, W, 3] expected (got %s %s)' % (path, img.dtype, img.shape))
+    h, w, _ = img.shape
+    rows = img.reshape(h, w * 3)
+    raw = np.empty((h, w * 3 + 1), dtype=np.uint8)
+    raw[:, 0] = 2
+    raw[0, 1:] = rows[0]
+    raw[1:, 1:] = rows[1:] - rows[:-1]                   # modulo 256
+    with open(path, 'wb') as f:
+        f.write(_PNG_MAGIC + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
+                + _png_chunk(b'IDAT', zlib.compress(raw.tobytes(), 6)) + _png_chunk(b'IEND', b''))
+
+
+# ---- the raw renders (600 x 600 in the original set) and their preparation on the device ------------------------------------------
+RAW_BOX = (100, 100, 500, 500)                           # gen_chairs.py:31 of the reference
+OBJECTS_PER_BATCH = 8                                    # 8 x 62 raw renders of 600 x 600 = 536 MB on the host and in HBM, 1984 workgroups per launch
+_PREPARED = re.compile(r'^\d+\.png$')
+
+
+def list_objects(data_root):
+    """(rendered_chairs directory, its sorted entries without `all_chair_names.mat`): the listing of chairs.py:34-35."""
+    root = os.path.join(data_root, 'rendered_chairs')
+    objects = sorted(os.listdir(root))
+    objects.remove('all_chair_names.mat')
+    return root, objects
+
+
+def raw_render_names(renders_dir):
+    """`sorted(os.listdir(renders_dir))` (gen_chairs.py:29) without the names `<digits>.png`: those are the files the preparation itself
+    writes, which the reference would feed back in on a second run."""
+    return [f for f in sorted(os.listdir(renders_dir)) if not _PREPARED.match(f)]
+
+
+def decode_renders(paths, box, image_module=None):
+    """uint8 [n, H, W, 3] of raw renders, decoded on at most MAX_DECODE_WORKERS threads.  ValueError naming the file for one that is no
+    8-bit RGB image, does not contain `box` = (left, upper, right, lower), or differs in size from the first of the batch."""
+    left, upper, right, lower = box
+    if not (0 <= left < right and 0 <= upper < lower):
+        raise ValueError('the crop box %s is empty' % (tuple(box),))
+    first = read_frame(paths[0], None, image_module)
+    out = np.empty((len(paths),) + first.shape, dtype=np.uint8)
+
+    def decode(i):
+        arr = first if i == 0 else read_frame(paths[i], None, image_module)
+        if right > arr.shape[1] or lower > arr.shape[0]:
+            raise ValueError('%s: the crop box %s is not inside the %d x %d image' % (paths[i], tuple(box), arr.shape[1], arr.shape[0]))
+        if arr.shape != first.shape:
+            raise ValueError('%s: a %d x %d image among %d x %d ones (a batch is one tensor)'
+                             % (paths[i], arr.shape[1], arr.shape[0], first.shape[1], first.shape[0]))
+        out[i] = arr
+
+    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_WORKERS, len(paths))) as pool:
+        for _ in pool.map(decode, range(len(paths)), chunksize=1):
+            pass
+    return out
+
+
+def prepare_renders(paths, box, image_size, device, image_module=None, timings=None):
+    """uint8 [n, image_size, image_size, 3] on `device`: the raw renders cropped to `box` and resized with PIL's Lanczos filter -- decode
+    on the host, ONE upload, ONE launch (ops.resample_lanczos_u8).  timings: optional dict; seconds are added to 'decode', 'upload' and
+    'kernel' (which synchronises the device after each stage)."""
+    t0 = time.perf_counter()
+    raw = decode_renders(paths, box, image_module)
+    t1 = time.perf_counter()
+    raw_d = torch.from_numpy(raw).to(device)
+    if timings is not None:
+        torch.cuda.synchronize(device)
+    t2 = time.perf_counter()
+    out = ops.resample_lanczos_u8(raw_d, box, image_size)
+    if timings is not None:
+        torch.cuda.synchronize(device)
+        for key, dt in (('decode', t1 - t0), ('upload', t2 - t1), ('kernel', time.perf_counter() - t2)):
+            timings[key] = timings.get(key, 0.0) + dt
+    return out
 
 
 class Chairs(DeviceSet):
     """`Chairs(train, data_root, nt_cond, seq_len, image_size)` (chairs.py:23-67) with the split's views on `device`."""
 
     max_length = 62
+
+    @classmethod
+    def from_raw(cls, train, data_root, nt_cond, seq_len=15, image_size=64, box=RAW_BOX, device=None):
+        """The same set built straight from the RAW renders (`renders/<any name>.png`, 600 x 600 in the original set; exactly 62 per
+        object), with no files written: every view is decoded, cropped to `box` and resized on the device (ops.resample_lanczos_u8) as
+        preprocessing/chairs/gen_chairs.py would prepare it.  Same listing, shuffle and split: `frames` holds the bytes of
+        `Chairs(...)` on a tree that `gen_chairs.generate` prepared.  The constructor itself runs, with its own signature (a subclass
+        such as the content-swap set of test/chairs/test_disentanglement.py needs no change); it finds the box on the instance."""
+        self = cls.__new__(cls)
+        self.raw_box = tuple(int(v) for v in box)
+        self.__init__(train, data_root, nt_cond, seq_len=seq_len, image_size=image_size, device=device)
+        return self
+
+    raw_box = None                                       # set per instance by `from_raw`, before the constructor runs
 
     def __init__(self, train, data_root, nt_cond, seq_len=15, image_size=64, device=None):
         self.train, self.nt_cond = train, nt_cond
@@ -131,9 +239,7 @@ class Chairs(DeviceSet):
             raise ValueError('the rendered chairs are 64 x 64 images')
         self.seq_len, self.image_size = seq_len, image_size
         self.device = device = require_gpu('Chairs', device)
-        self.data_root = os.path.join(data_root, 'rendered_chairs')
-        self.sequences = sorted(os.listdir(self.data_root))
-        self.sequences.remove('all_chair_names.mat')
+        self.data_root, self.sequences = list_objects(data_root)
         rng = np.random.RandomState(42)
         rng.shuffle(self.sequences)
         if self.train:
@@ -142,11 +248,29 @@ class Chairs(DeviceSet):
             self.start_idx, self.stop_idx = int(len(self.sequences) * 0.85), len(self.sequences)
         if self.stop_idx <= self.start_idx:
             raise ValueError('no objects in the %s split of %s' % ('train' if train else 'test', self.data_root))
-        self.frames = torch.from_numpy(self._decode_split()).to(device)
+        self.frames = torch.from_numpy(self._decode_split()).to(device) if self.raw_box is None else self._prepare_split(self.raw_box)
 
     @property
     def n_objects(self):
         return self.stop_idx - self.start_idx
+
+    def _prepare_split(self, box):
+        """uint8 [n, 62, 64, 64, 3] on the device from the raw renders of the split's own objects, OBJECTS_PER_BATCH objects per launch."""
+        image_module = _pil_image()
+        size = self.image_size
+        objects = self.sequences[self.start_idx:self.stop_idx]
+        frames = torch.empty((len(objects), self.max_length, size, size, 3), dtype=torch.uint8, device=self.device)
+        for start in range(0, len(objects), OBJECTS_PER_BATCH):
+            paths = []
+            for obj in objects[start:start + OBJECTS_PER_BATCH]:
+                renders = os.path.join(self.data_root, obj, 'renders')
+                names = raw_render_names(renders)
+                if len(names) != self.max_length:
+                    raise ValueError('%s: %d raw renders, exactly %d are expected' % (os.path.join(self.data_root, obj), len(names), self.max_length))
+                paths += [os.path.join(renders, f) for f in names]
+            out = prepare_renders(paths, box, size, self.device, image_module)
+            frames[start:start + len(paths) // self.max_length] = out.view(-1, self.max_length, size, size, 3)
+        return frames
 
     def _decode_split(self):
         """uint8 [n, 62, 64, 64, 3]: `renders/0.png .. 61.png` of the split's own objects, in the split's order."""

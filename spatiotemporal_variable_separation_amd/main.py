@@ -1,6 +1,7 @@
 """Training entry point: `python -m spatiotemporal_variable_separation_amd.main --xp_dir ... --data_dir ...`
 (reference: main.py:49-162, same flags; `--data_dir synthetic` selects seeded synthetic batches, `--data_dir simulated` with
-`--data wave` / `wave_partial` the WaveEq set simulated on the device)."""
+`--data wave` / `wave_partial` the WaveEq set simulated on the device, `--chairs_raw` with `--data chairs` the original 3D Chairs renders
+cropped and resized on the device)."""
 import json
 import os
 
@@ -46,6 +47,8 @@ def load_dataset(args, device=None):
                                         device=device, seed=args.seed)
     if args.data == 'chairs' and on_gpu:
         from .data.chairs import Chairs                             # main.py:77-79 of the reference; views resident in HBM
+        if getattr(args, 'chairs_raw', False):                      # the original renders, prepared on the device (csrc/vs_resample.hip)
+            return Chairs.from_raw(True, args.data_dir, args.nt_cond, seq_len=args.nt_cond + args.nt_pred, box=args.chairs_box, device=device)
         return Chairs(True, args.data_dir, args.nt_cond, seq_len=args.nt_cond + args.nt_pred, device=device)
     if args.data == 'taxibj' and on_gpu:
         from .data.taxibj import TaxiBJ                             # main.py:82-86 of the reference; frames resident in HBM

@@ -1952,6 +1952,91 @@ def wave_simulate(f0, c, T, dt=0.001, init=None, normalise=False, device=None):
     return simul, minmax
 
 
+def lanczos_coeffs(in_size, out_size):
+    """(k int32 [out_size, ksize], bounds int32 [out_size, 2] = (first tap, taps)) of PIL's 8-bit Lanczos resampling of an axis of `in_size`
+    pixels to `out_size` (ImagingResample: `precompute_coeffs` + `normalize_coeffs_8bpc`, 22 fractional bits), on the host.  Python floats
+    (C doubles) and math.sin throughout: NumPy's vectorised sine may differ by an ulp, which can flip a rounded coefficient.  Entries of
+    a row beyond its taps are 0.  Checked once per table: every |k| < 2^23 (the kernel's 24-bit multiply is exact) and
+    255 * max row sum|k| + 2^21 < 2^31 (its 32-bit accumulator cannot overflow)."""
+    import math
+    import numpy as np
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise _lib.VarsepHipError('lanczos_coeffs: sizes must be positive (got %d -> %d)' % (in_size, out_size))
+
+    def sinc(x):
+        if x == 0.0:
+            return 1.0
+        x = x * math.pi
+        return math.sin(x) / x
+
+    def lanczos(x):
+        return sinc(x) * sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0
+
+    in0, in1 = 0.0, float(in_size)
+    scale = (in1 - in0) / out_size
+    fs = max(scale, 1.0)
+    support = 3.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    k = np.zeros((out_size, ksize), dtype=np.int64)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    for xx in range(out_size):
+        center = in0 + (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [lanczos((x + xmin - center + 0.5) / fs) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        k[xx, :xmax] = [int(v * 4194304.0 + 0.5) if v >= 0 else int(v * 4194304.0 - 0.5) for v in w]
+        bounds[xx] = (xmin, xmax)
+    if int(np.abs(k).max()) >= 1 << 23 or 255 * int(np.abs(k).sum(axis=1).max()) + (1 << 21) >= 1 << 31:
+        raise _lib.VarsepHipError('lanczos_coeffs(%d, %d): a coefficient needs more than 24 bits or a row sum overflows 32 bits' % (in_size, out_size))
+    return k.astype(np.int32), bounds
+
+
+_resample_tables = {}
+
+
+def _lanczos_tables(extent, size, device):
+    """(k, bounds) of an axis on `device`, built once per (extent, size, device)."""
+    key = (int(extent), int(size), device.type, device.index)
+    if key not in _resample_tables:
+        k, b = lanczos_coeffs(extent, size)
+        _resample_tables[key] = (torch.from_numpy(k).to(device), torch.from_numpy(b).to(device), k.shape[1])
+    return _resample_tables[key]
+
+
+def resample_lanczos_u8(images_u8, box, size):
+    """uint8 [n, H, W, C] on the device -> uint8 [n, size_h, size_w, C]: `Image.fromarray(img).crop(box).resize(size, Image.LANCZOS)` of every
+    image, bit for bit, in ONE launch of vs_resample_u8 (csrc/vs_resample.hip).  box = (left, upper, right, lower) as PIL orders it;
+    size = (w, h), or an int for a square output; C in 1..4.  The coefficient tables are cached on the device per (extent, size, device)."""
+    require_cuda(images_u8)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+        raise _lib.VarsepHipError('resample_lanczos_u8: uint8 [n, H, W, C] expected (got %s %s)' % (images_u8.dtype, tuple(images_u8.shape)))
+    out_w, out_h = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    left, upper, right, lower = (int(v) for v in box)
+    n, H, W, C = images_u8.shape
+    if not (0 <= left < right <= W and 0 <= upper < lower <= H) or out_w < 1 or out_h < 1 or n < 1:
+        raise _lib.VarsepHipError('resample_lanczos_u8: box %s must lie inside the %d x %d images, and the batch and the output size %s be '
+                                  'positive' % ((left, upper, right, lower), W, H, (out_w, out_h)))
+    images_u8 = images_u8.contiguous()
+    device = images_u8.device
+    with torch.cuda.device(device):
+        kx, bx, ksx = _lanczos_tables(right - left, out_w, device)
+        ky, by, ksy = _lanczos_tables(lower - upper, out_h, device)
+        out = torch.empty((n, out_h, out_w, C), dtype=torch.uint8, device=device)
+        e0 = _pb()
+        check(_lib.load_library().vs_resample_u8(images_u8.data_ptr(), n, H, W, C, left, upper, right - left, lower - upper, kx.data_ptr(),
+                                                 bx.data_ptr(), ksx, ky.data_ptr(), by.data_ptr(), ksy, out_w, out_h, out.data_ptr(),
+                                                 stream_ptr()), 'vs_resample_u8')
+        _pe(e0, 'vs_resample_u8', flops=2.0 * n * C * (float(lower - upper) * out_w * ksx + float(out_h) * out_w * ksy),
+            nbytes=float(n) * C * ((lower - upper) * (right - left) + out_h * out_w))
+    return out
+
+
 def chairs_gather(frames_u8, desc, seq_len, out_dtype=torch.float32, validate=True):
     """frames_u8 uint8 [n_objects, views, H, W, C] on the device, desc int32 [rows, 2] = (object, first view) -> [rows, seq_len, C, H, W]
     in `out_dtype`: frame t of a row is view (first + t) % views, values byte / 255 (vs_chairs_gather, one launch).

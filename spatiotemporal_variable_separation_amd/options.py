@@ -11,6 +11,20 @@ INITIALIZATIONS = ['orthogonal', 'kaiming', 'normal']
 MIXING = ['concat', 'mul']
 
 
+def add_chairs_box_flag(group):
+    """--chairs_box, shared with test/chairs/test_disentanglement_raw.py."""
+    group.add_argument('--chairs_box', type=int, nargs=4, metavar=('LEFT', 'UPPER', 'RIGHT', 'LOWER'), default=[100, 100, 500, 500],
+                       help='Crop box of the original 3D Chairs renders (--chairs_raw); the default is the one of the reference\'s preprocessing.')
+
+
+def add_chairs_raw_flags(group):
+    """--chairs_raw and the crop box it uses."""
+    group.add_argument('--chairs_raw', action='store_true',
+                       help='3D Chairs: --data_dir holds the ORIGINAL renders; crop and resize them on the device into HBM, writing no files '
+                            '(what preprocessing/chairs/gen_chairs.py would prepare).')
+    add_chairs_box_flag(group)
+
+
 def _build():
     p = argparse.ArgumentParser(prog="PDE-Driven Spatiotemporal Disentanglement (training)",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -117,6 +131,7 @@ def _build():
                         '(a ragged last batch) run eagerly either way.')
     g.add_argument('--log_interval', type=int, default=None, help='Print losses and frames/s every N steps.')
     g.add_argument('--synthetic_len', type=int, default=2048, help='Sequences per epoch of the synthetic dataset.')
+    add_chairs_raw_flags(g)
     return p
 
 
