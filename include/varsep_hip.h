@@ -109,7 +109,9 @@ int vs_gemm(int compute, int64_t M, int64_t N, int64_t K,
  * Element-wise / reduction helpers around the GEMMs.
  */
 
-/* dst[i] = (dst_dtype) src[i], i < n.  fp32 master weights -> bf16 shadow copies, input frames -> bf16. */
+/* dst[i] = (dst_dtype) src[i], i < n.  fp32 master weights -> bf16 shadow copies, input frames -> bf16.
+ * Any element-aligned src / dst: four elements per access where both are aligned to four elements, one at a time otherwise
+ * (vs_act_fwd and vs_act_bwd likewise). */
 int vs_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
 
 /* Strided 2-D copy with conversion: dst[r*ldd + c] = src[r*lds + c], r < rows, c < cols.
@@ -529,7 +531,8 @@ int vs_loss_scale_update(float* scale_state, float growth_factor, float backoff_
  * fp32: every observed frame; idx [G] int32 ON THE DEVICE: frame g is compared with full[:, idx[g]].
  *   fwd: sums[0] = sum of squared errors of frame 0, sums[1] = of frames 1..G-1 (float atomics: last-bit nondeterminism).
  *   bwd: dframes[b, g, :] = coef[g == 0 ? 0 : 1] * (frames - target); coef [2] on the device = 2/N_k times the upstream
- *        gradient of loss k, so no host synchronisation is needed.  D must make rows 16-byte aligned for speed.          */
+ *        gradient of loss k, so no host synchronisation is needed.  D must make rows 16-byte aligned for speed: with
+ *        D % 4 != 0, or frames / full / dframes off 16-byte alignment, every element is read and written on its own.     */
 int vs_frames_sse_fwd(const float* frames, const float* full, const int32_t* idx, int64_t B, int G, int T, int64_t D, float* sums,
                       void* stream);
 int vs_frames_sse_bwd(const float* frames, const float* full, const int32_t* idx, int64_t B, int G, int T, int64_t D, const float* coef,

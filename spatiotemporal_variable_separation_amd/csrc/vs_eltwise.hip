@@ -40,10 +40,11 @@ inline unsigned grid_for(int64_t work_items) {
     return (unsigned)b;
 }
 
-// 4 consecutive elements per thread per iteration
+// 4 consecutive elements per thread per iteration (one 8- or 16-byte access each way).  `vec` 0: x or y is off that access's alignment
+// (map4_vec_ok, on the host) and every element goes through the scalar tail loop.
 template <class F>
-__device__ __forceinline__ void map4(const void* x, int xd, void* y, int yd, int64_t n, F f) {
-    const int64_t n4 = n / 4;
+__device__ __forceinline__ void map4(const void* x, int xd, void* y, int yd, int64_t n, int vec, F f) {
+    const int64_t n4 = vec ? n / 4 : 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float v[4];
@@ -58,17 +59,17 @@ __device__ __forceinline__ void map4(const void* x, int xd, void* y, int yd, int
         vs_st(y, yd, i, f(vs_ld(x, xd, i), i));
 }
 
-__global__ __launch_bounds__(256) void cast_kernel(const void* src, int sd, void* dst, int dd, int64_t n) {
-    map4(src, sd, dst, dd, n, [](float v, int64_t) { return v; });
+__global__ __launch_bounds__(256) void cast_kernel(const void* src, int sd, void* dst, int dd, int64_t n, int vec) {
+    map4(src, sd, dst, dd, n, vec, [](float v, int64_t) { return v; });
 }
 
-__global__ __launch_bounds__(256) void act_fwd_kernel(const void* x, int xd, void* y, int yd, int act, int64_t n) {
-    map4(x, xd, y, yd, n, [act](float v, int64_t) { return vs_act(v, act); });
+__global__ __launch_bounds__(256) void act_fwd_kernel(const void* x, int xd, void* y, int yd, int act, int64_t n, int vec) {
+    map4(x, xd, y, yd, n, vec, [act](float v, int64_t) { return vs_act(v, act); });
 }
 
 __global__ __launch_bounds__(256) void act_bwd_kernel(const void* dy, int dyd, const void* y, int yd, void* dz, int dzd, int act,
-                                                      int64_t n) {
-    map4(dy, dyd, dz, dzd, n, [=](float g, int64_t i) { return g * vs_act_grad_from_out(vs_ld(y, yd, i), act); });
+                                                      int64_t n, int vec) {
+    map4(dy, dyd, dz, dzd, n, vec, [=](float g, int64_t i) { return g * vs_act_grad_from_out(vs_ld(y, yd, i), act); });
 }
 
 __global__ __launch_bounds__(256) void copy2d_kernel(const void* src, int sd, int64_t lds, void* dst, int dd, int64_t ldd,
@@ -259,8 +260,10 @@ __global__ __launch_bounds__(256) void colsum_multi_rows_kernel(ColsumJobs J) {
 // fp32 (all observed frames), idx[g] = index of the frame of `full` that frame g is compared with (device array, so the
 // random auto-encoding target can change without re-recording a graph).  sums[0] = SSE of frame 0 (ae_loss, train.py:85-86),
 // sums[1] = SSE of frames 1.. (forecast loss, train.py:139).
+// `vec` 0 (D % 4 != 0, or frames / full off 16-byte alignment: rows_vec_ok on the host): no row starts on a 16-byte boundary for sure, and
+// every element is read on its own.
 __global__ __launch_bounds__(256) void frames_sse_kernel(const float* frames, const float* full, const int* idx, int64_t rows, int G, int T,
-                                                         int64_t D, float* sums) {
+                                                         int64_t D, float* sums, int vec) {
     __shared__ float red[2][4];
     float s0 = 0.f, s1 = 0.f;                      // frame 0 / frames 1..
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {       // each workgroup walks many (sample, frame) rows:
@@ -269,13 +272,15 @@ __global__ __launch_bounds__(256) void frames_sse_kernel(const float* frames, co
         const float* f = frames + r * D;
         const float* t = full + (b * T + idx[g]) * D;
         float s = 0.f;
-        for (int64_t i = (int64_t)threadIdx.x * 4; i + 3 < D; i += 1024) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(f + i), c = *reinterpret_cast<const f32x4*>(t + i);
+        if (vec) {
+            for (int64_t i = (int64_t)threadIdx.x * 4; i + 3 < D; i += 1024) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(f + i), c = *reinterpret_cast<const f32x4*>(t + i);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = a[j] - c[j]; s += d * d; }
+                for (int j = 0; j < 4; ++j) { const float d = a[j] - c[j]; s += d * d; }
+            }
+        } else {
+            for (int64_t i = threadIdx.x; i < D; i += 256) { const float d = f[i] - t[i]; s += d * d; }
         }
-        if (threadIdx.x == 0)
-            for (int64_t i = D & ~(int64_t)3; i < D; ++i) { const float d = f[i] - t[i]; s += d * d; }
         if (g == 0) s0 += s; else s1 += s;
     }
 #pragma unroll
@@ -290,13 +295,17 @@ __global__ __launch_bounds__(256) void frames_sse_kernel(const float* frames, co
 
 // dframes[b,g,:] = coef[g == 0 ? 0 : 1] * (frames[b,g,:] - full[b,idx[g],:]);  coef on the device (2/N times the upstream gradient)
 __global__ __launch_bounds__(256) void frames_sse_bwd_kernel(const float* frames, const float* full, const int* idx, int G, int T, int64_t D,
-                                                             const float* coef, float* dframes) {
+                                                             const float* coef, float* dframes, int vec) {
     const int g = blockIdx.y % G;
     const int64_t b = blockIdx.y / G;
     const float k = coef[g == 0 ? 0 : 1];
     const float* f = frames + (b * G + g) * D;
     const float* t = full + (b * T + idx[g]) * D;
     float* o = dframes + (b * G + g) * D;
+    if (!vec) {                                                       // (rows_vec_ok on the host: some row is off 16-byte alignment)
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < D; i += (int64_t)gridDim.x * 256) o[i] = k * (f[i] - t[i]);
+        return;
+    }
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i + 3 < D; i += (int64_t)gridDim.x * 1024) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(f + i), c = *reinterpret_cast<const f32x4*>(t + i);
         f32x4 r;
@@ -304,8 +313,6 @@ __global__ __launch_bounds__(256) void frames_sse_bwd_kernel(const float* frames
         for (int j = 0; j < 4; ++j) r[j] = k * (a[j] - c[j]);
         *reinterpret_cast<f32x4*>(o + i) = r;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = D & ~(int64_t)3; i < D; ++i) o[i] = k * (f[i] - t[i]);
 }
 
 }  // namespace
@@ -663,13 +670,21 @@ extern "C" int vs_mix_codes_bwd(const float* dz, const float* s, const float* t_
     return VS_OK;
 }
 
+namespace {
+// every row of a [rows, D] fp32 matrix starts on a 16-byte boundary
+inline bool rows_vec_ok(const void* p, int64_t D) { return (uintptr_t)p % 16 == 0 && D % 4 == 0; }
+// map4's 4-element access of this operand is aligned (16 bytes fp32, 8 bytes 16-bit)
+inline bool map4_vec_ok(const void* p, int dtype) { return (uintptr_t)p % (4 * (size_t)vs_esize(dtype)) == 0; }
+}  // namespace
+
 extern "C" int vs_frames_sse_fwd(const float* frames, const float* full, const int32_t* idx, int64_t B, int G, int T, int64_t D, float* sums,
                                  void* stream) {
     VS_CHECK_ARG(frames && full && idx && sums && B > 0 && G > 0 && T > 0 && D > 0, "vs_frames_sse_fwd: bad argument");
     if (vs_zero_async(sums, 2 * sizeof(float), (hipStream_t)stream) != hipSuccess) return vs_fail(VS_ERR_LAUNCH, "vs_frames_sse_fwd: memset failed");
     int64_t wgs = B * G;
     if (wgs > 1024) wgs = 1024;
-    hipLaunchKernelGGL(frames_sse_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, frames, full, idx, B * G, G, T, D, sums);
+    hipLaunchKernelGGL(frames_sse_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, frames, full, idx, B * G, G, T, D, sums,
+                       (int)(rows_vec_ok(frames, D) && rows_vec_ok(full, D)));
     VS_CHECK_LAUNCH("vs_frames_sse_fwd");
     return VS_OK;
 }
@@ -681,7 +696,7 @@ extern "C" int vs_frames_sse_bwd(const float* frames, const float* full, const i
     if (gx > 8) gx = 8;
     if (gx < 1) gx = 1;
     hipLaunchKernelGGL(frames_sse_bwd_kernel, dim3(gx, (unsigned)(B * G)), dim3(256), 0, (hipStream_t)stream, frames, full, idx, G, T, D, coef,
-                       dframes);
+                       dframes, (int)(rows_vec_ok(frames, D) && rows_vec_ok(full, D) && rows_vec_ok(dframes, D)));
     VS_CHECK_LAUNCH("vs_frames_sse_bwd");
     return VS_OK;
 }
@@ -1007,23 +1022,28 @@ extern "C" int vs_cast(const void* src, int sd, void* dst, int dd, int64_t n, vo
     VS_CHECK_ARG(src && dst && n >= 0, "vs_cast: bad argument");
     VS_CHECK_ARG(vs_dtype_ok(sd) && vs_dtype_ok(dd), "vs_cast: bad dtype");
     if (n == 0) return VS_OK;
-    hipLaunchKernelGGL(cast_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, src, sd, dst, dd, n);
+    const bool vec = map4_vec_ok(src, sd) && map4_vec_ok(dst, dd);
+    hipLaunchKernelGGL(cast_kernel, dim3(grid_for(vec ? n / 4 + 1 : n)), dim3(256), 0, (hipStream_t)stream, src, sd, dst, dd, n, (int)vec);
     VS_CHECK_LAUNCH("vs_cast");
     return VS_OK;
 }
 
 extern "C" int vs_act_fwd(const void* x, int xd, void* y, int yd, int act, int64_t n, void* stream) {
     VS_CHECK_ARG(x && y && n >= 0, "vs_act_fwd: bad argument");
+    VS_CHECK_ARG(vs_dtype_ok(xd) && vs_dtype_ok(yd), "vs_act_fwd: bad dtype");
     if (n == 0) return VS_OK;
-    hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, x, xd, y, yd, act, n);
+    const bool vec = map4_vec_ok(x, xd) && map4_vec_ok(y, yd);
+    hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for(vec ? n / 4 + 1 : n)), dim3(256), 0, (hipStream_t)stream, x, xd, y, yd, act, n, (int)vec);
     VS_CHECK_LAUNCH("vs_act_fwd");
     return VS_OK;
 }
 
 extern "C" int vs_act_bwd(const void* dy, int dyd, const void* y, int yd, void* dz, int dzd, int act, int64_t n, void* stream) {
     VS_CHECK_ARG(dy && y && dz && n >= 0, "vs_act_bwd: bad argument");
+    VS_CHECK_ARG(vs_dtype_ok(dyd) && vs_dtype_ok(yd) && vs_dtype_ok(dzd), "vs_act_bwd: bad dtype");
     if (n == 0) return VS_OK;
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, dy, dyd, y, yd, dz, dzd, act, n);
+    const bool vec = map4_vec_ok(dy, dyd) && map4_vec_ok(dz, dzd);                    // (y is read element by element)
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(vec ? n / 4 + 1 : n)), dim3(256), 0, (hipStream_t)stream, dy, dyd, y, yd, dz, dzd, act, n, (int)vec);
     VS_CHECK_LAUNCH("vs_act_bwd");
     return VS_OK;
 }

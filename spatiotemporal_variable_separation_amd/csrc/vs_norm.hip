@@ -1559,8 +1559,9 @@ extern "C" int vs_bn_act_bwd_gsum(const void* dy, int dy_dtype, const void* x, i
     VS_CHECK_ARG(dy && x && mean && invstd && gamma && beta && dgamma && dbeta && dx && B > 0 && C > 0 && HW > 0 && groups >= 1 &&
                      B % groups == 0, "vs_bn_act_bwd: bad argument");
     const int w_ = x_dtype == VS_F32 ? 4 : 8;
-    int vec = (HW % 8 == 0);
-    if ((!vec || x_dtype != dy_dtype) && HW >= 8 && (int64_t)B * C * HW < ((int64_t)1 << 31) && ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 16 == 0)
+    const bool aligned = ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 16 == 0;
+    int vec = (HW % 8 == 0) && aligned;                                  // (off 16-byte alignment: element by element, vec 0)
+    if ((!vec || x_dtype != dy_dtype) && HW >= 8 && (int64_t)B * C * HW < ((int64_t)1 << 31) && aligned)
         vec = 2;                                                         // ragged planes and / or mixed dtypes: unit-per-plane path
     (void)w_;
     // the group sums inside the producing launch (bn_group_sums_arrive); VS_BN_GSUM_FUSED=0: the separate group_sum2_kernel launch

@@ -1422,7 +1422,9 @@ def bn_small_supported(x, groups=1):
         # default -- 8.95 ms with it, 8.93 without (the two-launch path's kernels overlap with their neighbours just as well)
         if not bn_small_groups_enabled() or B % groups != 0:
             return False
-    return x.is_contiguous() and bool(_lib.load_library().vs_bn_train_fwd_small_supported(dtype_code(x), B // groups, C, x.numel() // (B * C)))
+    # (16-byte vectors: a contiguous slice off 16-byte alignment takes the two-launch forms, as in bn_slab_supported)
+    return (x.is_contiguous() and x.data_ptr() % 16 == 0
+            and bool(_lib.load_library().vs_bn_train_fwd_small_supported(dtype_code(x), B // groups, C, x.numel() // (B * C))))
 
 
 def bn_small_supported_shape(dtype, B, C, HW):

@@ -1215,3 +1215,98 @@ def test_bn_group_sums_inside_the_backward_launch_equal_the_separate_launch(shap
         assert torch.equal(dg1, dg0) and torch.equal(db1, db0), f'{shape} call {it}: group sums differ: {(dg1 - dg0).abs().max().item()}'
         assert torch.equal(dx1, dx0)
     torch.cuda.synchronize()
+
+
+# ---- entry points the model runs that had no direct test: ops.chan_sum, ops.bn_stats_ub + ops.bn_act_fwd(running=...), ops.bn_act_bwd(training=False)
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('shape', [(3, 5, 7, 7), (2, 1, 64, 64), (64, 3, 33, 33)])
+def test_chan_sum_matches_fp64_and_is_bitwise_repeatable(dtype, shape):
+    """The bias gradient of every convolution without BatchNorm (vs_chan_sum_ws): per-chunk fp64 partial sums in a workspace, finished in a
+    fixed order -- one channel (all chunks meet on one address) included.  2e-6 relative L2: this file's bound for fp32 results of
+    fp64-accumulated reductions."""
+    from spatiotemporal_variable_separation_amd import ops
+    x = _rand(shape, 21).to(dtype).cuda()
+    ref = x.double().sum((0, 2, 3))
+    out = ops.chan_sum(x)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (shape[1],)
+    err = ((out.double() - ref).norm() / ref.norm()).item()
+    assert err < 2e-6, (shape, dtype, err)
+    assert torch.equal(ops.chan_sum(x), out)
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('groups', [1, 3])
+def test_batchnorm_running_estimates_folded_by_the_apply_launch(dtype, groups):
+    """ops.bn_stats_ub + ops.bn_act_fwd(..., running=(ub, rm, rv, momentum)): the route functional._bn_apply takes in training with tracked
+    running estimates when no one-launch form serves the tensor.  Against `groups` sequential fp64 BatchNorm2d calls: y and the running
+    estimates after 1 and after 16 calls (bounds of test_batchnorm_act_fwd_bwd), and bit-equal to bn_stats(..., rm, rv) + bn_act_fwd."""
+    from spatiotemporal_variable_separation_amd import ops
+    B, C, H, W = 6, 7, 12, 10
+    x = (_rand((B, C, H, W), 22) * 2 + 0.3).to(dtype)
+    gamma, beta = 1 + _rand((C,), 23, 0.3), _rand((C,), 24, 0.2)
+    rm, rv = _rand((C,), 25, 0.1), 1 + _rand((C,), 26, 0.2)
+    xc, gc, bc = x.cuda(), gamma.cuda(), beta.cuda()
+    assert not ops.bn_small_supported(xc, groups) and not ops.bn_slab_supported(xc, groups)       # so this IS the route _bn_apply takes
+    bn = torch.nn.BatchNorm2d(C).double()
+    with torch.no_grad():
+        bn.weight.copy_(gamma); bn.bias.copy_(beta); bn.running_mean.copy_(rm); bn.running_var.copy_(rv)
+    Bg = B // groups
+
+    def reference_call():
+        with torch.no_grad():
+            return torch.cat([F.leaky_relu(bn(x[g * Bg:(g + 1) * Bg].double()), 0.2) for g in range(groups)])
+
+    def rel(a, b):
+        return ((a.cpu().double() - b).norm() / (b.norm() + 1e-30)).item()
+    y64 = reference_call()
+    rmc, rvc = rm.clone().cuda(), rv.clone().cuda()
+    mean, invstd, ub = ops.bn_stats_ub(xc, 1e-5, groups=groups)
+    y = ops.bn_act_fwd(xc, mean, invstd, gc, bc, 'leaky_relu', torch.float32, groups=groups, running=(ub, rmc, rvc, 0.1))
+    assert tuple(mean.shape) == tuple(invstd.shape) == tuple(ub.shape) == (groups, C)
+    assert rel(y, y64) < 2e-6
+    assert rel(rmc, bn.running_mean) < 2e-6 and rel(rvc, bn.running_var) < 2e-6
+    # the two-launch statistics + the plain apply: same kernels, same arithmetic
+    rm2, rv2 = rm.clone().cuda(), rv.clone().cuda()
+    mean2, invstd2 = ops.bn_stats(xc, rm2, rv2, 0.1, 1e-5, groups=groups)
+    y2 = ops.bn_act_fwd(xc, mean2, invstd2, gc, bc, 'leaky_relu', torch.float32, groups=groups)
+    assert torch.equal(mean, mean2) and torch.equal(invstd, invstd2)
+    assert torch.equal(y, y2) and torch.equal(rmc, rm2) and torch.equal(rvc, rv2)
+    for _ in range(15):
+        reference_call()
+        ops.bn_act_fwd(xc, mean, invstd, gc, bc, 'leaky_relu', torch.float32, groups=groups, running=(ub, rmc, rvc, 0.1))
+        ops.bn_stats(xc, rm2, rv2, 0.1, 1e-5, groups=groups)
+    assert rel(rmc, bn.running_mean) < 1e-5 and rel(rvc, bn.running_var) < 1e-5
+    assert torch.equal(rmc, rm2) and torch.equal(rvc, rv2)
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('act', ['leaky_relu', 'none', 'sigmoid'])
+@pytest.mark.parametrize('shape', [(5, 7, 12, 10), (3, 5, 9, 9)])
+@pytest.mark.parametrize('groups', [1, 2])
+def test_batchnorm_act_bwd_eval_mode(groups, shape, act, dtype):
+    """ops.bn_act_bwd(..., training=False): the statistics are constants (mean = running_mean, invstd = 1 / sqrt(running_var + eps)).  Against
+    fp64 eval-mode batch_norm + activation; `groups` calls of `shape` stacked along the batch axis, each with running statistics of its own,
+    the parameter gradients summed over the calls.  Bounds of the training-mode test (test_batchnorm_act_fwd_bwd)."""
+    from spatiotemporal_variable_separation_amd import ops
+    Bg, C, H, W = shape
+    x = (_rand((groups * Bg, C, H, W), 27) * 2 + 0.3).to(dtype)
+    dy = _rand((groups * Bg, C, H, W), 28)
+    gamma, beta = 1 + _rand((C,), 29, 0.3), _rand((C,), 30, 0.2)
+    rm, rv = _rand((groups, C), 31, 0.4), 1 + _rand((groups, C), 32, 0.5)
+    eps = 1e-5
+    acts = {'leaky_relu': lambda t: F.leaky_relu(t, 0.2), 'none': lambda t: t, 'sigmoid': torch.sigmoid}
+    x64 = x.double().requires_grad_(True)
+    g64, b64 = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    y64 = torch.cat([acts[act](F.batch_norm(x64[g * Bg:(g + 1) * Bg], rm[g].double(), rv[g].double(), g64, b64, False, 0.1, eps)) for g in range(groups)])
+    y64.backward(dy.double())
+    mean, invstd = rm.cuda(), torch.rsqrt(rv.double() + eps).float().cuda()
+    xc = x.cuda()
+    y = ops.bn_act_fwd(xc, mean, invstd, gamma.cuda(), beta.cuda(), act, torch.float32, groups=groups)
+    dx, dg, db = ops.bn_act_bwd(dy.cuda(), xc, mean, invstd, gamma.cuda(), beta.cuda(), act, False, torch.float32, groups=groups)
+
+    def rel(a, b):
+        return ((a.cpu().double() - b).norm() / (b.norm() + 1e-30)).item()
+    assert rel(y, y64.detach()) < 2e-6
+    assert rel(dx, x64.grad) < 2e-5
+    assert tuple(dg.shape) == tuple(db.shape) == (C,)
+    assert rel(dg, g64.grad) < 2e-5 and rel(db, b64.grad) < 2e-5
