@@ -342,6 +342,23 @@ int vs_frame_metrics(const float* pred, const float* target, int64_t planes, int
 int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
                           int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream);
 
+/* The Moving-MNIST TEST set in one launch (reference: preprocessing/mnist/make_test_set.py:58-91, which calls `_compute_trajectory` per
+ * digit and composites on the host).  digits and init [n_videos, num_digits, 5] as for vs_moving_mnist_batch.  `frames` receives the RAW
+ * values 0..255 (sum of the digits, min(., 255); no division): uint8 when frames_fp32 == 0, fp32 otherwise.  Frame (t, v) starts at element
+ * t * frame_stride_t + v * frame_stride_v, so one entry point writes the file's time-major uint8 [T, N, 1, F, F] and the video-major fp32
+ * [N, T, 1, F, F] that the evaluation keeps in HBM.  latents [seq_len, n_videos, num_digits, 4] int32 = (rounded row, rounded column, row
+ * speed, column speed) after the collision step of frame t -- what `_compute_trajectory` appends; may be NULL.  Same double arithmetic as
+ * vs_moving_mnist_batch: bit-identical positions.  One workgroup per video, or per (video, chunk of >= 8 frames) below 512 videos.
+ * A digit index outside [0, n_digits_total) is never read: that digit is not drawn (its latents are still written).  16-byte vector stores
+ * when frame_size^2 is a multiple of 16 bytes' worth of elements and the base pointer and both strides keep frame starts 16-byte aligned;
+ * element by element otherwise.  VS_ERR_ARG (nothing launched) for a null digits / init / frames, a non-positive size, num_digits outside
+ * 1..8, a digit larger than the frame, or strides under which frames overlap (the faster index must step over whole frames and the slower
+ * one over the whole extent of the faster one); VS_ERR_UNSUPPORTED when the trajectory table of a workgroup and the digit images exceed
+ * 64 KiB of LDS (the message names the sizes).                                                                                        */
+int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int n_videos,
+                            int num_digits, int seq_len, int frame_size, void* frames, int frames_fp32, int64_t frame_stride_t,
+                            int64_t frame_stride_v, int32_t* latents, void* stream);
+
 /* One batch of 3D Chairs sequences gathered from the decoded views resident in HBM (reference: data/chairs.py:45-64 `get_sequence` +
  * `__getitem__`, for a whole batch of items).  frames [n_objects, views_per_object, H, W, C] uint8, HWC as `np.array(Image.open(f))`
  * yields; desc [rows, 2] int32 = (object, first view); out [rows, seq_len, C, H, W] (fp32 or a 16-bit type).  Frame t of a row is view

@@ -1,4 +1,5 @@
-// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253), the 3D
+// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253) and the
+// Moving-MNIST test set in one launch (reference: preprocessing/mnist/make_test_set.py; below the training generator), the 3D
 // Chairs batch gather (reference: data/chairs.py:45-64) and the table-driven window gather of the TaxiBJ timeline (reference:
 // data/taxibj.py:74-100), both at the end of this file.
 //
@@ -94,6 +95,113 @@ __global__ __launch_bounds__(256) void moving_mnist_kernel(const unsigned char* 
         }
         v = v > 255.f ? 255.f : v;
         vs_st(out, od, base + i, v / 255.f);
+    }
+}
+
+// ---- the Moving-MNIST TEST set (reference: preprocessing/mnist/make_test_set.py:58-91) ---------------------------------------------------
+// Thousands of long videos (5 000 x 100 frames), raw bytes instead of normalised floats, the latents (rounded position and speed per frame)
+// as a second output, and the file's time-major layout.  One workgroup per (video, chunk of `chunk_len` frames); with enough videos a chunk
+// is the whole video, so each trajectory is walked exactly once:
+//   1. thread d < nd walks digit d's trajectory with the arithmetic of moving_mnist_kernel (frames before the chunk are replayed, not
+//      recorded) and leaves (row, column) per frame in LDS and (row, column, row speed, column speed) in `latents`;
+//   2. the workgroup copies its nd digit images into LDS once (a digit index outside [0, n_digits_total) is never read: zeros);
+//   3. per frame every thread builds G consecutive pixels (16 bytes: G = 16 as uint8, 4 as fp32) from the LDS digits and stores them as one
+//      16-byte vector: at F = 64 as uint8 a frame is exactly one store per thread, a wave writes 1 KiB contiguous.  When the G pixels
+//      share a row (F % G == 0) the row is tested once per digit, and most rows miss a digit.
+// Frame (t, v) starts at element t * st + v * sv.  VEC needs F * F % G == 0 and 16-byte aligned frame starts (the entry point decides);
+// otherwise the same arithmetic goes element by element.  LDS: int2 pos[chunk_len][nd], then nd * dh * dw digit bytes.
+__device__ __forceinline__ unsigned mm_pixel(const int2* pos, const unsigned char* dig, int nd, int dh, int dw, int r, int c) {
+    unsigned v = 0;
+    for (int d = 0; d < nd; ++d) {
+        const int rr = r - pos[d].x, cc = c - pos[d].y;
+        if ((unsigned)rr < (unsigned)dh && (unsigned)cc < (unsigned)dw) v += dig[(d * dh + rr) * dw + cc];
+    }
+    return v > 255u ? 255u : v;
+}
+
+template <bool FP32, bool VEC>
+__global__ __launch_bounds__(256) void moving_mnist_testset_kernel(const unsigned char* __restrict__ digits, int64_t n_total, int dh, int dw,
+                                                                   const int* __restrict__ init, int n_videos, int nd, int T, int F, int chunks,
+                                                                   int chunk_len, void* frames, int64_t st, int64_t sv, int* latents) {
+    extern __shared__ int2 mm_lds[];
+    const int v = blockIdx.x / chunks, t0 = (blockIdx.x - v * chunks) * chunk_len;
+    const int len = T - t0 < chunk_len ? T - t0 : chunk_len;
+    int2* pos = mm_lds;
+    unsigned char* dig = reinterpret_cast<unsigned char*>(mm_lds + (size_t)chunk_len * nd);
+    const int tid = threadIdx.x, dsz = dh * dw;
+    if (tid < nd) {
+        const int* q = init + ((int64_t)v * nd + tid) * 5;
+        Traj s{(double)q[1], (double)q[2], q[3], q[4]};
+        const double x_max = (double)(F - dh), y_max = (double)(F - dw);
+        for (int tt = 0; tt < t0 + len; ++tt) {      // moving_mnist.py:166-175: bounce, record the rounded position and the speed, then move
+            process_collision(s, 0.0, x_max, 0.0, y_max);
+            if (tt >= t0) {
+                const int px = (int)rint(s.sx), py = (int)rint(s.sy);
+                pos[(tt - t0) * nd + tid] = make_int2(px, py);
+                if (latents) {
+                    int* l = latents + (((int64_t)tt * n_videos + v) * nd + tid) * 4;
+                    l[0] = px; l[1] = py; l[2] = s.dx; l[3] = s.dy;
+                }
+            }
+            s.sy += (double)s.dy;
+            s.sx += (double)s.dx;
+        }
+    }
+    for (int i = tid; i < nd * dsz; i += 256) {
+        const int d = i / dsz;
+        const int64_t idx = init[((int64_t)v * nd + d) * 5];
+        dig[i] = (idx >= 0 && idx < n_total) ? digits[idx * dsz + (i - d * dsz)] : (unsigned char)0;
+    }
+    __syncthreads();
+    const int FF = F * F;
+    if constexpr (VEC) {
+        constexpr int G = FP32 ? 4 : 16;
+        const int gpf = FF / G;
+        for (int g = tid; g < len * gpf; g += 256) {
+            const int f = g / gpf, p0 = (g - f * gpf) * G;
+            const int2* pf = pos + f * nd;
+            int r = p0 / F, c = p0 - r * F;
+            unsigned px[G];
+            if (F % G == 0) {                        // the G pixels share a row: one row test per digit, and most rows miss a digit
+#pragma unroll
+                for (int k = 0; k < G; ++k) px[k] = 0u;
+                for (int d = 0; d < nd; ++d) {
+                    const int rr = r - pf[d].x, c0 = c - pf[d].y;
+                    if ((unsigned)rr >= (unsigned)dh || c0 >= dw || c0 + G <= 0) continue;
+                    const unsigned char* row = dig + (d * dh + rr) * dw;
+#pragma unroll
+                    for (int k = 0; k < G; ++k)
+                        if ((unsigned)(c0 + k) < (unsigned)dw) px[k] += row[c0 + k];
+                }
+#pragma unroll
+                for (int k = 0; k < G; ++k) px[k] = px[k] > 255u ? 255u : px[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    px[k] = mm_pixel(pf, dig, nd, dh, dw, r, c);
+                    if (++c == F) { c = 0; ++r; }
+                }
+            }
+            const int64_t o = (int64_t)(t0 + f) * st + (int64_t)v * sv + p0;
+            if constexpr (FP32) {
+                const f32x4 w = {(float)px[0], (float)px[1], (float)px[2], (float)px[3]};
+                *reinterpret_cast<f32x4*>((float*)frames + o) = w;
+            } else {
+                u32x4 w;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) w[j] = px[4 * j] | (px[4 * j + 1] << 8) | (px[4 * j + 2] << 16) | (px[4 * j + 3] << 24);
+                *reinterpret_cast<u32x4*>((unsigned char*)frames + o) = w;
+            }
+        }
+    } else {
+        for (int i = tid; i < len * FF; i += 256) {
+            const int f = i / FF, p = i - f * FF;
+            const int r = p / F, c = p - r * F;
+            const unsigned val = mm_pixel(pos + f * nd, dig, nd, dh, dw, r, c);
+            const int64_t o = (int64_t)(t0 + f) * st + (int64_t)v * sv + p;
+            if constexpr (FP32) ((float*)frames)[o] = (float)val;
+            else ((unsigned char*)frames)[o] = (unsigned char)val;
+        }
     }
 }
 
@@ -255,5 +363,51 @@ extern "C" int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_tot
     hipLaunchKernelGGL(moving_mnist_kernel, dim3((unsigned)seq_len, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, digits, digit_h, digit_w, init,
                        num_digits, seq_len, frame_size, out, out_dtype);
     VS_CHECK_LAUNCH("vs_moving_mnist_batch");
+    return VS_OK;
+}
+
+extern "C" int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int n_videos,
+                                       int num_digits, int seq_len, int frame_size, void* frames, int frames_fp32, int64_t frame_stride_t,
+                                       int64_t frame_stride_v, int32_t* latents, void* stream) {
+    VS_CHECK_ARG(digits && init && frames, "vs_moving_mnist_testset: null pointer");
+    VS_CHECK_ARG(n_digits_total > 0 && digit_h > 0 && digit_w > 0 && n_videos > 0 && seq_len > 0, "vs_moving_mnist_testset: sizes must be positive");
+    VS_CHECK_ARG(num_digits >= 1 && num_digits <= MM_MAXD, "vs_moving_mnist_testset: 1..%d digits per video (got %d)", MM_MAXD, num_digits);
+    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "vs_moving_mnist_testset: a %d x %d digit does not fit a frame of %d", digit_h,
+                 digit_w, frame_size);
+    const int64_t FF = (int64_t)frame_size * frame_size;
+    // frames must not overlap: the faster-varying index steps over whole frames, the slower one over the whole extent of the faster one
+    const int64_t st = frame_stride_t, sv = frame_stride_v;
+    bool apart = st > 0 && sv > 0;
+    if (apart && seq_len > 1 && n_videos > 1) apart = st <= sv ? (st >= FF && sv >= (int64_t)seq_len * st) : (sv >= FF && st >= (int64_t)n_videos * sv);
+    else if (apart && seq_len > 1) apart = st >= FF;
+    else if (apart && n_videos > 1) apart = sv >= FF;
+    VS_CHECK_ARG(apart, "vs_moving_mnist_testset: strides (%lld, %lld) make the %d x %d frames of %lld elements overlap", (long long)st,
+                 (long long)sv, seq_len, n_videos, (long long)FF);
+    // few videos: several workgroups per video, each over a chunk of >= 8 frames, until about two workgroups per CU are in flight
+    int chunks = 1;
+    if (n_videos < 512) {
+        const int64_t want = vs_cdiv(512, n_videos), most = vs_cdiv(seq_len, 8);
+        chunks = (int)(want < most ? want : most);
+    }
+    const int chunk_len = (int)vs_cdiv(seq_len, chunks);
+    chunks = (int)vs_cdiv(seq_len, chunk_len);
+    VS_CHECK_ARG((int64_t)chunk_len * FF < (1ll << 31) && (int64_t)n_videos * chunks < (1ll << 31),
+                 "vs_moving_mnist_testset: %d frames of %d x %d per workgroup, or %d x %d workgroups, exceed 2^31", chunk_len, frame_size, frame_size,
+                 n_videos, chunks);
+    const size_t table = (size_t)chunk_len * num_digits * sizeof(int2), images = (size_t)num_digits * digit_h * digit_w;
+    if (table + images > 64 * 1024)
+        return vs_fail(VS_ERR_UNSUPPORTED, "vs_moving_mnist_testset: the trajectory table (%d frames x %d digits: %zu B) and the digit images (%zu B) "
+                       "exceed the 65536 B of LDS of a workgroup", chunk_len, num_digits, table, images);
+    const int esize = frames_fp32 ? 4 : 1;
+    const int vec = FF % (16 / esize) == 0 && (uintptr_t)frames % 16 == 0 && (st * esize) % 16 == 0 && (sv * esize) % 16 == 0;
+    const dim3 grid((unsigned)((int64_t)n_videos * chunks)), block(256);
+    const size_t lds = table + images;
+#define MM_TESTSET_LAUNCH(FP, VEC)                                                                                                               \
+    hipLaunchKernelGGL((moving_mnist_testset_kernel<FP, VEC>), grid, block, lds, (hipStream_t)stream, digits, n_digits_total, digit_h, digit_w, \
+                       (const int*)init, n_videos, num_digits, seq_len, frame_size, chunks, chunk_len, frames, st, sv, (int*)latents)
+    if (frames_fp32) { if (vec) MM_TESTSET_LAUNCH(true, true); else MM_TESTSET_LAUNCH(true, false); }
+    else { if (vec) MM_TESTSET_LAUNCH(false, true); else MM_TESTSET_LAUNCH(false, false); }
+#undef MM_TESTSET_LAUNCH
+    VS_CHECK_LAUNCH("vs_moving_mnist_testset");
     return VS_OK;
 }

@@ -56,6 +56,49 @@ def read_mnist_images(data_dir, train=True):
                             % (stem, data_dir))
 
 
+def read_mnist_labels(data_dir, train=False):
+    """uint8 [N] from the idx1-ubyte label file beside the images (`read_mnist_images` lists the locations; gzip or plain)."""
+    stem = 'train-labels-idx1-ubyte' if train else 't10k-labels-idx1-ubyte'
+    for base in (os.path.join(data_dir, 'MNIST', 'raw'), data_dir):
+        for name, opener in ((stem, open), (stem + '.gz', gzip.open)):
+            path = os.path.join(base, name)
+            if os.path.exists(path):
+                with opener(path, 'rb') as f:
+                    raw = f.read()
+                magic, n = np.frombuffer(raw[:8], dtype='>i4')
+                if magic != 2049:
+                    raise ValueError('%s is not an idx1-ubyte label file' % path)
+                return np.frombuffer(raw, dtype=np.uint8, offset=8)[:int(n)].copy()
+    raise FileNotFoundError('no %s[.gz] under %s (expected the raw MNIST files)' % (stem, data_dir))
+
+
+def draw_test_set(n_images, digit_shape, frame_size, max_speed, num_digits, seed):
+    """The draws of the reference's preprocessing/mnist/make_test_set.py, in its order, from the GLOBAL NumPy stream (which it reseeds):
+    np.random.seed(seed), the permutation of the test images, then per video and digit the four randint calls of `_compute_trajectory`
+    (start row, start column, row speed, column speed).  -> (digits_idx int64 [n_images], init int32 [n_images // num_digits, num_digits,
+    5]) with init[v, n, 0] = digits_idx[v * num_digits + n]; the n_images % num_digits last images of the permutation are unused."""
+    h, w = digit_shape
+    np.random.seed(seed)
+    digits_idx = np.random.permutation(n_images)
+    n_videos = n_images // num_digits
+    init = np.empty((n_videos, num_digits, 5), dtype=np.int32)
+    rnd = np.random.randint
+    for v in range(n_videos):
+        for n in range(num_digits):
+            init[v, n] = (digits_idx[v * num_digits + n], rnd(0, frame_size - h + 1), rnd(0, frame_size - w + 1),
+                          rnd(-max_speed, max_speed + 1), rnd(-max_speed, max_speed + 1))
+    return digits_idx, init
+
+
+_GENERATED = {}                  # the test sets generated in this process: one launch per (files, geometry, seed, device)
+
+
+def forget_generated():
+    """Release the test sets that `MovingMNIST.generated` keeps for the life of the process (8.2 GB of HBM for the reference's set); the
+    next call generates again.  Also the way to pick up idx files that changed under the same path: the key is the path, not the contents."""
+    _GENERATED.clear()
+
+
 class MovingMNIST:
     """Device-resident Moving MNIST.  `train=True`: videos generated per batch (`batch(B)` / DeviceMovingLoader); `train=False`: the
     precomputed test videos of the reference (`[s]mmnist_test_<n>digits_<nx>.npz`) kept in HBM."""
@@ -77,6 +120,8 @@ class MovingMNIST:
             self.digit_shape = (int(arr.shape[1]), int(arr.shape[2]))
             self.n_source = int(arr.shape[0])
             self.data = torch.from_numpy(arr).to(self.device)
+        elif isinstance(data, torch.Tensor):                     # `generated`: fp32 [N, T, 1, nx, nx], already in HBM
+            self.data = data
         else:
             self.data = torch.stack([torch.as_tensor(np.asarray(v), dtype=torch.float32) for v in data]).to(self.device)
 
@@ -132,6 +177,33 @@ class MovingMNIST:
             sequences = dataset['sequences']
             data = [sequences[:, i].astype(np.single) for i in range(sequences.shape[1])]
         return cls(data, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device=device)
+
+    @classmethod
+    def generated(cls, data_dir, nx, nt_cond, seq_len, max_speed, num_digits, device, seed=42, file_seq_len=100):
+        """The `train=False` set without its file: the videos `preprocessing/mnist/make_test_set.py --seed seed --seq_len file_seq_len`
+        would write from the t10k idx files under `data_dir`, rendered straight into HBM by one fp32 launch (vs_moving_mnist_testset).
+        `.data` equals, bit for bit, what `make_dataset(train=False)` loads from that file.  The object also keeps `latents` (int32
+        [file_seq_len, N, num_digits, 4] on the device), `test_images` (the t10k images, uint8 on the device, file order) and `digits_idx`
+        (the permutation: video v shows images digits_idx[v * num_digits + n]).  The global NumPy stream is left as it was found, and a
+        set is generated once per process: a second call with the same path, geometry, seed and device SHARES the tensors, so `.data`,
+        `latents` and `test_images` are read-only to every holder (`forget_generated()` releases them)."""
+        from .. import ops
+        device = torch.device(device)
+        key = (os.path.abspath(data_dir), nx, max_speed, num_digits, seed, file_seq_len, str(device))
+        if key not in _GENERATED:
+            images = read_mnist_images(data_dir, train=False)
+            state = np.random.get_state()
+            try:
+                digits_idx, init = draw_test_set(len(images), images.shape[1:], nx, max_speed, num_digits, seed)
+            finally:
+                np.random.set_state(state)
+            test_images = torch.from_numpy(images).to(device)
+            frames, latents = ops.moving_mnist_testset(test_images, init, file_seq_len, nx, fp32=True, time_major=False)
+            _GENERATED[key] = (frames, latents, test_images, digits_idx)
+        frames, latents, test_images, digits_idx = _GENERATED[key]
+        ds = cls(frames, nx, nt_cond, seq_len, max_speed, True, num_digits, False, device=device)
+        ds.latents, ds.test_images, ds.digits_idx = latents, test_images, digits_idx
+        return ds
 
 
 class DeviceMovingLoader:

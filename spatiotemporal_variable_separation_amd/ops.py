@@ -2338,6 +2338,46 @@ def moving_mnist_place(digits, positions, desc, seq_len, frame_size, out_dtype=t
     return out
 
 
+def moving_mnist_testset(digits, init, seq_len, frame_size, *, fp32=False, time_major=True):
+    """The Moving-MNIST test videos and their latents in ONE launch (vs_moving_mnist_testset).  digits uint8 [N, h, w] on the device; init
+    int32 [V, nd, 5] = (digit index, start row, start column, row speed, column speed), a host array or a tensor -> (frames, latents):
+    frames hold the raw values 0..255, uint8 or (fp32=True) float32, shaped [seq_len, V, 1, F, F] (time_major, the test file's layout) or
+    [V, seq_len, 1, F, F]; latents int32 [seq_len, V, nd, 4] = (row, column, row speed, column speed) per frame.  `init` is checked on the
+    host (a device tensor is read back: a host sync): a digit index outside [0, N) or a start position outside the frame raises, and so does a
+    non-zero speed along an axis on which the digit fills the frame (no room: the reference's bounce loop never ends there)."""
+    import numpy as np
+    require_cuda(digits)
+    host = init.detach().cpu().numpy() if isinstance(init, torch.Tensor) else np.asarray(init)
+    if digits.dtype != torch.uint8 or digits.dim() != 3 or host.dtype != np.int32 or host.ndim != 3 or host.shape[2] != 5 or host.shape[0] < 1 \
+            or int(seq_len) < 1:
+        raise _lib.VarsepHipError('moving_mnist_testset: digits uint8 [N, h, w], init int32 [V >= 1, nd, 5] and seq_len >= 1 expected')
+    N, h, w = digits.shape
+    V, nd = host.shape[0], host.shape[1]
+    seq_len, F = int(seq_len), int(frame_size)
+    if host[..., 0].min() < 0 or host[..., 0].max() >= N or host[..., 1:3].min() < 0 or host[..., 1].max() > F - h or host[..., 2].max() > F - w:
+        raise _lib.VarsepHipError('moving_mnist_testset: init names a digit outside [0, %d) or a start position outside the %d x %d frame'
+                                  % (N, F, F))
+    if (F == h and host[..., 3].any()) or (F == w and host[..., 4].any()):
+        # the reference's bounce loop never ends here (each pass mirrors the position about the single allowed point); the kernel's loop
+        # is bounded at 64 passes and would leave an arbitrary position
+        raise _lib.VarsepHipError('moving_mnist_testset: a %d x %d digit has no room to move in a %d x %d frame, yet init gives one a speed '
+                                  'along that axis (the reference does not terminate on this)' % (h, w, F, F))
+    digits = digits.contiguous()
+    device = digits.device
+    dev_init = init.to(device).contiguous() if isinstance(init, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(host)).to(device)
+    with torch.cuda.device(device):
+        dtype = torch.float32 if fp32 else torch.uint8
+        frames = torch.empty((seq_len, V, 1, F, F) if time_major else (V, seq_len, 1, F, F), dtype=dtype, device=device)
+        latents = torch.empty((seq_len, V, nd, 4), dtype=torch.int32, device=device)
+        stride_t, stride_v = (frames.stride(0), frames.stride(1)) if time_major else (frames.stride(1), frames.stride(0))
+        e0 = _pb()
+        check(_lib.load_library().vs_moving_mnist_testset(digits.data_ptr(), N, h, w, dev_init.data_ptr(), V, nd, seq_len, F, frames.data_ptr(),
+                                                          1 if fp32 else 0, stride_t, stride_v, latents.data_ptr(), stream_ptr()),
+              'vs_moving_mnist_testset')
+        _pe(e0, 'vs_moving_mnist_testset', nbytes=float(frames.numel() * frames.element_size() + latents.numel() * 4))
+    return frames, latents
+
+
 def frames_to_u8_nhwc(x):
     """[B, T, C, H, W] fp32 / 16-bit -> uint8 [B, T, H, W, C] on the device: (uint8)(x * 255.f), i.e. `x.mul(255).byte().permute(0, 1, 3, 4, 2)`
     bit for bit for x in [0, 1]; out-of-range values saturate to 0 / 255 (NaN -> 0) where torch's cast is undefined (vs_frames_to_u8_nhwc)."""

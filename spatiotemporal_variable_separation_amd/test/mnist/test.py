@@ -6,6 +6,8 @@ Forecasts the test set (MSE / PSNR / SSIM per sample, printed as the reference's
 each test video drives a forecast from a freshly generated training video.  The test set lives in HBM, the swap videos are rendered by
 the device generator from the global NumPy stream in the reference's order, the metrics run on the device (vs_frame_metrics) and every
 saved array is converted to uint8 on the device (vs_frames_to_u8_nhwc).  There is no CPU mode: --device is required.
+`--data_dir generated:D` needs only the raw MNIST idx files under D: the test set that preprocessing/mnist/make_test_set.py would write
+with its defaults is generated straight into HBM (`MovingMNIST.generated`), no .npz is read or written.
 """
 import os
 
@@ -17,9 +19,19 @@ from ...utils.metrics import frame_metrics
 from ..utils import add_precision_flag, base_parser, load_model, load_xp_config, print_results, seed_all, setup_device, to_host_u8
 
 
+GENERATED = 'generated:'         # --data_dir generated:D: the idx files are under D and the test set is generated in HBM, no .npz is read
+
+
+def split_data_dir(data_dir):
+    """(directory of the MNIST files, whether the test set is generated on the device instead of read from its file)."""
+    return (data_dir[len(GENERATED):], True) if data_dir.startswith(GENERATED) else (data_dir, False)
+
+
 def load_dataset(args, train=False, device='cuda'):
-    return MovingMNIST.make_dataset(args.data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, train,
-                                    device=device)
+    data_dir, generated = split_data_dir(args.data_dir)
+    if generated and not train:      # make_test_set.py's defaults: seed 42, 100 frames, frame size 64, speed 4
+        return MovingMNIST.generated(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, args.n_object, device)
+    return MovingMNIST.make_dataset(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, train, device=device)
 
 
 def test_batches(test_dataset, batch_size):
