@@ -411,6 +411,41 @@ int vs_resample_u8(const uint8_t* src, int64_t n, int H, int W, int C, int box_x
                    const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, int out_w, int out_h, uint8_t* out,
                    void* stream);
 
+/* PNG decoding on the device (csrc/vs_png.hip; the stream logic is csrc/vs_inflate_core.h): the IDAT streams of a batch of PNG files are
+ * inflated by vs_inflate_zlib, one wave per stream, and the filtered rows are turned into pixels by vs_png_unfilter.  Per-stream results
+ * are STATUS words, not return values: a damaged file fails alone, the launch returns VS_OK and its neighbours are decoded.            */
+#define VS_INFLATE_OK 0
+#define VS_INFLATE_HEADER 1      /* not a zlib header: CM != 8, window above 32 KiB, check bits wrong, or a preset dictionary (FDICT) */
+#define VS_INFLATE_BLOCK_TYPE 2  /* reserved block type 3 */
+#define VS_INFLATE_STORED_LEN 3  /* LEN and NLEN of a stored block disagree */
+#define VS_INFLATE_LENGTHS 4     /* code lengths: bad repeat, too many codes, over-subscribed or incomplete set, no end-of-block code */
+#define VS_INFLATE_SYMBOL 5      /* bits that are no code of the table, or an invalid length / distance symbol */
+#define VS_INFLATE_DISTANCE 6    /* a distance that reaches before the start of the output */
+#define VS_INFLATE_INPUT 7       /* the stream ends before the data does (also: offsets outside the packed buffer) */
+#define VS_INFLATE_OUT_LONG 8    /* more output than out_len (also: out_len outside 0 .. out_stride) */
+#define VS_INFLATE_OUT_SHORT 9   /* the stream ends with less output than out_len */
+#define VS_INFLATE_ADLER 10      /* the Adler-32 trailer does not match the bytes produced */
+#define VS_PNG_BAD_FILTER 11     /* vs_png_unfilter: a row with a filter type above 4 */
+
+/* n zlib streams (RFC 1950 framing, RFC 1951 stored / fixed / dynamic blocks in any number, lengths 3..258, distances 1..32768,
+ * overlapping copies) into n output slots, byte for byte what zlib's inflate produces; trailing bytes after the Adler-32 are ignored.
+ *   packed [packed_bytes] uint8: the streams back to back; stream i is bytes offsets[i] .. offsets[i + 1] (offsets int64 [n + 1]); no
+ *   alignment is required of packed, of a stream's start or of out.
+ *   out: slot i is the out_stride bytes from out + i * out_stride; out_len int64 [n]: the exact number of bytes stream i must produce.
+ *   status int32 [n] receives a VS_INFLATE_* code, produced int64 [n] the bytes produced (on a failure: before it was met).
+ * One wave per stream; the 32 KiB history is a window in LDS that is flushed to the slot in 4 KiB pieces.  The kernel terminates on any
+ * input, reads nothing outside a stream's bytes and writes nothing outside its slot (csrc/vs_inflate_core.h states why).  VS_ERR_ARG (and
+ * nothing launched) for a null pointer, n < 1, packed_bytes < 0, out_stride < 1 or n above the grid limit.                             */
+int vs_inflate_zlib(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets, int64_t n, const int64_t* out_len, uint8_t* out,
+                    int64_t out_stride, int32_t* status, int64_t* produced, void* stream);
+
+/* PNG row filters undone (all five types, bpp = C, the row above the first taken as zeros): raw slot i (raw + i * raw_stride) holds H rows
+ * of 1 + W * C bytes, pixels is uint8 [n, H, W, C].  status int32 [n] is vs_inflate_zlib's: an image whose status is not 0 is skipped (its
+ * pixels are left as they are), and an image with a filter byte above 4 gets VS_PNG_BAD_FILTER.  One workgroup per image, one wave per
+ * channel, 64 rows at a time as a skewed wavefront (lane k works on row y + k, one pixel behind lane k - 1).  VS_ERR_ARG for a null
+ * pointer, a non-positive size, C outside 1..4, raw_stride < H * (1 + W * C), n above the grid limit or a row of more than 65536 bytes. */
+int vs_png_unfilter(const uint8_t* raw, int64_t raw_stride, int64_t n, int H, int W, int C, uint8_t* pixels, int32_t* status, void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

@@ -9,7 +9,12 @@ item index follow the reference line by line, so that a seeded sampler visits th
 
 The 64 x 64 views are the output of the reference's preprocessing/chairs/gen_chairs.py over the original 600 x 600 renders (crop, Lanczos
 resize).  That step runs on the device here (ops.resample_lanczos_u8, PIL's arithmetic bit for bit): preprocessing/chairs/gen_chairs.py
-writes the files, `Chairs.from_raw` fills `frames` from the raw renders without writing any.  PNG decoding stays on the host.
+writes the files, `Chairs.from_raw` fills `frames` from the raw renders without writing any.
+
+The raw renders themselves can be decoded on the device too (ops.png_decode_rgb8: inflate + row filters, csrc/vs_png.hip): only the
+compressed bytes are uploaded, and the bytes are the host route's.  `decode='host' | 'device'` of `prepare_renders`, `gen_chairs.generate`
+and `Chairs.from_raw` selects the decoder; None reads the environment variable VARSEP_CHAIRS_DECODE (`host` or `device`), and when that is
+unset the device decodes where PIL does not import and the target is a GPU, the host otherwise (`chairs_decoder`).
 """
 import os
 import re
@@ -47,13 +52,16 @@ def _paeth_row(cur, up, bpp):
         cur[i] = (cur[i] + pred) & 255
 
 
-def read_png_rgb8(path):
-    """uint8 [H, W, 3] of a non-interlaced 8-bit RGB PNG, decoded with zlib and NumPy only (all five filter types).  Used when PIL is
-    not importable; ValueError for any other kind of file."""
-    with open(path, 'rb') as f:
-        raw = f.read()
+class PngNotCovered(ValueError):
+    """A file that may well be a valid image, but not one the device decoder covers (8-bit non-interlaced RGB PNG)."""
+
+
+def png_chunks(raw, path):
+    """(IHDR fields (width, height, depth, colour, compression, filter, interlace), [IDAT bodies]) of the bytes of a PNG file: signature,
+    IHDR, the IDAT chunks up to IEND.  ValueError naming `path` for a file without the signature (PngNotCovered), a truncated chunk or a
+    missing header."""
     if raw[:8] != _PNG_MAGIC:
-        raise ValueError('%s: not a PNG file' % path)
+        raise PngNotCovered('%s: not a PNG file' % path)
     pos, idat, header = 8, [], None
     while pos + 8 <= len(raw):
         length, kind = struct.unpack('>I4s', raw[pos:pos + 8])
@@ -69,6 +77,15 @@ def read_png_rgb8(path):
         pos += 12 + length
     if header is None:
         raise ValueError('%s: PNG without a header' % path)
+    return header, idat
+
+
+def read_png_rgb8(path):
+    """uint8 [H, W, 3] of a non-interlaced 8-bit RGB PNG, decoded with zlib and NumPy only (all five filter types).  Used when PIL is
+    not importable; ValueError for any other kind of file."""
+    with open(path, 'rb') as f:
+        raw = f.read()
+    header, idat = png_chunks(raw, path)
     width, height, depth, colour, _, _, interlace = header
     if depth != 8 or colour != 2 or interlace != 0:
         raise ValueError('%s: an 8-bit non-interlaced RGB PNG is expected (bit depth %d, colour type %d, interlace %d)'
@@ -191,10 +208,75 @@ def decode_renders(paths, box, image_module=None):
     return out
 
 
-def prepare_renders(paths, box, image_size, device, image_module=None, timings=None):
-    """uint8 [n, image_size, image_size, 3] on `device`: the raw renders cropped to `box` and resized with PIL's Lanczos filter -- decode
-    on the host, ONE upload, ONE launch (ops.resample_lanczos_u8).  timings: optional dict; seconds are added to 'decode', 'upload' and
-    'kernel' (which synchronises the device after each stage)."""
+DECODE_ENV = 'VARSEP_CHAIRS_DECODE'
+
+
+def chairs_decoder(decode=None, device=None):
+    """'host' or 'device': who decodes the raw renders.  The keyword wins; None reads the environment variable VARSEP_CHAIRS_DECODE; when that
+    is unset (or empty) the device decodes where PIL does not import and `device` is a GPU, and the host does otherwise."""
+    source = 'decode'
+    if decode is None:
+        decode, source = os.environ.get(DECODE_ENV) or None, DECODE_ENV
+    if decode is None:
+        on_gpu = device is not None and torch.device(device).type == 'cuda'
+        return 'device' if _pil_image() is None and on_gpu else 'host'
+    if decode not in ('host', 'device'):
+        raise ValueError("%s must be 'host' or 'device' (got %r)" % (source, decode))
+    return decode
+
+
+def read_files(paths):
+    """The bytes of every file, read on at most MAX_DECODE_WORKERS threads; ValueError naming a file that is missing."""
+    def read(path):
+        if not os.path.isfile(path):
+            raise ValueError('%s: missing' % path)
+        with open(path, 'rb') as f:
+            return f.read()
+
+    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_WORKERS, len(paths))) as pool:
+        return list(pool.map(read, paths, chunksize=1))
+
+
+def _prepare_on_device(paths, box, image_size, device, timings):
+    """The device route of `prepare_renders`, or None when a file of the batch is not one the kernels cover."""
+    left, upper, right, lower = box
+    if not (0 <= left < right and 0 <= upper < lower):
+        raise ValueError('the crop box %s is empty' % (tuple(box),))
+    t0 = time.perf_counter()
+    try:
+        width, height, packed, offsets = ops.png_pack(read_files(paths), paths)
+    except PngNotCovered:
+        return None
+    if right > width or lower > height:
+        raise ValueError('%s: the crop box %s is not inside the %d x %d image' % (paths[0], tuple(box), width, height))
+    t1 = time.perf_counter()
+    packed_d, offsets_d = torch.from_numpy(packed).to(device), torch.from_numpy(offsets).to(device)
+    if timings is not None:
+        torch.cuda.synchronize(device)
+    t2 = time.perf_counter()
+    pixels, status = ops.png_decode_packed(packed_d, offsets_d, height, width, 3)
+    out = ops.resample_lanczos_u8(pixels, box, image_size)
+    err = ops.png_status_error(status, paths)             # (reads the statuses back: the three launches are complete)
+    if err is not None:
+        raise err
+    if timings is not None:
+        for key, dt in (('decode', t1 - t0), ('upload', t2 - t1), ('kernel', time.perf_counter() - t2)):
+            timings[key] = timings.get(key, 0.0) + dt
+    return out
+
+
+def prepare_renders(paths, box, image_size, device, image_module=None, timings=None, decode=None):
+    """uint8 [n, image_size, image_size, 3] on `device`: the raw renders cropped to `box` and resized with PIL's Lanczos filter.
+    decode (see `chairs_decoder`) = 'host': decode on the host, ONE upload of the pixels, ONE launch (ops.resample_lanczos_u8).
+    'device': the files are read and their compressed streams packed on the host, the COMPRESSED bytes are uploaded, and three launches
+    (inflate, row filters, resample) do the rest -- the same bytes; a file whose decoding fails raises ValueError naming it and the reason.
+    If a file of the batch is an image the kernels do not cover (an interlaced PNG, say), the whole batch takes the host route.
+    timings: optional dict; seconds are added to 'decode' (host: decoding; device: reading and packing), 'upload' (host: the pixels;
+    device: the compressed bytes) and 'kernel' (all launches), and the device is synchronised after each stage."""
+    if chairs_decoder(decode, device) == 'device':
+        out = _prepare_on_device(paths, tuple(int(v) for v in box), image_size, device, timings)
+        if out is not None:
+            return out
     t0 = time.perf_counter()
     raw = decode_renders(paths, box, image_module)
     t1 = time.perf_counter()
@@ -216,18 +298,21 @@ class Chairs(DeviceSet):
     max_length = 62
 
     @classmethod
-    def from_raw(cls, train, data_root, nt_cond, seq_len=15, image_size=64, box=RAW_BOX, device=None):
+    def from_raw(cls, train, data_root, nt_cond, seq_len=15, image_size=64, box=RAW_BOX, device=None, decode=None):
         """The same set built straight from the RAW renders (`renders/<any name>.png`, 600 x 600 in the original set; exactly 62 per
         object), with no files written: every view is decoded, cropped to `box` and resized on the device (ops.resample_lanczos_u8) as
         preprocessing/chairs/gen_chairs.py would prepare it.  Same listing, shuffle and split: `frames` holds the bytes of
         `Chairs(...)` on a tree that `gen_chairs.generate` prepared.  The constructor itself runs, with its own signature (a subclass
-        such as the content-swap set of test/chairs/test_disentanglement.py needs no change); it finds the box on the instance."""
+        such as the content-swap set of test/chairs/test_disentanglement.py needs no change); it finds the box on the instance, and
+        `decode` ('host', 'device' or None: see `chairs_decoder`) likewise."""
         self = cls.__new__(cls)
         self.raw_box = tuple(int(v) for v in box)
+        self.raw_decode = decode
         self.__init__(train, data_root, nt_cond, seq_len=seq_len, image_size=image_size, device=device)
         return self
 
     raw_box = None                                       # set per instance by `from_raw`, before the constructor runs
+    raw_decode = None                                    # likewise: who decodes the raw renders
 
     def __init__(self, train, data_root, nt_cond, seq_len=15, image_size=64, device=None):
         self.train, self.nt_cond = train, nt_cond
@@ -268,7 +353,7 @@ class Chairs(DeviceSet):
                 if len(names) != self.max_length:
                     raise ValueError('%s: %d raw renders, exactly %d are expected' % (os.path.join(self.data_root, obj), len(names), self.max_length))
                 paths += [os.path.join(renders, f) for f in names]
-            out = prepare_renders(paths, box, size, self.device, image_module)
+            out = prepare_renders(paths, box, size, self.device, image_module, decode=self.raw_decode)
             frames[start:start + len(paths) // self.max_length] = out.view(-1, self.max_length, size, size, 3)
         return frames
 

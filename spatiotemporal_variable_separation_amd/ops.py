@@ -2039,6 +2039,119 @@ def resample_lanczos_u8(images_u8, box, size):
     return out
 
 
+# ---- PNG decoding on the device (csrc/vs_png.hip) ----------------------------------------------------------------------------------
+INFLATE_STATUS = {1: 'bad zlib header', 2: 'reserved block type', 3: 'stored-block length mismatch',
+                  4: 'bad, over-subscribed or incomplete code lengths', 5: 'invalid symbol or distance code',
+                  6: 'distance before the start of the output', 7: 'compressed data ends early', 8: 'more image data than the header announces',
+                  9: 'less image data than the header announces', 10: 'Adler-32 mismatch', 11: 'unknown PNG filter type'}
+
+
+def inflate_zlib(packed, offsets, out_len, out_stride):
+    """`n` zlib streams in one launch of vs_inflate_zlib.  packed: uint8 [bytes] on the device, the streams back to back (any alignment);
+    offsets: int64 [n + 1]; out_len: int64 [n], the exact length every stream must produce.  Returns (out uint8 [n, out_stride], status
+    int32 [n], produced int64 [n]); stream i is out[i, :out_len[i]] when status[i] == 0 (INFLATE_STATUS names the other values), and a
+    damaged stream fails alone.  Bytes of a slot beyond what its stream produced are not written."""
+    require_cuda(packed, offsets, out_len)
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 or out_len.dtype != torch.int64 \
+            or out_len.dim() != 1 or offsets.numel() != out_len.numel() + 1 or out_len.numel() < 1 or int(out_stride) < 1:
+        raise _lib.VarsepHipError('inflate_zlib: packed uint8 [bytes], offsets int64 [n + 1], out_len int64 [n], n >= 1 and out_stride >= 1 '
+                                  'expected')
+    if not packed.is_contiguous():
+        packed = packed.contiguous()
+    offsets, out_len = offsets.contiguous(), out_len.contiguous()
+    n, device = out_len.numel(), packed.device
+    with torch.cuda.device(device):
+        out = torch.empty((n, int(out_stride)), dtype=torch.uint8, device=device)
+        status = torch.empty((n,), dtype=torch.int32, device=device)
+        produced = torch.empty((n,), dtype=torch.int64, device=device)
+        e0 = _pb()
+        check(_lib.load_library().vs_inflate_zlib(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, out_len.data_ptr(), out.data_ptr(),
+                                                  int(out_stride), status.data_ptr(), produced.data_ptr(), stream_ptr()), 'vs_inflate_zlib')
+        _pe(e0, 'vs_inflate_zlib', nbytes=float(packed.numel()) + float(n) * int(out_stride))
+    return out, status, produced
+
+
+def png_unfilter(raw, status, H, W, C):
+    """raw: uint8 [n, stride >= H * (1 + W * C)] on the device, the filtered rows of n images (what inflate_zlib returns); status int32 [n]
+    of the inflate launch -> pixels uint8 [n, H, W, C], all five PNG filter types undone in one launch of vs_png_unfilter.  An image whose
+    status is not 0 is skipped; a filter byte above 4 sets its status to 11 (in place)."""
+    require_cuda(raw, status)
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.stride(1) != 1 or status.dtype != torch.int32 or status.dim() != 1 \
+            or not status.is_contiguous() or status.numel() != raw.shape[0]:
+        raise _lib.VarsepHipError('png_unfilter: raw uint8 [n, stride] with contiguous rows and status int32 [n] expected')
+    n, device = raw.shape[0], raw.device
+    with torch.cuda.device(device):
+        pixels = torch.empty((n, int(H), int(W), int(C)), dtype=torch.uint8, device=device)
+        e0 = _pb()
+        check(_lib.load_library().vs_png_unfilter(raw.data_ptr(), raw.stride(0), n, int(H), int(W), int(C), pixels.data_ptr(), status.data_ptr(),
+                                                  stream_ptr()), 'vs_png_unfilter')
+        _pe(e0, 'vs_png_unfilter', nbytes=float(n) * int(H) * (1 + 2 * int(W) * int(C)))
+    return pixels
+
+
+def png_pack(blobs, names=None):
+    """The host part of png_decode_rgb8: every file's chunks are parsed as data/chairs.py's `read_png_rgb8` parses them (signature, IHDR,
+    concatenated IDAT bodies, stop at IEND) and the zlib streams are packed back to back.  Returns (W, H, packed uint8 array, offsets int64
+    [n + 1]).  ValueError naming the file for a damaged file or one of another size than the first; `chairs.PngNotCovered` (a ValueError)
+    for a file the kernels do not decode (no PNG signature, or not 8-bit non-interlaced RGB)."""
+    import numpy as np
+    from .data import chairs
+    names = ['image %d of the batch' % i for i in range(len(blobs))] if names is None else list(names)
+    if not blobs or len(names) != len(blobs):
+        raise ValueError('png_pack: a non-empty batch and one name per file are expected')
+    streams, size = [], None
+    for blob, name in zip(blobs, names):
+        (width, height, depth, colour, _, _, interlace), idat = chairs.png_chunks(blob, name)
+        if (depth, colour, interlace) != (8, 2, 0):
+            raise chairs.PngNotCovered('%s: an 8-bit non-interlaced RGB PNG is expected (bit depth %d, colour type %d, interlace %d)'
+                                       % (name, depth, colour, interlace))
+        if width < 1 or height < 1:
+            raise ValueError('%s: a PNG of %d x %d pixels' % (name, width, height))
+        if size is None:
+            size = (width, height)
+        elif (width, height) != size:
+            raise ValueError('%s: a %d x %d image among %d x %d ones (a batch is one tensor)' % (name, width, height, size[0], size[1]))
+        streams.append(b''.join(idat))
+    offsets = np.zeros(len(streams) + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in streams], out=offsets[1:])
+    packed = np.frombuffer(bytearray(b''.join(streams) or b'\0'), dtype=np.uint8)      # (writable: torch shares it)
+    return size[0], size[1], packed, offsets
+
+
+def png_decode_packed(packed, offsets, H, W, C=3):
+    """The device part: packed uint8 [bytes] and offsets int64 [n + 1] on the device -> (pixels uint8 [n, H, W, C], status int32 [n]); the
+    two launches."""
+    n = offsets.numel() - 1
+    size = H * (1 + W * C)
+    out_len = torch.full((n,), size, dtype=torch.int64, device=packed.device)
+    raw, status, _ = inflate_zlib(packed, offsets, out_len, size)
+    return png_unfilter(raw, status, H, W, C), status
+
+
+def png_status_error(status, names=None):
+    """The ValueError for the first non-zero entry of a status tensor (naming the file and the reason), or None.  Reads the statuses back."""
+    bad = status.cpu().numpy()
+    for i in bad.nonzero()[0]:
+        name = names[i] if names is not None else 'image %d of the batch' % i
+        return ValueError('%s: %s (decoder status %d)' % (name, INFLATE_STATUS.get(int(bad[i]), 'unknown status'), int(bad[i])))
+    return None
+
+
+def png_decode_rgb8(blobs, names=None, device=None, check_status=False):
+    """blobs: the bytes of n non-interlaced 8-bit RGB PNG files of one common size -> (uint8 [n, H, W, 3] on the device, status int32 [n]):
+    the chunks are parsed and the compressed streams packed on the host, only the COMPRESSED bytes are uploaded, and two launches decode
+    them (inflate, then the row filters).  Pixels of image i are valid where status[i] == 0; check_status=True reads the statuses back
+    and raises ValueError naming the first failed file and the reason."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    W, H, packed, offsets = png_pack(blobs, names)
+    pixels, status = png_decode_packed(torch.from_numpy(packed).to(device), torch.from_numpy(offsets).to(device), H, W, 3)
+    if check_status:
+        err = png_status_error(status, names)
+        if err is not None:
+            raise err
+    return pixels, status
+
+
 def chairs_gather(frames_u8, desc, seq_len, out_dtype=torch.float32, validate=True):
     """frames_u8 uint8 [n_objects, views, H, W, C] on the device, desc int32 [rows, 2] = (object, first view) -> [rows, seq_len, C, H, W]
     in `out_dtype`: frame t of a row is view (first + t) % views, values byte / 255 (vs_chairs_gather, one launch).

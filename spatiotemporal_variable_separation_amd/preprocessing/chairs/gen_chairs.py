@@ -6,8 +6,9 @@ For every object of D/rendered_chairs, the i-th of its sorted raw renders (600 x
 resized to image_size x image_size with PIL's Lanczos filter and written as renders/{i}.png: the files `Chairs(D, ...)`, the reference's
 loader and test/chairs/test_disentanglement.py read.  The reference does this with PIL, one image after the other on the host; here the
 crop and the resize of a batch of whole objects are ONE launch (ops.resample_lanczos_u8, csrc/vs_resample.hip), which reproduces PIL's
-8-bit arithmetic bit for bit.  Decoding the PNG files stays on the host (PIL when it imports, data/chairs.py's own reader otherwise) and
-dominates the run.  One deviation from the reference: names of the form <digits>.png are left out of an object's listing, so a second
+8-bit arithmetic bit for bit.  The PNG files are decoded on the host (PIL when it imports, data/chairs.py's own reader otherwise) or on the
+device (ops.png_decode_rgb8: only the compressed bytes are uploaded; two more launches, the same bytes).  The environment variable
+VARSEP_CHAIRS_DECODE=host|device selects the decoder; unset, the device decodes where PIL does not import.  One deviation from the reference: names of the form <digits>.png are left out of an object's listing, so a second
 run reproduces the first (the reference would feed its own outputs back in).  There is no CPU mode: --device is required.
 `--chairs_raw` of main.py and test/chairs/test_disentanglement_raw.py build the same set straight in HBM, without files (`Chairs.from_raw`).
 """
@@ -35,10 +36,11 @@ def _save_all(paths, images, image_module):
             pass
 
 
-def generate(data_dir, image_size, device, box=C.RAW_BOX, timings=None):
+def generate(data_dir, image_size, device, box=C.RAW_BOX, timings=None, decode=None):
     """The reference's `generate` (gen_chairs.py:23-33) plus the device and the crop box.  Works in batches of whole objects: decode, one
     upload, one launch, one download, write.  Returns the number of files written.  timings: optional dict that receives the seconds
-    spent in 'decode', 'upload', 'kernel', 'download' and 'write' (the device is then synchronised after every stage)."""
+    spent in 'decode', 'upload', 'kernel', 'download' and 'write' (the device is then synchronised after every stage).  decode: 'host',
+    'device' or None (the environment variable VARSEP_CHAIRS_DECODE, then the default rule of data/chairs.py's `chairs_decoder`)."""
     device = C.require_gpu('Chairs preprocessing', device)
     box = tuple(int(v) for v in box)
     root, objects = C.list_objects(data_dir)
@@ -53,7 +55,7 @@ def generate(data_dir, image_size, device, box=C.RAW_BOX, timings=None):
             targets += [os.path.join(renders, '%d.png' % i) for i in range(len(names))]
         if not sources:
             continue
-        out = C.prepare_renders(sources, box, image_size, device, image_module, timings)
+        out = C.prepare_renders(sources, box, image_size, device, image_module, timings, decode)
         t0 = time.perf_counter()
         host = out.cpu().numpy()
         t1 = time.perf_counter()
