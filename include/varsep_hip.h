@@ -446,6 +446,31 @@ int vs_inflate_zlib(const uint8_t* packed, int64_t packed_bytes, const int64_t* 
  * pointer, a non-positive size, C outside 1..4, raw_stride < H * (1 + W * C), n above the grid limit or a row of more than 65536 bytes. */
 int vs_png_unfilter(const uint8_t* raw, int64_t raw_stride, int64_t n, int H, int W, int C, uint8_t* pixels, int32_t* status, void* stream);
 
+/* DEFLATE compression on the device (csrc/vs_deflate.hip; the logic is csrc/vs_deflate_core.h): the encoder that writes .npz members from
+ * arrays in HBM.  The input is cut into independent chunks; every chunk becomes one stored, fixed or dynamic block (the smallest by exact
+ * bit count) with literals and distance-1 run matches, and ends with an empty stored block (00 00 FF FF on a byte boundary), so chunks
+ * concatenate by bytes into a raw RFC 1951 stream WITHOUT a final block: the writer of the stream appends 03 00.  There is no window
+ * search: content without byte runs is Huffman-coded only.                                                                            */
+#define VS_DEFLATE_MIN_CHUNK 1024
+#define VS_DEFLATE_MAX_CHUNK 32768    /* also the default (the size against zlib by chunk length) */
+#define VS_DEFLATE_SLOT_EXTRA 10      /* worst case of a chunk: its bytes + 5 of a stored block's header + 5 of the closing marker */
+/* src [n_bytes] uint8 (no alignment, any length; the last chunk is short) -> chunk c compressed into the slot slots + c * slot_stride, its
+ * byte count into sizes[c] (int64 [ceil(n_bytes / chunk_bytes)]).  One wave per chunk; nothing is written past sizes[c] bytes of a slot,
+ * and sizes[c] <= chunk length + VS_DEFLATE_SLOT_EXTRA.  n_bytes == 0 launches nothing.  VS_ERR_ARG (and nothing launched) for a null
+ * pointer, n_bytes < 0, chunk_bytes outside VS_DEFLATE_MIN_CHUNK .. VS_DEFLATE_MAX_CHUNK, slot_stride < chunk_bytes + VS_DEFLATE_SLOT_EXTRA
+ * or more chunks than a grid holds.                                                                                                    */
+int vs_deflate_chunks(const uint8_t* src, int64_t n_bytes, int chunk_bytes, uint8_t* slots, int64_t slot_stride, int64_t* sizes, void* stream);
+/* The used part of every slot to its place in one buffer: dst[offsets[c] .. offsets[c] + sizes[c]) = slot c (offsets int64 [n_chunks]: the
+ * exclusive prefix sum of sizes).  A chunk whose size is outside 0 .. slot_stride or whose bytes would leave dst [dst_bytes] is not copied.
+ * VS_ERR_ARG for a null pointer, n_chunks < 1 or above the grid limit, slot_stride < 1 or dst_bytes < 0.                               */
+int vs_deflate_pack(const uint8_t* slots, int64_t slot_stride, const int64_t* sizes, const int64_t* offsets, int64_t n_chunks, uint8_t* dst,
+                    int64_t dst_bytes, void* stream);
+/* CRC-32 (the zip / zlib polynomial) of src [n_bytes] in pieces: partial[p], p < ceil(n_bytes / chunk_bytes), receives the CRC of piece p
+ * advanced past the bytes that follow it (a multiplication by x^(8 bytes) mod P), piece 0 also the term of the initial state, so that
+ * zlib.crc32(data, init) == ~(XOR of the partials).  One wave per piece.  n_bytes == 0 launches nothing (the CRC is init).  VS_ERR_ARG for
+ * a null pointer, n_bytes < 0, chunk_bytes outside 256 .. 2^24 or more pieces than a grid holds.                                         */
+int vs_crc32(const uint8_t* src, int64_t n_bytes, int64_t chunk_bytes, uint32_t init, uint32_t* partial, void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

@@ -1,0 +1,159 @@
+// vs_deflate.hip -- DEFLATE compression on the device: vs_deflate_chunks (one wave per independent chunk), vs_deflate_pack (the used part of
+// every slot into one buffer) and vs_crc32 (the CRC a zip member needs, piecewise).  An array that is already in HBM -- the Moving-MNIST
+// test videos -- is compressed where it lies; only the compressed bytes cross to the host, which writes them into the .npz member.
+//
+// vs_deflate_chunks.  The logic (runs, tokens, code construction, the choice among stored / fixed / dynamic by exact bits, header, emission)
+// is csrc/vs_deflate_core.h, which also runs on the CPU; this file adds the wave primitives and the moves between HBM and LDS.  ONE
+// WORKGROUP OF ONE WAVE PER CHUNK of at most 32 KiB.  Per workgroup, in LDS (about 73 KiB: two workgroups per CU of 160 KiB):
+//   * the chunk, staged with 16-byte loads (byte loads up to the first and after the last 16-byte boundary of the source), at the source's
+//     own offset inside a 16-byte line;
+//   * the run-start mask (one bit per position: 64 positions per __ballot), histogram, code tables and header scratch (VsdWork, 8.5 KiB);
+//   * the image of the chunk's output.  Each lane encodes the token that starts at its position; a wave prefix sum of the bit lengths
+//     gives every lane its bit offset and the bits are OR-ed into the image with LDS atomics.  A window of 64 background positions (no
+//     run starts, no 258-piece starts) is recognised from the mask alone and skipped.
+// The image is written to the slot with 16-byte stores when the slot is aligned so, by bytes otherwise; only the chunk's own byte count
+// is written, and that count is at most chunk length + VS_DEFLATE_SLOT_EXTRA, which the entry point checks against slot_stride.
+//
+// vs_crc32.  One wave per piece, four waves per workgroup sharing the byte table in LDS.  Each lane takes a sub-piece, computes its plain
+// CRC (word loads) and advances it past all bytes behind it by square-and-multiply in GF(2)[x] / P; the lanes' results are XOR-ed.
+#include "vs_common.h"
+
+namespace {
+
+__device__ __forceinline__ int wave_incl_scan(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+
+}  // namespace
+
+// the wave's forms of the core's primitives (the core is compiled for the device only here)
+#define VSD_HD __device__ inline
+#define VSD_SYNC() __syncthreads()
+#define VSD_BALLOT(p) ((uint64_t)__ballot(p))
+#define VSD_SCAN(v, before, total) ((total) = wave_incl_scan(v), (before) = (total) - (v), (total) = __shfl((total), 63, 64))
+#define VSD_ATOMIC_ADD(p, v) atomicAdd((p), (v))
+#define VSD_ATOMIC_OR(p, v) atomicOr((p), (v))
+#include "vs_deflate_core.h"
+
+namespace {
+
+constexpr int STAGE_BYTES = VSD_MAX_CHUNK + 16;
+constexpr int IMAGE_WORDS = (VSD_MAX_CHUNK + VSD_SLOT_EXTRA + 3) / 4;
+
+__global__ __launch_bounds__(64) void deflate_chunks_kernel(const uint8_t* __restrict__ src, int64_t n_bytes, int chunk_bytes,
+                                                            uint8_t* __restrict__ slots, int64_t slot_stride, int64_t* __restrict__ sizes) {
+    __shared__ VsdWork work;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint32_t image[(IMAGE_WORDS + 3) / 4 * 4];
+    const int lane = threadIdx.x;
+    const int64_t c = blockIdx.x, lo = c * (int64_t)chunk_bytes;
+    const int n = (int)(n_bytes - lo < chunk_bytes ? n_bytes - lo : chunk_bytes);      // 1 .. chunk_bytes: the grid is ceil(n_bytes / chunk_bytes)
+    const uint8_t* in = src + lo;
+    const int a = (int)((uintptr_t)in & 15);
+    uint8_t* x = stage + a;                                                // x + i and in + i share their offset inside a 16-byte line
+    int head = (16 - a) & 15;
+    if (head > n) head = n;
+    const int vecs = (n - head) >> 4;
+    if (lane < head) x[lane] = in[lane];
+    for (int v = lane; v < vecs; v += 64)
+        *reinterpret_cast<u32x4*>(x + head + 16 * v) = *reinterpret_cast<const u32x4*>(in + head + 16 * v);
+    for (int i = head + 16 * vecs + lane; i < n; i += 64) x[i] = in[i];     // at most 15 bytes
+    const int size = vsd_deflate_chunk(x, n, &work, image, lane, 64);
+    uint8_t* slot = slots + c * slot_stride;
+    const uint8_t* img = reinterpret_cast<const uint8_t*>(image);
+    int done = 0;
+    if (((uintptr_t)slot & 15) == 0) {
+        const int full = size >> 4;
+        for (int v = lane; v < full; v += 64) reinterpret_cast<u32x4*>(slot)[v] = reinterpret_cast<const u32x4*>(image)[v];
+        done = full << 4;
+    }
+    for (int i = done + lane; i < size; i += 64) slot[i] = img[i];
+    if (lane == 0) sizes[c] = size;
+}
+
+__global__ __launch_bounds__(256) void deflate_pack_kernel(const uint8_t* __restrict__ slots, int64_t slot_stride, const int64_t* __restrict__ sizes,
+                                                           const int64_t* __restrict__ offsets, uint8_t* __restrict__ dst, int64_t dst_bytes) {
+    const int64_t c = blockIdx.x, size = sizes[c], off = offsets[c];
+    if (size < 0 || size > slot_stride || off < 0 || off > dst_bytes - size) return;
+    const uint8_t* s = slots + c * slot_stride;
+    uint8_t* d = dst + off;
+    int64_t head = (int64_t)((4 - ((uintptr_t)d & 3)) & 3);                 // the destination in words; the source by bytes (it is in cache)
+    if (head > size) head = size;
+    if ((int64_t)threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
+    const int64_t words = (size - head) >> 2;
+    for (int64_t wd = threadIdx.x; wd < words; wd += 256) {
+        const uint8_t* p = s + head + 4 * wd;
+        reinterpret_cast<uint32_t*>(d + head)[wd] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    }
+    for (int64_t i = head + 4 * words + threadIdx.x; i < size; i += 256) d[i] = s[i];
+}
+
+constexpr int CRC_WAVES = 4;
+
+__global__ __launch_bounds__(64 * CRC_WAVES) void crc32_kernel(const uint8_t* __restrict__ src, int64_t n_bytes, int64_t chunk_bytes, uint32_t init,
+                                                                uint32_t* __restrict__ partial, int64_t pieces) {
+    __shared__ uint32_t table[256];
+    table[threadIdx.x] = vsd_crc_table_entry(threadIdx.x);                  // 256 threads, 256 entries
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * CRC_WAVES + (threadIdx.x >> 6);
+    if (p >= pieces) return;
+    const int64_t lo = p * chunk_bytes, hi = lo + chunk_bytes < n_bytes ? lo + chunk_bytes : n_bytes;
+    const uint32_t r = wave_xor(vsd_crc_partial(table, src + lo, n_bytes, lo, hi, init, lane, 64));
+    if (lane == 0) partial[p] = r;
+}
+
+}  // namespace
+
+extern "C" int vs_deflate_chunks(const uint8_t* src, int64_t n_bytes, int chunk_bytes, uint8_t* slots, int64_t slot_stride, int64_t* sizes,
+                                 void* stream) {
+    VS_CHECK_ARG(src && slots && sizes, "vs_deflate_chunks: null pointer");
+    VS_CHECK_ARG(n_bytes >= 0, "vs_deflate_chunks: n_bytes %lld is negative", (long long)n_bytes);
+    VS_CHECK_ARG(chunk_bytes >= VS_DEFLATE_MIN_CHUNK && chunk_bytes <= VS_DEFLATE_MAX_CHUNK, "vs_deflate_chunks: chunk_bytes %d outside %d .. %d",
+                 chunk_bytes, VS_DEFLATE_MIN_CHUNK, VS_DEFLATE_MAX_CHUNK);
+    VS_CHECK_ARG(slot_stride >= (int64_t)chunk_bytes + VS_DEFLATE_SLOT_EXTRA, "vs_deflate_chunks: slot_stride %lld is below the worst case %d + %d",
+                 (long long)slot_stride, chunk_bytes, VS_DEFLATE_SLOT_EXTRA);
+    const int64_t chunks = (n_bytes + chunk_bytes - 1) / chunk_bytes;
+    VS_CHECK_ARG(chunks <= 2147483647ll, "vs_deflate_chunks: %lld chunks exceed the grid limit", (long long)chunks);
+    if (chunks == 0) return VS_OK;
+    hipLaunchKernelGGL(deflate_chunks_kernel, dim3((unsigned)chunks), dim3(64), 0, (hipStream_t)stream, src, n_bytes, chunk_bytes, slots, slot_stride,
+                       sizes);
+    VS_CHECK_LAUNCH("vs_deflate_chunks");
+    return VS_OK;
+}
+
+extern "C" int vs_deflate_pack(const uint8_t* slots, int64_t slot_stride, const int64_t* sizes, const int64_t* offsets, int64_t n_chunks, uint8_t* dst,
+                               int64_t dst_bytes, void* stream) {
+    VS_CHECK_ARG(slots && sizes && offsets && dst, "vs_deflate_pack: null pointer");
+    VS_CHECK_ARG(n_chunks >= 1 && slot_stride >= 1 && dst_bytes >= 0, "vs_deflate_pack: n_chunks %lld and slot_stride %lld must be positive, dst_bytes "
+                 "%lld non-negative", (long long)n_chunks, (long long)slot_stride, (long long)dst_bytes);
+    VS_CHECK_ARG(n_chunks <= 2147483647ll, "vs_deflate_pack: %lld chunks exceed the grid limit", (long long)n_chunks);
+    hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, slots, slot_stride, sizes, offsets, dst,
+                       dst_bytes);
+    VS_CHECK_LAUNCH("vs_deflate_pack");
+    return VS_OK;
+}
+
+extern "C" int vs_crc32(const uint8_t* src, int64_t n_bytes, int64_t chunk_bytes, uint32_t init, uint32_t* partial, void* stream) {
+    VS_CHECK_ARG(src && partial, "vs_crc32: null pointer");
+    VS_CHECK_ARG(n_bytes >= 0, "vs_crc32: n_bytes %lld is negative", (long long)n_bytes);
+    VS_CHECK_ARG(chunk_bytes >= 256 && chunk_bytes <= (1ll << 24), "vs_crc32: chunk_bytes %lld outside 256 .. 2^24", (long long)chunk_bytes);
+    const int64_t pieces = (n_bytes + chunk_bytes - 1) / chunk_bytes, blocks = (pieces + CRC_WAVES - 1) / CRC_WAVES;
+    VS_CHECK_ARG(blocks <= 2147483647ll, "vs_crc32: %lld pieces exceed the grid limit", (long long)pieces);
+    if (pieces == 0) return VS_OK;
+    hipLaunchKernelGGL(crc32_kernel, dim3((unsigned)blocks), dim3(64 * CRC_WAVES), 0, (hipStream_t)stream, src, n_bytes, chunk_bytes, init, partial,
+                       pieces);
+    VS_CHECK_LAUNCH("vs_crc32");
+    return VS_OK;
+}

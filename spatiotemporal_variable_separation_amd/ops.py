@@ -2504,3 +2504,85 @@ def frames_to_u8_nhwc(x):
         check(_lib.load_library().vs_frames_to_u8_nhwc(x.data_ptr(), dtype_code(x), B * T, C, H * W, out.data_ptr(), stream_ptr()),
               'vs_frames_to_u8_nhwc')
     return out
+
+
+# ---- DEFLATE compression and CRC-32 on the device (csrc/vs_deflate.hip) -------------------------------------------------------------
+DEFLATE_CHUNK = 32768             # VS_DEFLATE_MAX_CHUNK: bytes per independent chunk (one wave each)
+DEFLATE_MIN_CHUNK = 1024          # VS_DEFLATE_MIN_CHUNK
+DEFLATE_SLOT_EXTRA = 10           # VS_DEFLATE_SLOT_EXTRA: worst case of a chunk beyond its own bytes
+DEFLATE_SLAB_BYTES = 256 << 20    # input bytes compressed per pass: slots + packed output stay below about 1 GiB whatever the array's size
+CRC_PIECE = 1 << 16               # bytes per wave of vs_crc32
+
+
+def _as_bytes(t, what):
+    require_cuda(t)
+    if not t.is_contiguous():
+        raise _lib.VarsepHipError('%s: a contiguous tensor is expected (got strides %s of shape %s)' % (what, tuple(t.stride()), tuple(t.shape)))
+    return t.reshape(-1).view(torch.uint8)
+
+
+def deflate_raw_slabs(t, chunk_bytes=None, slab_bytes=None):
+    """Iterator form of deflate_raw: yields (packed uint8 [bytes] on the device, n_chunks) for one slab of at most `slab_bytes` of input
+    after the other (default DEFLATE_SLAB_BYTES, rounded down to whole chunks), so that a writer can stream an array of any size to a file
+    with a bounded workspace.  The pieces concatenate by bytes.  An empty tensor yields nothing."""
+    data = _as_bytes(t, 'deflate_raw')
+    chunk = DEFLATE_CHUNK if chunk_bytes is None else int(chunk_bytes)
+    if chunk < DEFLATE_MIN_CHUNK or chunk > DEFLATE_CHUNK:
+        raise _lib.VarsepHipError('deflate_raw: chunk_bytes %d outside %d .. %d' % (chunk, DEFLATE_MIN_CHUNK, DEFLATE_CHUNK))
+    slab = max(chunk, (DEFLATE_SLAB_BYTES if slab_bytes is None else int(slab_bytes)) // chunk * chunk)
+    stride = (chunk + DEFLATE_SLOT_EXTRA + 15) // 16 * 16
+    n, device = data.numel(), data.device
+    if n == 0:
+        return
+    lib = _lib.load_library()
+    with torch.cuda.device(device):
+        for lo in range(0, n, slab):
+            part = data[lo:lo + slab]
+            n_chunks = -(-part.numel() // chunk)
+            slots = torch.empty((n_chunks, stride), dtype=torch.uint8, device=device)
+            sizes = torch.empty((n_chunks,), dtype=torch.int64, device=device)
+            e0 = _pb()
+            check(lib.vs_deflate_chunks(part.data_ptr(), part.numel(), chunk, slots.data_ptr(), stride, sizes.data_ptr(), stream_ptr()),
+                  'vs_deflate_chunks')
+            _pe(e0, 'vs_deflate_chunks', nbytes=float(part.numel()))
+            ends = torch.cumsum(sizes, 0)
+            offsets = ends - sizes
+            total = int(ends[-1].item())
+            packed = torch.empty((total,), dtype=torch.uint8, device=device)
+            e0 = _pb()
+            check(lib.vs_deflate_pack(slots.data_ptr(), stride, sizes.data_ptr(), offsets.data_ptr(), n_chunks, packed.data_ptr(), total,
+                                      stream_ptr()), 'vs_deflate_pack')
+            _pe(e0, 'vs_deflate_pack', nbytes=2.0 * total)
+            yield packed, n_chunks
+
+
+def deflate_raw(t, chunk_bytes=None, slab_bytes=None):
+    """`t` (any contiguous device tensor, taken as bytes) as a raw DEFLATE stream (RFC 1951) WITHOUT its final block: (packed uint8 [bytes]
+    on the device, n_chunks).  Every chunk of `chunk_bytes` (default DEFLATE_CHUNK) is compressed on its own by one wave (vs_deflate_chunks:
+    literals and distance-1 run matches, stored / fixed / dynamic by exact cost) and ends on a byte boundary with an empty stored block, so
+    `packed + b'\\x03\\x00'` is a complete stream that zlib inflates to t's bytes.  vs_deflate_pack gathers the chunks.  An empty tensor gives
+    (empty, 0).  For arrays above DEFLATE_SLAB_BYTES prefer deflate_raw_slabs, which bounds the workspace."""
+    pieces = list(deflate_raw_slabs(t, chunk_bytes, slab_bytes))
+    if not pieces:
+        return torch.empty((0,), dtype=torch.uint8, device=t.device), 0
+    if len(pieces) == 1:
+        return pieces[0]
+    return torch.cat([p for p, _ in pieces]), sum(n for _, n in pieces)
+
+
+def crc32(t, init=0):
+    """zlib.crc32(bytes of t, init) as a Python int, for a contiguous device tensor of any dtype: vs_crc32 leaves one partial per piece of
+    CRC_PIECE bytes (each already advanced past the bytes behind it), the host XORs the partials it reads back."""
+    import numpy as np
+    data = _as_bytes(t, 'crc32')
+    init = int(init) & 0xFFFFFFFF
+    n = data.numel()
+    if n == 0:
+        return init
+    pieces = -(-n // CRC_PIECE)
+    with torch.cuda.device(data.device):
+        partial = torch.empty((pieces,), dtype=torch.int32, device=data.device)
+        e0 = _pb()
+        check(_lib.load_library().vs_crc32(data.data_ptr(), n, CRC_PIECE, init, partial.data_ptr(), stream_ptr()), 'vs_crc32')
+        _pe(e0, 'vs_crc32', nbytes=float(n))
+    return int(np.bitwise_xor.reduce(partial.cpu().numpy().view(np.uint32))) ^ 0xFFFFFFFF

@@ -13,15 +13,24 @@ D/MNIST/raw, the files torchvision keeps; nothing is downloaded.  Writing the fi
 0.2 s, while np.savez_compressed (zlib over 2 GB on one host thread) takes 13.2 s of 13.4 s.  There is no CPU mode: --device is required.
 `--data_dir generated:D` of test/mnist/test.py and the script test/mnist/test_disentanglement_generated.py build the same set straight
 in HBM, without the file (`MovingMNIST.generated`).
+
+Who compresses the file: the environment variable VARSEP_NPZ_COMPRESS=host|device (`save_test_set(..., compress=)` in code; the keyword
+wins, then the variable, then the default `host`).  `host` is np.savez_compressed as above.  `device` keeps the four arrays in HBM
+(`generate_device`), compresses them there (ops.deflate_raw_slabs: csrc/vs_deflate.hip, run matching + dynamic Huffman codes per 32 KiB
+chunk; ops.crc32) and writes the compressed bytes into the same zip container (utils/npz.py); np.load and the reference's readers load
+either file to the same arrays.  Measurements: profiles/deflate_timing.md.
 """
 import argparse
 import os
 import time
+import zlib
 
 import numpy as np
 import torch
 
 from ... import ops
+from ..._lib import VarsepHipError
+from ...utils import npz
 from ...data.device import require_gpu
 from ...data.moving_mnist import draw_test_set, read_mnist_images, read_mnist_labels
 
@@ -61,6 +70,73 @@ def generate(data_dir, seq_len, seed, digits, frame_size, max_speed, device, tim
     return out
 
 
+def generate_device(data_dir, seq_len, seed, digits, frame_size, max_speed, device, timings=None):
+    """`generate` with the four arrays left on the device, in the file's dtypes and layouts: sequences uint8 [T, N, 1, F, F], latents int64
+    [T, N, digits, 4] (widened on the device), labels uint8 [N, digits], digits uint8 [N, digits, h, w] (both uploaded once).  timings:
+    as in `generate`, without 'download'."""
+    device = require_gpu('Moving-MNIST test', device)
+    t0 = time.perf_counter()
+    images, labels = read_test_digits(data_dir)
+    if digits < 1 or len(images) < digits:
+        raise ValueError('%d digits per video need at least as many test images (found %d)' % (digits, len(images)))
+    t1 = time.perf_counter()
+    digits_idx, init = draw_test_set(len(images), images.shape[1:], frame_size, max_speed, digits, seed)
+    t2 = time.perf_counter()
+    dev_images = torch.from_numpy(images).to(device)
+    frames, latents = ops.moving_mnist_testset(dev_images, init, seq_len, frame_size)
+    used = torch.from_numpy(np.ascontiguousarray(digits_idx[:init.shape[0] * digits]).astype(np.int64)).to(device)
+    out = dict(sequences=frames, latents=latents.to(torch.int64),
+               labels=torch.from_numpy(labels.astype(np.uint8)).to(device)[used].reshape(-1, digits).contiguous(),
+               digits=dev_images[used].reshape((-1, digits) + tuple(images.shape[1:])).contiguous())
+    if timings is not None:
+        torch.cuda.synchronize(device)
+        timings.update(read=t1 - t0, draw=t2 - t1, kernel=time.perf_counter() - t2)
+    return out
+
+
+COMPRESS_ENV = 'VARSEP_NPZ_COMPRESS'
+
+
+def npz_compressor(compress=None):
+    """'host' or 'device': who compresses the test file.  The keyword wins; None reads the environment variable VARSEP_NPZ_COMPRESS; when
+    that is unset or empty the host does (np.savez_compressed, the behaviour before the device encoder existed).  Any other value raises,
+    naming the two."""
+    source = 'compress'
+    if compress is None:
+        compress, source = os.environ.get('VARSEP_NPZ_COMPRESS', '') or 'host', COMPRESS_ENV
+    if compress not in ('host', 'device'):
+        raise ValueError("%s=%r: 'host' or 'device' expected" % (source, compress))
+    return compress
+
+
+def save_test_set(path, arrays, compress=None, timings=None):
+    """Writes the four arrays (host arrays or device tensors, `generate` / `generate_device`) to the .npz file `path`.  compress: 'host'
+    (tensors are downloaded; np.savez_compressed), 'device' (device tensors are compressed in HBM and only the compressed bytes are
+    downloaded: ops.deflate_raw_slabs, ops.crc32, utils/npz.write_npz) or None (`npz_compressor`).  timings: optional dict that receives
+    the seconds of 'download' + 'write' (host) or of 'write' (device: compression, download of the compressed bytes and file together)."""
+    compress = npz_compressor(compress)
+    t0 = time.perf_counter()
+    if compress == 'host':
+        host = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in arrays.items()}
+        t1 = time.perf_counter()
+        np.savez_compressed(path, **host)
+        if timings is not None:
+            timings.update(download=t1 - t0, write=time.perf_counter() - t1)
+        return
+    members = []
+    for name, t in arrays.items():
+        if not isinstance(t, torch.Tensor):
+            raise VarsepHipError("save_test_set: compress='device' takes device tensors (generate_device); %s is a %s"
+                                 % (name, type(t).__name__))
+        t = t.contiguous()
+        header = npz.npy_header(tuple(t.shape), npz.numpy_dtype(t.dtype))
+        members.append(npz.Member(name + '.npy', header, (piece.cpu().numpy() for piece, _ in ops.deflate_raw_slabs(t)),
+                                  ops.crc32(t, init=zlib.crc32(header)), t.numel() * t.element_size()))
+    npz.write_npz(path, members)
+    if timings is not None:
+        timings.update(write=time.perf_counter() - t0)
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog='Moving MNIST testing set generation.', formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                 description='Generates the Moving MNIST testing set on an MI355X. Videos and latent space (position, speed) '
@@ -81,12 +157,14 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.device is None:
         parser.error('the generation runs on an MI355X: pass --device N (there is no CPU mode)')
-    arrays = generate(args.data_dir, args.seq_len, args.seed, args.digits, args.frame_size, args.max_speed, torch.device('cuda', args.device))
+    compress = npz_compressor(None)
+    make = generate_device if compress == 'device' else generate
+    arrays = make(args.data_dir, args.seq_len, args.seed, args.digits, args.frame_size, args.max_speed, torch.device('cuda', args.device))
     fname = f'mmnist_test_{args.digits}digits_{args.frame_size}.npz'
     print(f'Saving testset at {os.path.join(args.data_dir, fname)}')
     if not os.path.isdir(args.data_dir):
         os.makedirs(args.data_dir)
-    np.savez_compressed(os.path.join(args.data_dir, fname), **arrays)
+    save_test_set(os.path.join(args.data_dir, fname), arrays, compress)
 
 
 if __name__ == '__main__':
