@@ -471,6 +471,24 @@ int vs_deflate_pack(const uint8_t* slots, int64_t slot_stride, const int64_t* si
  * a null pointer, n_bytes < 0, chunk_bytes outside 256 .. 2^24 or more pieces than a grid holds.                                         */
 int vs_crc32(const uint8_t* src, int64_t n_bytes, int64_t chunk_bytes, uint32_t init, uint32_t* partial, void* stream);
 
+/* NumPy's legacy random stream on the device (csrc/vs_mt19937.hip; the logic is csrc/vs_mt19937_core.h): np.random.RandomState is MT19937,
+ * and its scalar randint(low, high) is masked rejection on the 32-bit outputs.  The Moving-MNIST training loader draws its table of five
+ * integers per digit from a state that lives in HBM, in the order and with the values of the host loop it replaces.                     */
+#define VS_MT19937_STATE_WORDS 625    /* key[624], pos */
+#define VS_MT19937_MAX_COLS 8
+#define VS_MT19937_MAX_ROWS (1ll << 40)
+/* state uint32 [625] in HBM = key[624], pos (0 .. 624), advanced in place; lows / highs: HOST arrays of k columns, 1 <= k <= 8; out int32
+ * [n_rows, k]: out[r, j] is the (r * k + j)-th scalar randint(lows[j], highs[j]) of the stream, any int32 low < high (the widest, (-2^31,
+ * 2^31 - 1), included).  A column with high == low + 1 is filled with low and consumes nothing; if every column is such, the state is not
+ * touched.  pos after the call is one past the output that completed the last draw; a block is regenerated only when one of its outputs is
+ * needed.  One launch is ONE workgroup: a stream is one sequence, and launches on one HIP stream continue it in their order.  bad: optional
+ * int32 word on the device (may be NULL), left alone on success; the kernel sets it to 1 for a pos above 624 read from the state (out and
+ * the state are then untouched) and to 2 if it gave up after 64 outputs per draw plus 4096 (a state that is no stream; the state is not
+ * advanced).  n_rows == 0 launches nothing.  VS_ERR_ARG (and nothing launched) for a null state / lows / highs / out, k outside 1 .. 8,
+ * n_rows < 0 or above VS_MT19937_MAX_ROWS, or lows[j] >= highs[j].                                                                       */
+int vs_mt19937_randint(uint32_t* state, const int32_t* lows, const int32_t* highs, int k, int64_t n_rows, int32_t* out, int32_t* bad,
+                       void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

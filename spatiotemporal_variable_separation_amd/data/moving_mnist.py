@@ -19,6 +19,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, dtype_code, require_cuda, stream_ptr
+from .numpy_stream import DeviceRandomState
 
 
 def synthetic_digits(n=256, size=28, seed=1234):
@@ -105,7 +106,8 @@ class MovingMNIST:
     eps = 1e-8
     device_resident = True
     generated_on_device = True
-    rng = None                   # None: the global NumPy stream (the reference's); a np.random.RandomState: a private stream
+    rng = None                   # None: the global NumPy stream (the reference's); a np.random.RandomState: a private stream on the host;
+                                 # a DeviceRandomState (data/numpy_stream.py): a private stream in HBM, drawn from by one launch per batch
 
     def __init__(self, data, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device='cuda'):
         self.frame_size, self.nt_cond, self.seq_len = nx, nt_cond, seq_len
@@ -129,8 +131,14 @@ class MovingMNIST:
         return 200000 if self.train else int(self.data.shape[0])       # moving_mnist.py:104-111: arbitrary epoch length when training
 
     def draw(self, batch):
-        """The reference's draws for `batch` consecutive items from the global NumPy stream (moving_mnist.py:121-123, 156-160)."""
+        """The reference's draws for `batch` consecutive items from the global NumPy stream (moving_mnist.py:121-123, 156-160): int32
+        [batch, num_digits, 5], a host array -- or, when `rng` is a DeviceRandomState, a device tensor with the same values from ONE launch
+        (ops.mt19937_randint) and no upload or synchronisation."""
         h, w = self.digit_shape
+        if isinstance(self.rng, DeviceRandomState):
+            lows = (0, 0, 0, -self.max_speed, -self.max_speed)
+            highs = (self.n_source, self.frame_size - h + 1, self.frame_size - w + 1, self.max_speed + 1, self.max_speed + 1)
+            return self.rng.randint_table(lows, highs, batch * self.num_digits).view(batch, self.num_digits, 5)
         rnd = (self.rng or np.random).randint
         init = np.empty((batch, self.num_digits, 5), dtype=np.int32)
         for b in range(batch):

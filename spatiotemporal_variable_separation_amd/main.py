@@ -62,6 +62,39 @@ def load_dataset(args, device=None):
         'train() directly' % args.data)
 
 
+DRAWS_ENV = 'VARSEP_MMNIST_DRAWS'
+
+
+def mmnist_draws():
+    """'host' or 'device': who draws the Moving-MNIST training trajectories, read from the environment variable VARSEP_MMNIST_DRAWS.  Unset,
+    empty or 'host': the host loop over np.random.randint (the behaviour before the device stream existed).  Any other value raises,
+    naming the two."""
+    draws = os.environ.get('VARSEP_MMNIST_DRAWS', '') or 'host'
+    if draws not in ('host', 'device'):
+        raise ValueError("%s=%r: 'host' or 'device' expected" % (DRAWS_ENV, draws))
+    return draws
+
+
+def moving_mnist_loader(train_set, batch_size, seed, rank, world, device):
+    """The training loader of a dataset generated on the device (Moving MNIST) and the stream its videos are drawn from.
+
+    VARSEP_MMNIST_DRAWS unset, empty or 'host': at world size 1 the draws come from the global NumPy stream like the reference's; with
+    several ranks that stream is shared (it also draws t_random and must agree across replicas), so each rank gets a private
+    RandomState(seed + 7919 * (rank + 1)) for its videos.  'device': at EVERY world size the videos come from that private stream, kept in
+    HBM and drawn from by one launch per batch (data/numpy_stream.py) -- at world size 1 they are therefore no longer the global stream's
+    videos but those of `rng = RandomState(seed + 7919)` on the host route, and the global stream is left to t_random alone.  Each rank
+    generates 1/world of the epoch."""
+    from .data.moving_mnist import DeviceMovingLoader
+    draws = mmnist_draws()
+    if draws == 'device':
+        from .data.numpy_stream import DeviceRandomState
+        train_set.rng = DeviceRandomState(np.random.RandomState(seed + 7919 * (rank + 1)), device)
+    elif world > 1:
+        train_set.rng = np.random.RandomState(seed + 7919 * (rank + 1))
+    epoch_len = int(os.environ['VARSEP_MMNIST_EPOCH_LEN']) if os.environ.get('VARSEP_MMNIST_EPOCH_LEN') else None   # default 200000 (reference)
+    return DeviceMovingLoader(train_set, batch_size, world=world, epoch_len=epoch_len)
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     os.environ['OMP_NUM_THREADS'] = str(args.num_workers)
@@ -108,14 +141,8 @@ def main(argv=None):
         from torch.utils.data.distributed import DistributedSampler
         sampler = DistributedSampler(train_set, num_replicas=world, rank=rank, shuffle=True, seed=seed)
     if getattr(train_set, 'generated_on_device', False):
-        # Moving MNIST: every item is a fresh video, indices mean nothing -- no sampler.  The draws come from the global NumPy
-        # stream like the reference's; with several ranks that stream is shared (it also draws t_random and must agree across
-        # replicas), so each rank gets a private stream for its videos and 1/world of the epoch
-        from .data.moving_mnist import DeviceMovingLoader
-        if world > 1:
-            train_set.rng = np.random.RandomState(seed + 7919 * (rank + 1))
-        epoch_len = int(os.environ['VARSEP_MMNIST_EPOCH_LEN']) if os.environ.get('VARSEP_MMNIST_EPOCH_LEN') else None   # default 200000 (reference)
-        train_loader = DeviceMovingLoader(train_set, args.batch_size, world=world, epoch_len=epoch_len)
+        # Moving MNIST: every item is a fresh video, indices mean nothing -- no sampler; `moving_mnist_loader` says which stream draws them
+        train_loader = moving_mnist_loader(train_set, args.batch_size, seed, rank, world, device)
     elif getattr(train_set, 'device_resident', False):
         from .data.device import DeviceBatchLoader                 # same sampler stream as the DataLoader below, one gather launch per batch
         train_loader = DeviceBatchLoader(train_set, args.batch_size, shuffle=sampler is None, sampler=sampler)

@@ -2586,3 +2586,48 @@ def crc32(t, init=0):
         check(_lib.load_library().vs_crc32(data.data_ptr(), n, CRC_PIECE, init, partial.data_ptr(), stream_ptr()), 'vs_crc32')
         _pe(e0, 'vs_crc32', nbytes=float(n))
     return int(np.bitwise_xor.reduce(partial.cpu().numpy().view(np.uint32))) ^ 0xFFFFFFFF
+
+
+# ---- NumPy's legacy random stream on the device (csrc/vs_mt19937.hip) ----------------------------------------------------------------
+MT19937_STATE_WORDS = 625         # VS_MT19937_STATE_WORDS: key[624], pos
+MT19937_MAX_COLS = 8              # VS_MT19937_MAX_COLS
+MT19937_STATUS = {1: 'the state holds a pos above 624 (nothing was drawn, the state is untouched)',
+                  2: 'gave up after 64 outputs per draw: the state is not a stream (it was not advanced)'}
+
+
+def mt19937_randint(state, lows, highs, n_rows, out=None, validate=True):
+    """state: int32 [625] on the device, the words key[624], pos of np.random.RandomState's MT19937 state (the bit patterns of its uint32
+    values), advanced in place; lows / highs: k <= 8 host integers each -> int32 [n_rows, k] on the device: out[r, j] is the (r * k + j)-th
+    scalar `randint(lows[j], highs[j])` of the stream, bit for bit NumPy's (vs_mt19937_randint: one workgroup, launches on one stream
+    continue the sequence in their order).  validate=True reads back the launch's status word (a host sync) and raises VarsepHipError for a
+    pos above 624 in the state; validate=False keeps the call free of host syncs (the caller has checked the state it uploaded)."""
+    import ctypes
+    require_cuda(state, out)
+    lows, highs = [int(v) for v in lows], [int(v) for v in highs]
+    k, n_rows = len(lows), int(n_rows)
+    if state.dtype != torch.int32 or state.dim() != 1 or state.numel() != MT19937_STATE_WORDS or not state.is_contiguous():
+        raise _lib.VarsepHipError('mt19937_randint: state must be a contiguous int32 [%d] tensor (key[624], pos), got %s %s with strides %s'
+                                  % (MT19937_STATE_WORDS, state.dtype, tuple(state.shape), tuple(state.stride())))
+    if len(highs) != k or any(not -2 ** 31 <= v < 2 ** 31 for v in lows + highs):
+        raise _lib.VarsepHipError('mt19937_randint: lows and highs must be equally many int32 values (got %r and %r)' % (lows, highs))
+    if n_rows < 0:
+        raise _lib.VarsepHipError('mt19937_randint: n_rows %d is negative' % n_rows)
+    if out is None:
+        out = torch.empty((n_rows, k), dtype=torch.int32, device=state.device)
+    elif out.dtype != torch.int32 or out.numel() != n_rows * k or not out.is_contiguous() or out.device != state.device:
+        raise _lib.VarsepHipError('mt19937_randint: out must be a contiguous int32 tensor of %d x %d entries on %s' % (n_rows, k, state.device))
+    c_lows, c_highs = (ctypes.c_int32 * max(k, 1))(*lows), (ctypes.c_int32 * max(k, 1))(*highs)
+    if n_rows == 0:                                  # nothing to draw (an empty tensor has no address to hand over): only the columns are checked
+        check(_lib.load_library().vs_mt19937_randint(state.data_ptr(), c_lows, c_highs, k, 0, state.data_ptr(), None, None), 'vs_mt19937_randint')
+        return out
+    with torch.cuda.device(state.device):
+        bad = torch.zeros((1,), dtype=torch.int32, device=state.device) if validate else None
+        e0 = _pb()
+        check(_lib.load_library().vs_mt19937_randint(state.data_ptr(), c_lows, c_highs, k, n_rows, _ptr(out), _ptr(bad), stream_ptr()),
+              'vs_mt19937_randint')
+        _pe(e0, 'vs_mt19937_randint', nbytes=float(out.numel() * 4 + 2 * 4 * MT19937_STATE_WORDS))
+    if validate:
+        status = int(bad.item())
+        if status:
+            raise _lib.VarsepHipError('mt19937_randint: %s' % MT19937_STATUS.get(status, 'status %d' % status))
+    return out
