@@ -489,6 +489,28 @@ int vs_crc32(const uint8_t* src, int64_t n_bytes, int64_t chunk_bytes, uint32_t 
 int vs_mt19937_randint(uint32_t* state, const int32_t* lows, const int32_t* highs, int k, int64_t n_rows, int32_t* out, int32_t* bad,
                        void* stream);
 
+/* The STOCHASTIC Moving-MNIST trajectories on the device (csrc/vs_mmnist_walk.hip; the logic is csrc/vs_mmnist_walk_core.h): the reference's
+ * sampler with deterministic=False redraws the speed vector from the NumPy stream at every bounce (data/moving_mnist.py:232-234), so the
+ * outputs a trajectory takes depend on the trajectory.  One launch (ONE workgroup) walks n_traj trajectories from the state in HBM, one
+ * after the other in the stream's order, bit for bit the reference's values: per trajectory n_pre scalar draws randint(lows[j], highs[j])
+ * (HOST arrays; training: digit index, start row, start column, row speed, column speed; n_pre == 4: the last four alone), then seq_len
+ * steps of collision pass (speeds redrawn in [-max_speed, max_speed]), record, move.  With n_pre < 4 the start state of trajectory i is
+ * start[i] = (row, column, row speed, column speed) of a device table int32 [n_traj, 4] and the prefix is only drawn and recorded.
+ * x_max / y_max: frame - digit height / width.  Outputs (device): pre int32 [n_traj, n_pre]; positions int32 [seq_len, n_traj, 2], which
+ * vs_moving_mnist_place reads as [T, n_seq, nd, 2]; latents int32 [seq_len, n_traj, 4] = (row, column, row speed, column speed), optional;
+ * desc int32 [n_traj / desc_nd, 1 + desc_nd] = (video index, the digit indices pre[.., 0] of its trajectories), optional, n_pre == 5 only.
+ * state as for vs_mt19937_randint: advanced past the last output consumed, a block regenerated only when an output of it is needed.
+ * bad: optional device word, left alone on success; 1: pos above 624 (nothing written); 2: a draw rejected 4096 outputs in a row; 3: a
+ * collision pass count above 64 -- for 2 and 3 the outputs are partly written; on every one the state is not advanced.  n_traj == 0
+ * launches nothing.  VS_ERR_ARG (and nothing launched) for a null state / positions / needed table, n_pre outside 0 .. 5, seq_len < 1,
+ * n_traj < 0 or above VS_MMNIST_WALK_MAX_TRAJ, x_max or y_max < 1, max_speed < 0, lows[j] >= highs[j], or a desc without its conditions. */
+#define VS_MMNIST_WALK_MAX_PRE 5
+#define VS_MMNIST_WALK_MAX_TRAJ (1ll << 24)
+#define VS_MMNIST_WALK_STATUS_BOUNCE 3
+int vs_mmnist_stochastic_trajectories(uint32_t* state, const int32_t* lows, const int32_t* highs, int n_pre, int64_t n_traj, int seq_len,
+                                      int x_max, int y_max, int max_speed, const int32_t* start, int32_t* pre, int32_t* positions,
+                                      int32_t* latents, int32_t* desc, int desc_nd, int32_t* bad, void* stream);
+
 /* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's

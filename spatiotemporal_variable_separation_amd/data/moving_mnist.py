@@ -9,7 +9,11 @@ batch into HBM.  A 4-worker host generator tops out far below the > 100 k frames
 
 Digits come from the raw MNIST idx files under `data_dir` (the files torchvision downloads: `MNIST/raw/train-images-idx3-ubyte[.gz]`;
 torchvision itself is not needed), or -- `data_dir='synthetic_digits'` -- from seeded 28x28 blobs for benchmarks and tests.
-Only the deterministic variant (the one main.py constructs) is generated on the device.
+Both variants are generated on the device.  The deterministic one (the one main.py constructs by default) as above.  The stochastic one
+(`deterministic=False`, `main --mnist_stochastic`) redraws the speed vector from the stream at every bounce (`moving_mnist.py:232-234`), so
+the outputs a trajectory takes depend on the trajectory: with a `DeviceRandomState` ONE launch (`vs_mmnist_stochastic_trajectories`) draws and
+walks the whole batch from the stream in HBM and `vs_moving_mnist_place` renders it; otherwise `draw_stochastic` makes the same draws from
+the host stream in a Python loop.  A stochastic test file (`smmnist_test_*.npz`) is not generated here.
 """
 import gzip
 import os
@@ -91,6 +95,45 @@ def draw_test_set(n_images, digit_shape, frame_size, max_speed, num_digits, seed
     return digits_idx, init
 
 
+_EPS = 1e-8
+
+
+def _stochastic_collision(rnd, sx, sy, dx, dy, x_max, y_max, max_speed):
+    """`_process_collision` of the reference with deterministic=False (moving_mnist.py:172-253) in Python floats: while the digit is outside
+    [0, x_max] x [0, y_max], find where it left, redraw the speed vector, mirror it off the edges that were hit and spend the rest of the step."""
+    left, upper, right, bottom = sx < -_EPS, sy < -_EPS, sx > x_max + _EPS, sy > y_max + _EPS
+    cx = cy = 0
+    while left or right or upper or bottom:
+        if dx == 0:
+            cx, cy = sx, (0 if upper else y_max)
+        elif dy == 0:
+            cx, cy = (0 if left else x_max), sy
+        else:
+            a = dy / dx
+            b = sy - a * sx
+            for edge, lim in ((0, 0), (1, x_max)):                    # left, right: where the line meets the row lim
+                if (left, right)[edge]:
+                    y = a * lim + b
+                    hit = -_EPS <= y <= y_max + _EPS
+                    left, right = (hit, right) if edge == 0 else (left, hit)
+                    if hit:
+                        cx, cy = lim, y
+            for edge, lim in ((0, 0), (1, y_max)):                    # upper, bottom: where it meets the column lim
+                if (upper, bottom)[edge]:
+                    x = (lim - b) / a
+                    hit = -_EPS <= x <= x_max + _EPS
+                    upper, bottom = (hit, bottom) if edge == 0 else (upper, hit)
+                    if hit:
+                        cx, cy = x, lim
+        p = (sx - cx) / dx if dx != 0 else (sy - cy) / dy
+        dx, dy = rnd(-max_speed, max_speed + 1), rnd(-max_speed, max_speed + 1)     # dx first
+        dx = abs(dx) if left else -abs(dx) if right else dx
+        dy = abs(dy) if upper else -abs(dy) if bottom else dy
+        sx, sy = cx + dx * p, cy + dy * p
+        left, upper, right, bottom = sx < -_EPS, sy < -_EPS, sx > x_max + _EPS, sy > y_max + _EPS
+    return sx, sy, dx, dy
+
+
 _GENERATED = {}                  # the test sets generated in this process: one launch per (files, geometry, seed, device)
 
 
@@ -114,14 +157,14 @@ class MovingMNIST:
         self.max_speed, self.deterministic, self.num_digits, self.train = max_speed, deterministic, num_digits, train
         self.device = torch.device(device)
         if train:
-            if not deterministic:
-                raise NotImplementedError('stochastic Moving MNIST redraws speeds inside the bounce loop (data-dependent RNG use); only the '
-                                          'deterministic variant -- the one main.py trains on -- is generated on the device')
             arr = np.ascontiguousarray(np.stack([np.asarray(d, dtype=np.uint8) for d in data]) if not isinstance(data, np.ndarray) else data)
             assert arr.dtype == np.uint8 and arr.ndim == 3, 'digits: uint8 [N, h, w]'
             self.digit_shape = (int(arr.shape[1]), int(arr.shape[2]))
             self.n_source = int(arr.shape[0])
             self.data = torch.from_numpy(arr).to(self.device)
+            if not deterministic and min(nx - self.digit_shape[0], nx - self.digit_shape[1]) < 1:
+                raise ValueError('stochastic Moving MNIST: a %d x %d digit fills the %d x %d frame along an axis (unsupported)'
+                                 % (self.digit_shape + (nx, nx)))
         elif isinstance(data, torch.Tensor):                     # `generated`: fp32 [N, T, 1, nx, nx], already in HBM
             self.data = data
         else:
@@ -163,9 +206,49 @@ class MovingMNIST:
               'vs_moving_mnist_batch')
         return out
 
+    def draw_stochastic(self, batch):
+        """The stochastic variant's draws AND walks for `batch` consecutive items (moving_mnist.py:119-123, 153-170, 230-234): (desc int32
+        [batch, 1 + num_digits] = (item, its digits' indices), positions int32 [seq_len, batch, num_digits, 2] = (row, column) per frame),
+        the operands of ops.moving_mnist_place.  When `rng` is a DeviceRandomState both are device tensors from ONE launch
+        (ops.mmnist_stochastic_trajectories) with no upload or synchronisation; otherwise host arrays from a Python loop over the host
+        stream, the same draws in the same order."""
+        h, w = self.digit_shape
+        x_max, y_max, s, nd = self.frame_size - h, self.frame_size - w, self.max_speed, self.num_digits
+        if isinstance(self.rng, DeviceRandomState):
+            _, positions, _, desc = self.rng.stochastic_trajectories(batch * nd, self.seq_len, (0, 0, 0, -s, -s),
+                                                                     (self.n_source, x_max + 1, y_max + 1, s + 1, s + 1), x_max, y_max, s, desc_nd=nd)
+            return desc, positions.view(self.seq_len, batch, nd, 2)
+        rnd = (self.rng or np.random).randint
+        desc = np.empty((batch, 1 + nd), dtype=np.int32)
+        positions = np.empty((self.seq_len, batch, nd, 2), dtype=np.int32)
+        for b in range(batch):
+            desc[b, 0] = b
+            for n in range(nd):
+                desc[b, 1 + n] = rnd(self.n_source)
+                sx, sy = rnd(0, x_max + 1), rnd(0, y_max + 1)
+                dx, dy = rnd(-s, s + 1), rnd(-s, s + 1)
+                for t in range(self.seq_len):
+                    sx, sy, dx, dy = _stochastic_collision(rnd, sx, sy, dx, dy, x_max, y_max, s)
+                    positions[t, b, n] = (int(round(sx)), int(round(sy)))
+                    sy += dy
+                    sx += dx
+        return desc, positions
+
+    def render_stochastic(self, desc, positions, out_dtype=torch.float32):
+        """(desc, positions) of `draw_stochastic` (host arrays or device tensors) -> videos [B, seq_len, 1, nx, nx] on the device: the digits
+        summed at their positions, min(., 255), / 255 (ops.moving_mnist_place, the arithmetic of the deterministic renderer)."""
+        from .. import ops
+        if not isinstance(desc, torch.Tensor):
+            desc = torch.from_numpy(desc).to(self.device, non_blocking=True)
+            positions = torch.from_numpy(positions).to(self.device, non_blocking=True)
+        return ops.moving_mnist_place(self.data, positions, desc, self.seq_len, self.frame_size, out_dtype, validate=False)
+
     def batch(self, batch, out_dtype=torch.float32):
         """(cond, target) of `batch` fresh videos (training) -- `__getitem__` of the reference for a whole batch."""
-        x = self.render(self.draw(batch), out_dtype)
+        if self.deterministic:
+            x = self.render(self.draw(batch), out_dtype)
+        else:
+            x = self.render_stochastic(*self.draw_stochastic(batch), out_dtype)
         return x[:, :self.nt_cond], x[:, self.nt_cond:]
 
     def __getitem__(self, index):

@@ -35,6 +35,11 @@ class DeviceRandomState:
         launch; nothing is read back (the state was checked when it was uploaded)."""
         return ops.mt19937_randint(self.state, lows, highs, n_rows, validate=False)
 
+    def stochastic_trajectories(self, n_traj, seq_len, lows, highs, x_max, y_max, max_speed, **kwargs):
+        """(pre, positions, latents, desc) of `n_traj` stochastic Moving-MNIST trajectories drawn from the stream (ops.mmnist_stochastic_
+        trajectories, which documents the operands).  One launch; nothing is read back."""
+        return ops.mmnist_stochastic_trajectories(self.state, n_traj, seq_len, lows, highs, x_max, y_max, max_speed, validate=False, **kwargs)
+
     def get_state(self):
         """NumPy's state tuple ('MT19937', key, pos, has_gauss, cached_gaussian) of the stream as it stands after the launches enqueued
         so far (a download: it waits for them).  The stream itself stays where it is."""

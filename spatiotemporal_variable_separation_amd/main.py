@@ -43,8 +43,8 @@ def load_dataset(args, device=None):
                              device=device)
     if args.data == 'mnist' and on_gpu:
         from .data.moving_mnist import MovingMNIST                  # sequences generated on the device (data/moving_mnist.py)
-        return MovingMNIST.make_dataset(args.data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, True,
-                                        device=device, seed=args.seed)
+        return MovingMNIST.make_dataset(args.data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4,
+                                        not getattr(args, 'mnist_stochastic', False), args.n_object, True, device=device, seed=args.seed)
     if args.data == 'chairs' and on_gpu:
         from .data.chairs import Chairs                             # main.py:77-79 of the reference; views resident in HBM
         if getattr(args, 'chairs_raw', False):                      # the original renders, prepared on the device (csrc/vs_resample.hip)

@@ -2631,3 +2631,71 @@ def mt19937_randint(state, lows, highs, n_rows, out=None, validate=True):
         if status:
             raise _lib.VarsepHipError('mt19937_randint: %s' % MT19937_STATUS.get(status, 'status %d' % status))
     return out
+
+
+# ---- the stochastic Moving-MNIST trajectories on the device (csrc/vs_mmnist_walk.hip) ---------------------------------------------------
+MMNIST_WALK_MAX_PRE = 5           # VS_MMNIST_WALK_MAX_PRE
+MMNIST_WALK_STATUS = {1: MT19937_STATUS[1],
+                      2: 'a draw rejected 4096 outputs in a row: the state is not a stream (it was not advanced)',
+                      3: 'a collision took more than 64 passes (the state was not advanced)'}
+
+
+def mmnist_stochastic_trajectories(state, n_traj, seq_len, lows, highs, x_max, y_max, max_speed, *, start=None, latents=False, desc_nd=None,
+                                   validate=True):
+    """`n_traj` trajectories of the reference's stochastic Moving-MNIST sampler (speeds redrawn at every bounce) from the NumPy stream in
+    `state` (int32 [625] on the device, as for mt19937_randint; advanced in place), bit for bit the reference's: per trajectory the
+    len(lows) <= 5 prefix draws randint(lows[j], highs[j]) (training: digit index, start row, start column, row speed, column speed; four:
+    without the digit index), then `seq_len` steps inside 0 .. x_max rows, 0 .. y_max columns (frame - digit height / width, both >= 1)
+    with speeds in [-max_speed, max_speed].  With fewer than four prefix draws `start` int32 [n_traj, 4] on the device gives the start
+    states.  -> (pre int32 [n_traj, n_pre], positions int32 [seq_len, n_traj, 2], latents int32 [seq_len, n_traj, 4] or None, desc int32
+    [n_traj / desc_nd, 1 + desc_nd] or None): `positions.view(seq_len, -1, desc_nd, 2)` and `desc` are what moving_mnist_place reads.
+    One launch of one workgroup (vs_mmnist_stochastic_trajectories); launches on one stream continue the sequence in their order.
+    validate=True reads back the launch's status word (a host sync) and raises VarsepHipError; validate=False keeps the call free of host
+    syncs."""
+    import ctypes
+    require_cuda(state, start)
+    lows, highs = [int(v) for v in lows], [int(v) for v in highs]
+    n_pre, n_traj, seq_len, x_max, y_max, max_speed = len(lows), int(n_traj), int(seq_len), int(x_max), int(y_max), int(max_speed)
+    if state.dtype != torch.int32 or state.dim() != 1 or state.numel() != MT19937_STATE_WORDS or not state.is_contiguous():
+        raise _lib.VarsepHipError('mmnist_stochastic_trajectories: state must be a contiguous int32 [%d] tensor (key[624], pos), got %s %s with '
+                                  'strides %s' % (MT19937_STATE_WORDS, state.dtype, tuple(state.shape), tuple(state.stride())))
+    if len(highs) != n_pre or n_pre > MMNIST_WALK_MAX_PRE or any(not -2 ** 31 <= v < 2 ** 31 for v in lows + highs):
+        raise _lib.VarsepHipError('mmnist_stochastic_trajectories: lows and highs must be equally many, at most %d, int32 values (got %r and %r)'
+                                  % (MMNIST_WALK_MAX_PRE, lows, highs))
+    if n_traj < 0 or seq_len < 1:
+        raise _lib.VarsepHipError('mmnist_stochastic_trajectories: n_traj %d must not be negative and seq_len %d must be positive' % (n_traj, seq_len))
+    if x_max < 1 or y_max < 1 or max_speed < 0:
+        raise _lib.VarsepHipError('mmnist_stochastic_trajectories: x_max %d and y_max %d must be >= 1 (a digit that fills the frame along an '
+                                  'axis is unsupported) and max_speed %d >= 0' % (x_max, y_max, max_speed))
+    if n_pre < 4 and (start is None or start.dtype != torch.int32 or tuple(start.shape) != (n_traj, 4) or not start.is_contiguous()
+                      or start.device != state.device):
+        raise _lib.VarsepHipError('mmnist_stochastic_trajectories: with %d prefix draws, start must be a contiguous int32 [%d, 4] tensor on %s'
+                                  % (n_pre, n_traj, state.device))
+    if desc_nd is not None and (n_pre != 5 or not 1 <= int(desc_nd) <= 8 or n_traj % int(desc_nd)):
+        raise _lib.VarsepHipError('mmnist_stochastic_trajectories: desc needs five prefix draws and 1 .. 8 digits per video that divide n_traj '
+                                  '(got %d draws, desc_nd %r, n_traj %d)' % (n_pre, desc_nd, n_traj))
+    nd = int(desc_nd) if desc_nd is not None else 0
+    dev = state.device
+    pre = torch.empty((n_traj, n_pre), dtype=torch.int32, device=dev)
+    positions = torch.empty((seq_len, n_traj, 2), dtype=torch.int32, device=dev)
+    lat = torch.empty((seq_len, n_traj, 4), dtype=torch.int32, device=dev) if latents else None
+    desc = torch.empty((n_traj // nd, 1 + nd), dtype=torch.int32, device=dev) if nd else None
+    c_lows, c_highs = (ctypes.c_int32 * 5)(*lows), (ctypes.c_int32 * 5)(*highs)
+    fn = _lib.load_library().vs_mmnist_stochastic_trajectories
+    if n_traj == 0:                                  # nothing to walk (an empty tensor has no address to hand over): only the arguments are checked
+        p = state.data_ptr()
+        check(fn(p, c_lows, c_highs, n_pre, 0, seq_len, x_max, y_max, max_speed, p, p, p, None, None, 0, None, None),
+              'vs_mmnist_stochastic_trajectories')
+        return pre, positions, lat, desc
+    with torch.cuda.device(dev):
+        bad = torch.zeros((1,), dtype=torch.int32, device=dev) if validate else None
+        e0 = _pb()
+        check(fn(state.data_ptr(), c_lows, c_highs, n_pre, n_traj, seq_len, x_max, y_max, max_speed, _ptr(start) if n_pre < 4 else None,
+                 _ptr(pre) if n_pre else None, _ptr(positions), _ptr(lat), _ptr(desc), nd, _ptr(bad), stream_ptr()),
+              'vs_mmnist_stochastic_trajectories')
+        _pe(e0, 'vs_mmnist_stochastic_trajectories', nbytes=float(4 * (pre.numel() + positions.numel()) + 2 * 4 * MT19937_STATE_WORDS))
+    if validate:
+        status = int(bad.item())
+        if status:
+            raise _lib.VarsepHipError('mmnist_stochastic_trajectories: %s' % MMNIST_WALK_STATUS.get(status, 'status %d' % status))
+    return pre, positions, lat, desc

@@ -111,6 +111,8 @@ def _build():
       help='Number of random pixels to select for partial WaveEq (WaveEq-100).')
     A('--zones', type=int, metavar='ZONES', default=list(range(1, 30)), nargs='+', help='SST zones to train on.')
     A('--n_object', type=int, metavar='NUMBER', default=2, help='Number of digits in the Moving MNIST data.')
+    A('--mnist_stochastic', action='store_true',
+      help='Train on the stochastic Moving MNIST variant (the speed vector is redrawn at every bounce); the default is the deterministic one.')
 
     g = p.add_argument_group(title='MI355X', description='Additive options of the MI355X-native path.')
     g.add_argument('--precision', type=str, default=None, choices=['fp32', 'bf16', 'fp16'],
