@@ -359,6 +359,22 @@ int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_total, int d
                             int num_digits, int seq_len, int frame_size, void* frames, int frames_fp32, int64_t frame_stride_t,
                             int64_t frame_stride_v, int32_t* latents, void* stream);
 
+/* The same RAW test-set frames from STORED positions instead of walked trajectories: the renderer of the STOCHASTIC test set
+ * (smmnist_test_*.npz), whose trajectories vs_mmnist_stochastic_trajectories walks first because they consume the random stream as they go.
+ * digits as above; positions [seq_len, n_videos, num_digits, 2] int32 = (row, column) of each digit's top-left corner per frame (the walk
+ * kernel's `positions` [seq_len, n_traj, 2] viewed per video); digit_idx [n_videos, num_digits] int32.  frames, frames_fp32 and the two
+ * strides exactly as for vs_moving_mnist_testset: raw min(sum of the digits, 255), uint8 or fp32, time- or video-major.  Same launch
+ * shape (one workgroup per video, or per (video, chunk of >= 8 frames) below 512 videos; the slice of the position table and the digit
+ * images in LDS) and the same compositing code and store widths as vs_moving_mnist_testset.  A digit index outside [0, n_digits_total)
+ * (that digit in no frame), or a digit not wholly inside the frame at some frame (that digit in that frame), is not drawn and sets
+ * *bad = 1 (bad: optional int32 word on the device, may be NULL, left alone otherwise); the launch never reads or writes out of bounds.
+ * VS_ERR_ARG (nothing launched) for a null digits / positions / digit_idx / frames, a non-positive size, num_digits outside 1..8, a digit
+ * larger than the frame, or strides under which frames overlap; VS_ERR_UNSUPPORTED when the position table of a workgroup and the digit
+ * images exceed 64 KiB of LDS (the message names the sizes).                                                                          */
+int vs_moving_mnist_testset_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions,
+                                  const int32_t* digit_idx, int n_videos, int num_digits, int seq_len, int frame_size, void* frames,
+                                  int frames_fp32, int64_t frame_stride_t, int64_t frame_stride_v, int32_t* bad, void* stream);
+
 /* One batch of 3D Chairs sequences gathered from the decoded views resident in HBM (reference: data/chairs.py:45-64 `get_sequence` +
  * `__getitem__`, for a whole batch of items).  frames [n_objects, views_per_object, H, W, C] uint8, HWC as `np.array(Image.open(f))`
  * yields; desc [rows, 2] int32 = (object, first view); out [rows, seq_len, C, H, W] (fp32 or a 16-bit type).  Frame t of a row is view

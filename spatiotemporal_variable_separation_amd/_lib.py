@@ -144,6 +144,7 @@ SIGNATURES = {
     'vs_bn_stats_from_sums': (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp]),
     'vs_moving_mnist_batch': (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     'vs_moving_mnist_testset': (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _vp]),
+    'vs_moving_mnist_testset_place': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _vp]),
     'vs_chairs_gather': (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     'vs_gather_timeline': (_i32, [_vp, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     'vs_gather_windows': (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),

@@ -1,5 +1,6 @@
 // vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253) and the
-// Moving-MNIST test set in one launch (reference: preprocessing/mnist/make_test_set.py; below the training generator), the 3D
+// Moving-MNIST test set in one launch (reference: preprocessing/mnist/make_test_set.py; below the training generator; walked in the launch,
+// or -- the stochastic set -- rendered from positions that vs_mmnist_walk.hip walked), the 3D
 // Chairs batch gather (reference: data/chairs.py:45-64) and the table-driven window gather of the TaxiBJ timeline (reference:
 // data/taxibj.py:74-100), both at the end of this file.
 //
@@ -119,40 +120,12 @@ __device__ __forceinline__ unsigned mm_pixel(const int2* pos, const unsigned cha
     return v > 255u ? 255u : v;
 }
 
+// Step 3 for one workgroup: frames t0 .. t0 + len - 1 of video v from the positions and digit images in LDS.  Shared by the walking kernel
+// and the placing kernel below, which differ only in where the positions come from.
 template <bool FP32, bool VEC>
-__global__ __launch_bounds__(256) void moving_mnist_testset_kernel(const unsigned char* __restrict__ digits, int64_t n_total, int dh, int dw,
-                                                                   const int* __restrict__ init, int n_videos, int nd, int T, int F, int chunks,
-                                                                   int chunk_len, void* frames, int64_t st, int64_t sv, int* latents) {
-    extern __shared__ int2 mm_lds[];
-    const int v = blockIdx.x / chunks, t0 = (blockIdx.x - v * chunks) * chunk_len;
-    const int len = T - t0 < chunk_len ? T - t0 : chunk_len;
-    int2* pos = mm_lds;
-    unsigned char* dig = reinterpret_cast<unsigned char*>(mm_lds + (size_t)chunk_len * nd);
-    const int tid = threadIdx.x, dsz = dh * dw;
-    if (tid < nd) {
-        const int* q = init + ((int64_t)v * nd + tid) * 5;
-        Traj s{(double)q[1], (double)q[2], q[3], q[4]};
-        const double x_max = (double)(F - dh), y_max = (double)(F - dw);
-        for (int tt = 0; tt < t0 + len; ++tt) {      // moving_mnist.py:166-175: bounce, record the rounded position and the speed, then move
-            process_collision(s, 0.0, x_max, 0.0, y_max);
-            if (tt >= t0) {
-                const int px = (int)rint(s.sx), py = (int)rint(s.sy);
-                pos[(tt - t0) * nd + tid] = make_int2(px, py);
-                if (latents) {
-                    int* l = latents + (((int64_t)tt * n_videos + v) * nd + tid) * 4;
-                    l[0] = px; l[1] = py; l[2] = s.dx; l[3] = s.dy;
-                }
-            }
-            s.sy += (double)s.dy;
-            s.sx += (double)s.dx;
-        }
-    }
-    for (int i = tid; i < nd * dsz; i += 256) {
-        const int d = i / dsz;
-        const int64_t idx = init[((int64_t)v * nd + d) * 5];
-        dig[i] = (idx >= 0 && idx < n_total) ? digits[idx * dsz + (i - d * dsz)] : (unsigned char)0;
-    }
-    __syncthreads();
+__device__ __forceinline__ void mm_compose(const int2* pos, const unsigned char* dig, int nd, int dh, int dw, int F, int len, int t0, int v,
+                                           void* frames, int64_t st, int64_t sv) {
+    const int tid = threadIdx.x;
     const int FF = F * F;
     if constexpr (VEC) {
         constexpr int G = FP32 ? 4 : 16;
@@ -203,6 +176,78 @@ __global__ __launch_bounds__(256) void moving_mnist_testset_kernel(const unsigne
             else ((unsigned char*)frames)[o] = (unsigned char)val;
         }
     }
+}
+
+template <bool FP32, bool VEC>
+__global__ __launch_bounds__(256) void moving_mnist_testset_kernel(const unsigned char* __restrict__ digits, int64_t n_total, int dh, int dw,
+                                                                   const int* __restrict__ init, int n_videos, int nd, int T, int F, int chunks,
+                                                                   int chunk_len, void* frames, int64_t st, int64_t sv, int* latents) {
+    extern __shared__ int2 mm_lds[];
+    const int v = blockIdx.x / chunks, t0 = (blockIdx.x - v * chunks) * chunk_len;
+    const int len = T - t0 < chunk_len ? T - t0 : chunk_len;
+    int2* pos = mm_lds;
+    unsigned char* dig = reinterpret_cast<unsigned char*>(mm_lds + (size_t)chunk_len * nd);
+    const int tid = threadIdx.x, dsz = dh * dw;
+    if (tid < nd) {
+        const int* q = init + ((int64_t)v * nd + tid) * 5;
+        Traj s{(double)q[1], (double)q[2], q[3], q[4]};
+        const double x_max = (double)(F - dh), y_max = (double)(F - dw);
+        for (int tt = 0; tt < t0 + len; ++tt) {      // moving_mnist.py:166-175: bounce, record the rounded position and the speed, then move
+            process_collision(s, 0.0, x_max, 0.0, y_max);
+            if (tt >= t0) {
+                const int px = (int)rint(s.sx), py = (int)rint(s.sy);
+                pos[(tt - t0) * nd + tid] = make_int2(px, py);
+                if (latents) {
+                    int* l = latents + (((int64_t)tt * n_videos + v) * nd + tid) * 4;
+                    l[0] = px; l[1] = py; l[2] = s.dx; l[3] = s.dy;
+                }
+            }
+            s.sy += (double)s.dy;
+            s.sx += (double)s.dx;
+        }
+    }
+    for (int i = tid; i < nd * dsz; i += 256) {
+        const int d = i / dsz;
+        const int64_t idx = init[((int64_t)v * nd + d) * 5];
+        dig[i] = (idx >= 0 && idx < n_total) ? digits[idx * dsz + (i - d * dsz)] : (unsigned char)0;
+    }
+    __syncthreads();
+    mm_compose<FP32, VEC>(pos, dig, nd, dh, dw, F, len, t0, v, frames, st, sv);
+}
+
+// The same frames from STORED positions (the stochastic test set: its trajectories consume the random stream as they go, so one workgroup
+// walks them all first, vs_mmnist_walk.hip).  Step 1 becomes a copy: the workgroup's slice of positions [T][n_videos][nd][2] goes to LDS.
+// A digit whose index is outside [0, n_total), or which is not wholly inside the frame at a frame of the slice, raises *bad and gets a
+// position that no pixel of any frame meets, so it is not drawn there; nothing is read outside `digits` or `positions`.
+constexpr int MM_AWAY = 1 << 24;    // r - MM_AWAY < 0 for every row of a frame that passed the entry point's size checks
+
+template <bool FP32, bool VEC>
+__global__ __launch_bounds__(256) void moving_mnist_testset_place_kernel(const unsigned char* __restrict__ digits, int64_t n_total, int dh, int dw,
+                                                                         const int* __restrict__ positions, const int* __restrict__ digit_idx,
+                                                                         int n_videos, int nd, int T, int F, int chunks, int chunk_len, void* frames,
+                                                                         int64_t st, int64_t sv, int* bad) {
+    extern __shared__ int2 mm_lds[];
+    const int v = blockIdx.x / chunks, t0 = (blockIdx.x - v * chunks) * chunk_len;
+    const int len = T - t0 < chunk_len ? T - t0 : chunk_len;
+    int2* pos = mm_lds;
+    unsigned char* dig = reinterpret_cast<unsigned char*>(mm_lds + (size_t)chunk_len * nd);
+    const int tid = threadIdx.x, dsz = dh * dw;
+    for (int i = tid; i < len * nd; i += 256) {
+        const int f = i / nd, d = i - f * nd;
+        const int* q = positions + (((int64_t)(t0 + f) * n_videos + v) * nd + d) * 2;
+        const int px = q[0], py = q[1];
+        const int64_t idx = digit_idx[(int64_t)v * nd + d];
+        const bool ok = idx >= 0 && idx < n_total && px >= 0 && py >= 0 && px <= F - dh && py <= F - dw;
+        if (!ok && bad) *bad = 1;
+        pos[i] = ok ? make_int2(px, py) : make_int2(MM_AWAY, MM_AWAY);
+    }
+    for (int i = tid; i < nd * dsz; i += 256) {
+        const int d = i / dsz;
+        const int64_t idx = digit_idx[(int64_t)v * nd + d];
+        dig[i] = (idx >= 0 && idx < n_total) ? digits[idx * dsz + (i - d * dsz)] : (unsigned char)0;
+    }
+    __syncthreads();
+    mm_compose<FP32, VEC>(pos, dig, nd, dh, dw, F, len, t0, v, frames, st, sv);
 }
 
 // ---- 3D Chairs: batch gather from the decoded views resident in HBM (data/chairs.py:45-64) ----------------------------------------
@@ -366,23 +411,25 @@ extern "C" int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_tot
     return VS_OK;
 }
 
-extern "C" int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int n_videos,
-                                       int num_digits, int seq_len, int frame_size, void* frames, int frames_fp32, int64_t frame_stride_t,
-                                       int64_t frame_stride_v, int32_t* latents, void* stream) {
-    VS_CHECK_ARG(digits && init && frames, "vs_moving_mnist_testset: null pointer");
-    VS_CHECK_ARG(n_digits_total > 0 && digit_h > 0 && digit_w > 0 && n_videos > 0 && seq_len > 0, "vs_moving_mnist_testset: sizes must be positive");
-    VS_CHECK_ARG(num_digits >= 1 && num_digits <= MM_MAXD, "vs_moving_mnist_testset: 1..%d digits per video (got %d)", MM_MAXD, num_digits);
-    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "vs_moving_mnist_testset: a %d x %d digit does not fit a frame of %d", digit_h,
-                 digit_w, frame_size);
+namespace {
+
+// What vs_moving_mnist_testset and vs_moving_mnist_testset_place check and decide alike: the sizes, the strides, the split of a video over
+// workgroups, the LDS of a workgroup and whether frame starts allow 16-byte stores.  VS_OK, or the code vs_fail returned (nothing launched).
+struct MmTestsetPlan { int chunks, chunk_len, vec; size_t lds; };
+
+int mm_testset_plan(const char* me, int64_t n_digits_total, int digit_h, int digit_w, int n_videos, int num_digits, int seq_len, int frame_size,
+                    const void* frames, int frames_fp32, int64_t st, int64_t sv, MmTestsetPlan& plan) {
+    VS_CHECK_ARG(n_digits_total > 0 && digit_h > 0 && digit_w > 0 && n_videos > 0 && seq_len > 0, "%s: sizes must be positive", me);
+    VS_CHECK_ARG(num_digits >= 1 && num_digits <= MM_MAXD, "%s: 1..%d digits per video (got %d)", me, MM_MAXD, num_digits);
+    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "%s: a %d x %d digit does not fit a frame of %d", me, digit_h, digit_w, frame_size);
     const int64_t FF = (int64_t)frame_size * frame_size;
     // frames must not overlap: the faster-varying index steps over whole frames, the slower one over the whole extent of the faster one
-    const int64_t st = frame_stride_t, sv = frame_stride_v;
     bool apart = st > 0 && sv > 0;
     if (apart && seq_len > 1 && n_videos > 1) apart = st <= sv ? (st >= FF && sv >= (int64_t)seq_len * st) : (sv >= FF && st >= (int64_t)n_videos * sv);
     else if (apart && seq_len > 1) apart = st >= FF;
     else if (apart && n_videos > 1) apart = sv >= FF;
-    VS_CHECK_ARG(apart, "vs_moving_mnist_testset: strides (%lld, %lld) make the %d x %d frames of %lld elements overlap", (long long)st,
-                 (long long)sv, seq_len, n_videos, (long long)FF);
+    VS_CHECK_ARG(apart, "%s: strides (%lld, %lld) make the %d x %d frames of %lld elements overlap", me, (long long)st, (long long)sv, seq_len,
+                 n_videos, (long long)FF);
     // few videos: several workgroups per video, each over a chunk of >= 8 frames, until about two workgroups per CU are in flight
     int chunks = 1;
     if (n_videos < 512) {
@@ -392,22 +439,59 @@ extern "C" int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_t
     const int chunk_len = (int)vs_cdiv(seq_len, chunks);
     chunks = (int)vs_cdiv(seq_len, chunk_len);
     VS_CHECK_ARG((int64_t)chunk_len * FF < (1ll << 31) && (int64_t)n_videos * chunks < (1ll << 31),
-                 "vs_moving_mnist_testset: %d frames of %d x %d per workgroup, or %d x %d workgroups, exceed 2^31", chunk_len, frame_size, frame_size,
-                 n_videos, chunks);
+                 "%s: %d frames of %d x %d per workgroup, or %d x %d workgroups, exceed 2^31", me, chunk_len, frame_size, frame_size, n_videos, chunks);
     const size_t table = (size_t)chunk_len * num_digits * sizeof(int2), images = (size_t)num_digits * digit_h * digit_w;
     if (table + images > 64 * 1024)
-        return vs_fail(VS_ERR_UNSUPPORTED, "vs_moving_mnist_testset: the trajectory table (%d frames x %d digits: %zu B) and the digit images (%zu B) "
-                       "exceed the 65536 B of LDS of a workgroup", chunk_len, num_digits, table, images);
+        return vs_fail(VS_ERR_UNSUPPORTED, "%s: the position table (%d frames x %d digits: %zu B) and the digit images (%zu B) exceed the 65536 B "
+                       "of LDS of a workgroup", me, chunk_len, num_digits, table, images);
     const int esize = frames_fp32 ? 4 : 1;
-    const int vec = FF % (16 / esize) == 0 && (uintptr_t)frames % 16 == 0 && (st * esize) % 16 == 0 && (sv * esize) % 16 == 0;
-    const dim3 grid((unsigned)((int64_t)n_videos * chunks)), block(256);
-    const size_t lds = table + images;
-#define MM_TESTSET_LAUNCH(FP, VEC)                                                                                                               \
-    hipLaunchKernelGGL((moving_mnist_testset_kernel<FP, VEC>), grid, block, lds, (hipStream_t)stream, digits, n_digits_total, digit_h, digit_w, \
-                       (const int*)init, n_videos, num_digits, seq_len, frame_size, chunks, chunk_len, frames, st, sv, (int*)latents)
-    if (frames_fp32) { if (vec) MM_TESTSET_LAUNCH(true, true); else MM_TESTSET_LAUNCH(true, false); }
-    else { if (vec) MM_TESTSET_LAUNCH(false, true); else MM_TESTSET_LAUNCH(false, false); }
+    plan.chunks = chunks;
+    plan.chunk_len = chunk_len;
+    plan.vec = FF % (16 / esize) == 0 && (uintptr_t)frames % 16 == 0 && (st * esize) % 16 == 0 && (sv * esize) % 16 == 0;
+    plan.lds = table + images;
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int n_videos,
+                                       int num_digits, int seq_len, int frame_size, void* frames, int frames_fp32, int64_t frame_stride_t,
+                                       int64_t frame_stride_v, int32_t* latents, void* stream) {
+    const char* me = "vs_moving_mnist_testset";
+    VS_CHECK_ARG(digits && init && frames, "%s: null pointer", me);
+    MmTestsetPlan plan;
+    const int rc = mm_testset_plan(me, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, frames, frames_fp32,
+                                   frame_stride_t, frame_stride_v, plan);
+    if (rc != VS_OK) return rc;
+    const dim3 grid((unsigned)((int64_t)n_videos * plan.chunks)), block(256);
+#define MM_TESTSET_LAUNCH(FP, VEC)                                                                                                                    \
+    hipLaunchKernelGGL((moving_mnist_testset_kernel<FP, VEC>), grid, block, plan.lds, (hipStream_t)stream, digits, n_digits_total, digit_h, digit_w, \
+                       (const int*)init, n_videos, num_digits, seq_len, frame_size, plan.chunks, plan.chunk_len, frames, frame_stride_t,             \
+                       frame_stride_v, (int*)latents)
+    if (frames_fp32) { if (plan.vec) MM_TESTSET_LAUNCH(true, true); else MM_TESTSET_LAUNCH(true, false); }
+    else { if (plan.vec) MM_TESTSET_LAUNCH(false, true); else MM_TESTSET_LAUNCH(false, false); }
 #undef MM_TESTSET_LAUNCH
-    VS_CHECK_LAUNCH("vs_moving_mnist_testset");
+    VS_CHECK_LAUNCH(me);
+    return VS_OK;
+}
+
+extern "C" int vs_moving_mnist_testset_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions,
+                                             const int32_t* digit_idx, int n_videos, int num_digits, int seq_len, int frame_size, void* frames,
+                                             int frames_fp32, int64_t frame_stride_t, int64_t frame_stride_v, int32_t* bad, void* stream) {
+    const char* me = "vs_moving_mnist_testset_place";
+    VS_CHECK_ARG(digits && positions && digit_idx && frames, "%s: null pointer", me);
+    MmTestsetPlan plan;
+    const int rc = mm_testset_plan(me, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, frames, frames_fp32,
+                                   frame_stride_t, frame_stride_v, plan);
+    if (rc != VS_OK) return rc;
+    const dim3 grid((unsigned)((int64_t)n_videos * plan.chunks)), block(256);
+#define MM_PLACE_LAUNCH(FP, VEC)                                                                                                                      \
+    hipLaunchKernelGGL((moving_mnist_testset_place_kernel<FP, VEC>), grid, block, plan.lds, (hipStream_t)stream, digits, n_digits_total, digit_h,    \
+                       digit_w, (const int*)positions, (const int*)digit_idx, n_videos, num_digits, seq_len, frame_size, plan.chunks, plan.chunk_len, \
+                       frames, frame_stride_t, frame_stride_v, (int*)bad)
+    if (frames_fp32) { if (plan.vec) MM_PLACE_LAUNCH(true, true); else MM_PLACE_LAUNCH(true, false); }
+    else { if (plan.vec) MM_PLACE_LAUNCH(false, true); else MM_PLACE_LAUNCH(false, false); }
+#undef MM_PLACE_LAUNCH
+    VS_CHECK_LAUNCH(me);
     return VS_OK;
 }

@@ -13,7 +13,8 @@ Both variants are generated on the device.  The deterministic one (the one main.
 (`deterministic=False`, `main --mnist_stochastic`) redraws the speed vector from the stream at every bounce (`moving_mnist.py:232-234`), so
 the outputs a trajectory takes depend on the trajectory: with a `DeviceRandomState` ONE launch (`vs_mmnist_stochastic_trajectories`) draws and
 walks the whole batch from the stream in HBM and `vs_moving_mnist_place` renders it; otherwise `draw_stochastic` makes the same draws from
-the host stream in a Python loop.  A stochastic test file (`smmnist_test_*.npz`) is not generated here.
+the host stream in a Python loop.  The stochastic TEST set (`smmnist_test_*.npz`, `stochastic_test_set`) is two launches: the same walk
+kernel over all its trajectories, from the stream as the permutation of the test images leaves it, and `vs_moving_mnist_testset_place`.
 """
 import gzip
 import os
@@ -95,6 +96,34 @@ def draw_test_set(n_images, digit_shape, frame_size, max_speed, num_digits, seed
     return digits_idx, init
 
 
+def stochastic_test_set(test_images, frame_size, max_speed, num_digits, seed, seq_len, fp32=False, time_major=True):
+    """The STOCHASTIC test set (`smmnist_test_*.npz`): the reference's preprocessing/mnist/make_test_set.py loop with a sampler built with
+    deterministic=False, which redraws the speed vector from the global stream at every bounce.  test_images: uint8 [n_images, h, w] on the
+    device.  The host only seeds the global NumPy stream and draws the permutation of the images, as the reference does; the stream's state
+    then goes to HBM, ONE launch draws and walks all n_videos * num_digits trajectories in the stream's order (four prefix draws each: start
+    row, start column, row speed, column speed -- ops.mmnist_stochastic_trajectories) and ONE launch renders the frames from the positions
+    (ops.moving_mnist_testset_place).  -> (digits_idx int64 [n_images], frames, latents int32 [seq_len, n_videos, num_digits, 4]); frames
+    as ops.moving_mnist_testset gives them for the same `fp32` / `time_major`.  Both launches are validated (two host syncs: the set is made
+    once), and the global stream is left where the reference's script leaves it: past the last draw of the last trajectory."""
+    from .. import ops
+    n_images, h, w = (int(v) for v in test_images.shape)
+    x_max, y_max, s = frame_size - h, frame_size - w, max_speed
+    if min(x_max, y_max) < 1:
+        raise ValueError('stochastic Moving MNIST: a %d x %d digit fills the %d x %d frame along an axis (unsupported)'
+                         % (h, w, frame_size, frame_size))
+    np.random.seed(seed)
+    digits_idx = np.random.permutation(n_images)
+    n_videos = n_images // num_digits
+    rs = DeviceRandomState(None, test_images.device)
+    _, positions, latents, _ = ops.mmnist_stochastic_trajectories(rs.state, n_videos * num_digits, seq_len, (0, 0, -s, -s),
+                                                                  (x_max + 1, y_max + 1, s + 1, s + 1), x_max, y_max, s, latents=True)
+    used = torch.from_numpy(digits_idx[:n_videos * num_digits].astype(np.int32)).to(test_images.device).view(n_videos, num_digits)
+    frames = ops.moving_mnist_testset_place(test_images, positions.view(seq_len, n_videos, num_digits, 2), used, frame_size, fp32=fp32,
+                                            time_major=time_major)
+    np.random.set_state(rs.get_state())
+    return digits_idx, frames, latents.view(seq_len, n_videos, num_digits, 4)
+
+
 _EPS = 1e-8
 
 
@@ -134,7 +163,7 @@ def _stochastic_collision(rnd, sx, sy, dx, dy, x_max, y_max, max_speed):
     return sx, sy, dx, dy
 
 
-_GENERATED = {}                  # the test sets generated in this process: one launch per (files, geometry, seed, device)
+_GENERATED = {}                  # the test sets generated in this process: one per (files, geometry, seed, device, variant)
 
 
 def forget_generated():
@@ -269,30 +298,42 @@ class MovingMNIST:
             data = [sequences[:, i].astype(np.single) for i in range(sequences.shape[1])]
         return cls(data, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device=device)
 
+    @staticmethod
+    def generated_key(data_dir, nx, max_speed, num_digits, device, seed=42, file_seq_len=100, deterministic=True):
+        """What identifies a set kept by `generated`: the files' path, the geometry, the seed, the device and the variant."""
+        key = (os.path.abspath(data_dir), nx, max_speed, num_digits, seed, file_seq_len, str(torch.device(device)))
+        return key if deterministic else key + ('stochastic',)
+
     @classmethod
-    def generated(cls, data_dir, nx, nt_cond, seq_len, max_speed, num_digits, device, seed=42, file_seq_len=100):
+    def generated(cls, data_dir, nx, nt_cond, seq_len, max_speed, num_digits, device, seed=42, file_seq_len=100, deterministic=True):
         """The `train=False` set without its file: the videos `preprocessing/mnist/make_test_set.py --seed seed --seq_len file_seq_len`
         would write from the t10k idx files under `data_dir`, rendered straight into HBM by one fp32 launch (vs_moving_mnist_testset).
-        `.data` equals, bit for bit, what `make_dataset(train=False)` loads from that file.  The object also keeps `latents` (int32
+        `.data` equals, bit for bit, what `make_dataset(train=False)` loads from that file.  deterministic=False: the stochastic set that
+        `make_test_set.py --stochastic` writes (`stochastic_test_set`: one walk launch and one fp32 render launch), which equals what
+        `make_dataset(train=False, deterministic=False)` loads; the two variants are kept apart.  The object also keeps `latents` (int32
         [file_seq_len, N, num_digits, 4] on the device), `test_images` (the t10k images, uint8 on the device, file order) and `digits_idx`
         (the permutation: video v shows images digits_idx[v * num_digits + n]).  The global NumPy stream is left as it was found, and a
         set is generated once per process: a second call with the same path, geometry, seed and device SHARES the tensors, so `.data`,
         `latents` and `test_images` are read-only to every holder (`forget_generated()` releases them)."""
         from .. import ops
         device = torch.device(device)
-        key = (os.path.abspath(data_dir), nx, max_speed, num_digits, seed, file_seq_len, str(device))
+        key = cls.generated_key(data_dir, nx, max_speed, num_digits, device, seed, file_seq_len, deterministic)
         if key not in _GENERATED:
             images = read_mnist_images(data_dir, train=False)
+            test_images = torch.from_numpy(images).to(device)
             state = np.random.get_state()
             try:
-                digits_idx, init = draw_test_set(len(images), images.shape[1:], nx, max_speed, num_digits, seed)
+                if deterministic:
+                    digits_idx, init = draw_test_set(len(images), images.shape[1:], nx, max_speed, num_digits, seed)
+                    frames, latents = ops.moving_mnist_testset(test_images, init, file_seq_len, nx, fp32=True, time_major=False)
+                else:
+                    digits_idx, frames, latents = stochastic_test_set(test_images, nx, max_speed, num_digits, seed, file_seq_len, fp32=True,
+                                                                      time_major=False)
             finally:
                 np.random.set_state(state)
-            test_images = torch.from_numpy(images).to(device)
-            frames, latents = ops.moving_mnist_testset(test_images, init, file_seq_len, nx, fp32=True, time_major=False)
             _GENERATED[key] = (frames, latents, test_images, digits_idx)
         frames, latents, test_images, digits_idx = _GENERATED[key]
-        ds = cls(frames, nx, nt_cond, seq_len, max_speed, True, num_digits, False, device=device)
+        ds = cls(frames, nx, nt_cond, seq_len, max_speed, bool(deterministic), num_digits, False, device=device)
         ds.latents, ds.test_images, ds.digits_idx = latents, test_images, digits_idx
         return ds
 

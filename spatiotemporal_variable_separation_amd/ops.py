@@ -2491,6 +2491,39 @@ def moving_mnist_testset(digits, init, seq_len, frame_size, *, fp32=False, time_
     return frames, latents
 
 
+def moving_mnist_testset_place(digits, positions, digit_idx, frame_size, *, fp32=False, time_major=True, validate=True):
+    """The RAW test-set frames of `moving_mnist_testset` from STORED positions, in ONE launch (vs_moving_mnist_testset_place): the renderer
+    of the stochastic test set, whose trajectories mmnist_stochastic_trajectories walks.  digits uint8 [N, h, w], positions int32 [T, V, nd,
+    2] = (row, column) of the top-left corners, digit_idx int32 [V, nd], all on the device -> frames with the raw values 0..255, uint8 or
+    (fp32=True) float32, shaped [T, V, 1, F, F] (time_major, the test file's layout) or [V, T, 1, F, F].  validate=True reads back the
+    launch's error word (a host sync) and raises VarsepHipError for a digit index outside [0, N) or a digit that would be cut at the frame
+    border (such a digit is not drawn); validate=False keeps the call free of host syncs (the caller has checked the tables)."""
+    require_cuda(digits, positions, digit_idx)
+    if digits.dtype != torch.uint8 or digits.dim() != 3 or positions.dtype != torch.int32 or positions.dim() != 4 or positions.shape[3] != 2 \
+            or positions.shape[0] < 1 or positions.shape[1] < 1 or digit_idx.dtype != torch.int32 or digit_idx.dim() != 2 \
+            or tuple(digit_idx.shape) != tuple(positions.shape[1:3]):
+        raise _lib.VarsepHipError('moving_mnist_testset_place: digits uint8 [N, h, w], positions int32 [T >= 1, V >= 1, nd, 2] and digit_idx '
+                                  'int32 [V, nd] expected')
+    digits, positions, digit_idx = digits.contiguous(), positions.contiguous(), digit_idx.contiguous()
+    N, h, w = digits.shape
+    T, V, nd = positions.shape[:3]
+    F = int(frame_size)
+    device = digits.device
+    with torch.cuda.device(device):
+        frames = torch.empty((T, V, 1, F, F) if time_major else (V, T, 1, F, F), dtype=torch.float32 if fp32 else torch.uint8, device=device)
+        bad = torch.zeros((1,), dtype=torch.int32, device=device) if validate else None
+        stride_t, stride_v = (frames.stride(0), frames.stride(1)) if time_major else (frames.stride(1), frames.stride(0))
+        e0 = _pb()
+        check(_lib.load_library().vs_moving_mnist_testset_place(digits.data_ptr(), N, h, w, positions.data_ptr(), digit_idx.data_ptr(), V, nd, T, F,
+                                                                frames.data_ptr(), 1 if fp32 else 0, stride_t, stride_v, _ptr(bad), stream_ptr()),
+              'vs_moving_mnist_testset_place')
+        _pe(e0, 'vs_moving_mnist_testset_place', nbytes=float(frames.numel() * frames.element_size() + positions.numel() * 4))
+    if validate and int(bad.item()):
+        raise _lib.VarsepHipError('moving_mnist_testset_place: a digit index is outside [0, %d) or a digit does not lie inside the %d x %d frame'
+                                  % (N, F, F))
+    return frames
+
+
 def frames_to_u8_nhwc(x):
     """[B, T, C, H, W] fp32 / 16-bit -> uint8 [B, T, H, W, C] on the device: (uint8)(x * 255.f), i.e. `x.mul(255).byte().permute(0, 1, 3, 4, 2)`
     bit for bit for x in [0, 1]; out-of-range values saturate to 0 / 255 (NaN -> 0) where torch's cast is undefined (vs_frames_to_u8_nhwc)."""

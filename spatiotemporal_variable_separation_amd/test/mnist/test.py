@@ -8,6 +8,8 @@ the device generator from the global NumPy stream in the reference's order, the 
 saved array is converted to uint8 on the device (vs_frames_to_u8_nhwc).  There is no CPU mode: --device is required.
 `--data_dir generated:D` needs only the raw MNIST idx files under D: the test set that preprocessing/mnist/make_test_set.py would write
 with its defaults is generated straight into HBM (`MovingMNIST.generated`), no .npz is read or written.
+`--mnist_stochastic` evaluates a model trained with `main --mnist_stochastic`: the test set is the stochastic one (smmnist_test_*.npz, or
+generated with the prefix) and the swap videos come from the stochastic sampler; test_disentanglement_stochastic.py is the content swap on it.
 """
 import os
 
@@ -27,11 +29,24 @@ def split_data_dir(data_dir):
     return (data_dir[len(GENERATED):], True) if data_dir.startswith(GENERATED) else (data_dir, False)
 
 
-def load_dataset(args, train=False, device='cuda'):
+def load_dataset(args, train=False, device='cuda', stochastic=False):
+    """stochastic: the command line's --mnist_stochastic, never the `mnist_stochastic` that training saved in params.json (`args` is that
+    configuration): an existing experiment is evaluated on what it was evaluated on before."""
     data_dir, generated = split_data_dir(args.data_dir)
     if generated and not train:      # make_test_set.py's defaults: seed 42, 100 frames, frame size 64, speed 4
-        return MovingMNIST.generated(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, args.n_object, device)
-    return MovingMNIST.make_dataset(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, True, args.n_object, train, device=device)
+        return MovingMNIST.generated(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, args.n_object, device,
+                                     deterministic=not stochastic)
+    return MovingMNIST.make_dataset(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, not stochastic, args.n_object, train,
+                                    device=device)
+
+
+def add_stochastic_flag(p):
+    """--mnist_stochastic (not in the reference), off by default.  Returns `p`."""
+    p.add_argument('--mnist_stochastic', action='store_true',
+                   help='Evaluate on the stochastic Moving MNIST variant: the test set is smmnist_test_*.npz (make_test_set.py --stochastic) '
+                        'or, with --data_dir generated:D, the stochastic set generated in HBM; swap videos come from the stochastic sampler. '
+                        'Only this flag selects it, never the mnist_stochastic saved with the experiment.')
+    return p
 
 
 def test_batches(test_dataset, batch_size):
@@ -52,8 +67,9 @@ def main(args):
     xp_config = load_xp_config(args, device, args.nt_pred)
 
     print('Loading data...')
-    test_dataset = load_dataset(xp_config, train=False, device=device)
-    train_dataset = load_dataset(xp_config, train=True, device=device)
+    stochastic = bool(getattr(args, 'mnist_stochastic', False))
+    test_dataset = load_dataset(xp_config, train=False, device=device, stochastic=stochastic)
+    train_dataset = load_dataset(xp_config, train=True, device=device, stochastic=stochastic)
     nc = 1
     size = 64
 
@@ -108,10 +124,11 @@ def main(args):
     return results
 
 
-def build_parser():
+def build_parser(stochastic=False):
+    """The reference's flags plus --precision; stochastic=True (the command line's parser) adds --mnist_stochastic."""
     p = base_parser('PDE-Driven Spatiotemporal Disentanglement (Moving MNIST testing)', batch_size=16, test_seed=True)
-    return add_precision_flag(p)
+    return add_stochastic_flag(add_precision_flag(p)) if stochastic else add_precision_flag(p)
 
 
 if __name__ == '__main__':
-    main(build_parser().parse_args())
+    main(build_parser(stochastic=True).parse_args())
