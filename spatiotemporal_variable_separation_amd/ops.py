@@ -2524,18 +2524,29 @@ def moving_mnist_testset_place(digits, positions, digit_idx, frame_size, *, fp32
     return frames
 
 
-def frames_to_u8_nhwc(x):
+def frames_to_u8_nhwc(x, out=None):
     """[B, T, C, H, W] fp32 / 16-bit -> uint8 [B, T, H, W, C] on the device: (uint8)(x * 255.f), i.e. `x.mul(255).byte().permute(0, 1, 3, 4, 2)`
-    bit for bit for x in [0, 1]; out-of-range values saturate to 0 / 255 (NaN -> 0) where torch's cast is undefined (vs_frames_to_u8_nhwc)."""
-    require_cuda(x)
+    bit for bit for x in [0, 1]; out-of-range values saturate to 0 / 255 (NaN -> 0) where torch's cast is undefined (vs_frames_to_u8_nhwc).
+    out: optional contiguous uint8 [B, T, H, W, C] tensor on x's device, written in place and returned (a slice of a preallocated
+    [N, T, H, W, C] buffer, for instance); anything else is refused."""
+    require_cuda(x, out)
     if x.dim() != 5:
         raise _lib.VarsepHipError('frames_to_u8_nhwc: [B, T, C, H, W] expected (got %s)' % (tuple(x.shape),))
     B, T, C, H, W = x.shape
     x = x.contiguous()
-    out = torch.empty((B, T, H, W, C), dtype=torch.uint8, device=x.device)
+    if out is None:
+        out = torch.empty((B, T, H, W, C), dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, T, H, W, C) or out.device != x.device or not out.is_contiguous():
+        raise _lib.VarsepHipError('frames_to_u8_nhwc: out must be a contiguous uint8 %s tensor on %s (got %s %s on %s, strides %s)'
+                                  % ((B, T, H, W, C), x.device, out.dtype, tuple(out.shape), out.device, tuple(out.stride())))
     if out.numel():
-        check(_lib.load_library().vs_frames_to_u8_nhwc(x.data_ptr(), dtype_code(x), B * T, C, H * W, out.data_ptr(), stream_ptr()),
+        # the kernel stores four bytes at a time: a slice that starts off a 4-byte boundary (odd frame sizes) is filled through a fresh,
+        # aligned tensor and one device copy
+        dst = out if out.data_ptr() % 4 == 0 else torch.empty_like(out)
+        check(_lib.load_library().vs_frames_to_u8_nhwc(x.data_ptr(), dtype_code(x), B * T, C, H * W, dst.data_ptr(), stream_ptr()),
               'vs_frames_to_u8_nhwc')
+        if dst is not out:
+            out.copy_(dst)
     return out
 
 

@@ -29,14 +29,13 @@ either file to the same arrays.  Measurements: profiles/deflate_timing.md.
 import argparse
 import os
 import time
-import zlib
 
 import numpy as np
 import torch
 
 from ... import ops
-from ..._lib import VarsepHipError
-from ...utils import npz
+from ..._lib import VarsepHipError, require_cuda
+from ...utils.savez import COMPRESS_ENV, npz_compressor, savez_compressed  # noqa: F401  (the rule lives there; importable from here as before)
 from ...data.device import require_gpu
 from ...data.moving_mnist import draw_test_set, read_mnist_images, read_mnist_labels, stochastic_test_set
 
@@ -110,47 +109,21 @@ def generate_device(data_dir, seq_len, seed, digits, frame_size, max_speed, devi
     return out
 
 
-COMPRESS_ENV = 'VARSEP_NPZ_COMPRESS'
-
-
-def npz_compressor(compress=None):
-    """'host' or 'device': who compresses the test file.  The keyword wins; None reads the environment variable VARSEP_NPZ_COMPRESS; when
-    that is unset or empty the host does (np.savez_compressed, the behaviour before the device encoder existed).  Any other value raises,
-    naming the two."""
-    source = 'compress'
-    if compress is None:
-        compress, source = os.environ.get('VARSEP_NPZ_COMPRESS', '') or 'host', COMPRESS_ENV
-    if compress not in ('host', 'device'):
-        raise ValueError("%s=%r: 'host' or 'device' expected" % (source, compress))
-    return compress
-
-
 def save_test_set(path, arrays, compress=None, timings=None):
-    """Writes the four arrays (host arrays or device tensors, `generate` / `generate_device`) to the .npz file `path`.  compress: 'host'
-    (tensors are downloaded; np.savez_compressed), 'device' (device tensors are compressed in HBM and only the compressed bytes are
-    downloaded: ops.deflate_raw_slabs, ops.crc32, utils/npz.write_npz) or None (`npz_compressor`).  timings: optional dict that receives
-    the seconds of 'download' + 'write' (host) or of 'write' (device: compression, download of the compressed bytes and file together)."""
+    """Writes the four arrays (host arrays or device tensors, `generate` / `generate_device`) to the .npz file `path` through
+    utils/savez.savez_compressed.  compress: 'host' (tensors are downloaded; np.savez_compressed), 'device' (device tensors are compressed
+    in HBM and only the compressed bytes are downloaded: ops.deflate_raw_slabs, ops.crc32, utils/npz.write_npz) or None
+    (`npz_compressor`).  Unlike the general writer, 'device' here takes device tensors only: the set was generated to stay in HBM.
+    timings: optional dict that receives the seconds of 'download' + 'write' (host) or of 'write' (device: compression, download of the
+    compressed bytes and file together)."""
     compress = npz_compressor(compress)
-    t0 = time.perf_counter()
-    if compress == 'host':
-        host = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in arrays.items()}
-        t1 = time.perf_counter()
-        np.savez_compressed(path, **host)
-        if timings is not None:
-            timings.update(download=t1 - t0, write=time.perf_counter() - t1)
-        return
-    members = []
-    for name, t in arrays.items():
-        if not isinstance(t, torch.Tensor):
-            raise VarsepHipError("save_test_set: compress='device' takes device tensors (generate_device); %s is a %s"
-                                 % (name, type(t).__name__))
-        t = t.contiguous()
-        header = npz.npy_header(tuple(t.shape), npz.numpy_dtype(t.dtype))
-        members.append(npz.Member(name + '.npy', header, (piece.cpu().numpy() for piece, _ in ops.deflate_raw_slabs(t)),
-                                  ops.crc32(t, init=zlib.crc32(header)), t.numel() * t.element_size()))
-    npz.write_npz(path, members)
-    if timings is not None:
-        timings.update(write=time.perf_counter() - t0)
+    if compress == 'device':
+        for name, t in arrays.items():
+            if not isinstance(t, torch.Tensor):
+                raise VarsepHipError("save_test_set: compress='device' takes device tensors (generate_device); %s is a %s"
+                                     % (name, type(t).__name__))
+        require_cuda(*arrays.values())
+    savez_compressed(path, arrays, compress, timings=timings)
 
 
 def build_parser(stochastic=False):

@@ -10,15 +10,19 @@ saved array is converted to uint8 on the device (vs_frames_to_u8_nhwc).  There i
 with its defaults is generated straight into HBM (`MovingMNIST.generated`), no .npz is read or written.
 `--mnist_stochastic` evaluates a model trained with `main --mnist_stochastic`: the test set is the stochastic one (smmnist_test_*.npz, or
 generated with the prefix) and the swap videos come from the stochastic sampler; test_disentanglement_stochastic.py is the content swap on it.
+Who compresses the six frame files: the environment variable VARSEP_NPZ_COMPRESS=host|device (utils/savez.py), read once at the start of
+`main`.  `host` (the default) copies every batch's uint8 frames to the host and writes with np.savez_compressed, as before; `device` keeps
+them in HBM, compresses them there and downloads only the compressed bytes.  Names, keys, dtypes, shapes and the arrays np.load gives are
+the same; measurements and the sizes of the device-written files: profiles/eval_npz_timing.md.
 """
 import os
 
-import numpy as np
 import torch
 
 from ...data.moving_mnist import MovingMNIST
+from ...utils import savez
 from ...utils.metrics import frame_metrics
-from ..utils import add_precision_flag, base_parser, load_model, load_xp_config, print_results, seed_all, setup_device, to_host_u8
+from ..utils import U8Frames, add_precision_flag, base_parser, load_model, load_xp_config, print_results, seed_all, setup_device
 
 
 GENERATED = 'generated:'         # --data_dir generated:D: the idx files are under D and the test set is generated in HBM, no .npz is read
@@ -62,6 +66,7 @@ def test_batches(test_dataset, batch_size):
 
 
 def main(args):
+    compress = savez.npz_compressor()         # who compresses the six frame files: read once, a bad value is refused before any work
     device = setup_device(args)
     seed_all(args.test_seed)
     xp_config = load_xp_config(args, device, args.nt_pred)
@@ -79,12 +84,13 @@ def main(args):
     print('Generating samples...')
     torch.set_grad_enabled(False)
     nt_test = xp_config.nt_cond + args.nt_pred
-    predictions, content_swap, cond_swap, target_swap, cond, gt = [], [], [], [], [], []
+    # (the device route converts every batch straight into one buffer per file: the number of test videos is known)
+    predictions, content_swap, cond_swap, target_swap, cond, gt = (U8Frames(compress, test_dataset.data.shape[0]) for _ in range(6))
     results = {'mse': [], 'psnr': [], 'ssim': []}
     for x_cond, x_target in test_batches(test_dataset, args.batch_size):
         bsz = len(x_cond)
-        cond.append(to_host_u8(x_cond))
-        gt.append(to_host_u8(x_target))
+        cond.append(x_cond)
+        gt.append(x_target)
 
         # Prediction
         x_pred, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
@@ -96,31 +102,31 @@ def main(args):
         x_swap_cond, x_swap_target = train_dataset.batch(args.batch_size)
         x_swap_cond = x_swap_cond[:bsz]
         x_swap_target = x_swap_target[:bsz]
-        cond_swap.append(to_host_u8(x_swap_cond))
-        target_swap.append(to_host_u8(x_swap_target))
+        cond_swap.append(x_swap_cond)
+        target_swap.append(x_swap_target)
         x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
         # reference quirk: `xp_config.dt` is not in params.json and DotDict reads a missing key as None, so this slice keeps all
         # nt_cond + nt_pred frames
         x_swap_pred = x_swap_pred[:, xp_config.dt:]
-        content_swap.append(to_host_u8(x_swap_pred))
+        content_swap.append(x_swap_pred)
 
         # Pixelwise quantitative eval
         x_target = x_target.reshape(-1, args.nt_pred, nc, size, size)
         metrics_batch = frame_metrics(x_pred.float().contiguous(), x_target)
-        predictions.append(to_host_u8(x_pred))
+        predictions.append(x_pred)
         for name in results:
             results[name].append(metrics_batch[name].cpu())
 
     results = print_results(results)
 
-    np.savez_compressed(os.path.join(args.xp_dir, 'results.npz'), **results)
-    np.savez_compressed(os.path.join(args.xp_dir, 'predictions.npz'), predictions=torch.cat(predictions).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'gt.npz'), gt=torch.cat(gt).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'cond.npz'), cond=torch.cat(cond).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'content_swap.npz'), content_swap=torch.cat(content_swap).numpy())
+    savez.savez_compressed(os.path.join(args.xp_dir, 'results.npz'), results, compress)
+    savez.savez_compressed(os.path.join(args.xp_dir, 'predictions.npz'), {'predictions': predictions.cat()}, compress)
+    savez.savez_compressed(os.path.join(args.xp_dir, 'gt.npz'), {'gt': gt.cat()}, compress)
+    savez.savez_compressed(os.path.join(args.xp_dir, 'cond.npz'), {'cond': cond.cat()}, compress)
+    savez.savez_compressed(os.path.join(args.xp_dir, 'content_swap.npz'), {'content_swap': content_swap.cat()}, compress)
     # reference quirk: the swap conditioning frames are stored under the key `target_swap`
-    np.savez_compressed(os.path.join(args.xp_dir, 'cond_swap.npz'), target_swap=torch.cat(cond_swap).numpy())
-    np.savez_compressed(os.path.join(args.xp_dir, 'target_swap.npz'), target_swap=torch.cat(target_swap).numpy())
+    savez.savez_compressed(os.path.join(args.xp_dir, 'cond_swap.npz'), {'target_swap': cond_swap.cat()}, compress)
+    savez.savez_compressed(os.path.join(args.xp_dir, 'target_swap.npz'), {'target_swap': target_swap.cat()}, compress)
     return results
 
 

@@ -8,6 +8,7 @@ import torch
 from .. import functional as VF
 from .. import ops
 from ..data.device import DeviceBatchLoader
+from ..utils import savez
 from ..utils.helper import load_json, load_sep_net
 from ..utils.metrics import _ssim_wrapper  # noqa: F401  (test/utils.py:19-24, on the device)
 
@@ -81,6 +82,48 @@ def to_host_u8(x):
     return ops.frames_to_u8_nhwc(x).cpu()
 
 
+class U8Frames:
+    """The uint8 frames an evaluation script saves, collected batch by batch.  compress='host': every batch is converted on the device and
+    copied to the host at once (`to_host_u8`), `cat()` is the NumPy array of `torch.cat` -- the calls of the time before the device
+    encoder, in their order.  compress='device': the uint8 batches stay in HBM and `cat()` is a device tensor for
+    utils/savez.savez_compressed; nothing is copied to the host per batch.  n_items: the number of samples when the caller knows it;
+    the device route then converts every batch straight into one preallocated [n_items, T, H, W, C] buffer (allocated at the first
+    batch, whose frame shape it takes) and `cat()` is that buffer, with no `torch.cat` copy beside it."""
+
+    def __init__(self, compress, n_items=None):
+        if compress not in ('host', 'device'):
+            raise ValueError("compress=%r: 'host' or 'device' expected" % (compress,))
+        self.compress, self.n_items = compress, n_items
+        self.parts, self.buffer, self.filled = [], None, 0
+
+    def append(self, x):
+        """x: [B, T, C, H, W] on the device."""
+        if self.compress == 'host':
+            self.parts.append(to_host_u8(x))
+        elif self.n_items is None:
+            self.parts.append(ops.frames_to_u8_nhwc(x))
+        else:
+            B, T, C, H, W = x.shape
+            if self.buffer is None:
+                self.buffer = torch.empty((int(self.n_items), T, H, W, C), dtype=torch.uint8, device=x.device)
+            if self.filled + B > self.buffer.shape[0]:
+                raise ValueError('U8Frames: %d samples appended to a collector made for %d' % (self.filled + B, self.buffer.shape[0]))
+            ops.frames_to_u8_nhwc(x, out=self.buffer[self.filled:self.filled + B])
+            self.filled += B
+
+    def cat(self):
+        """All frames in the order of the appends: a NumPy array (host) or a device tensor (device)."""
+        if self.compress == 'host':
+            return torch.cat(self.parts).numpy()
+        if self.n_items is None:
+            if len(self.parts) != 1:
+                self.parts = [torch.cat(self.parts)]          # (the batches are released: one copy of the frames stays in HBM)
+            return self.parts[0]
+        if self.buffer is None:
+            raise RuntimeError('U8Frames: nothing was appended')
+        return self.buffer[:self.filled]
+
+
 def print_results(results):
     """The reference's closing block (test/mnist/test.py:151-159): concatenated per-sample arrays and their means."""
     print('\n')
@@ -150,24 +193,28 @@ def best_of_permutations(pred, gt_swap):
     return {'mse': m.min(1)[0], 'psnr': psnr.max(1)[0], 'ssim': s.max(1)[0]}
 
 
-def run_content_swap(xp_dir, sep_net, nt_cond, nt_test, batches):
+def run_content_swap(xp_dir, sep_net, nt_cond, nt_test, batches, compress=None):
     """The loop and the five files both content-swap scripts share (test/mnist/test_disentanglement.py:118-223).  `batches` yields
     (x_cond, x_gt_swap, x_swap_cond, x_swap_target): S is extracted from `x_cond`, drives a forecast from `x_swap_cond`, and the forecast
     is scored against every candidate of `x_gt_swap` [B, P, ...], best per sample.  Reference quirks kept: `cond_swap_test` holds the S
-    video's conditioning frames `x_cond`, not `x_swap_cond`; `gt_swap` is the first candidate."""
-    gt_swap, content_swap, cond_swap, target_swap = [], [], [], []
+    video's conditioning frames `x_cond`, not `x_swap_cond`; `gt_swap` is the first candidate.
+    compress: who compresses the files (utils/savez.npz_compressor).  The content-swap scripts' `main`s hand nothing on, so the rule
+    (VARSEP_NPZ_COMPRESS) is read here, once, before the first batch is drawn: a bad value is refused before any forecast.  The number
+    of samples is not known here (`batches` is a generator), so on the device route the batches are kept and concatenated at the end."""
+    compress = savez.npz_compressor(compress)
+    gt_swap, content_swap, cond_swap, target_swap = (U8Frames(compress) for _ in range(4))
     results = {'mse': [], 'psnr': [], 'ssim': []}
     for x_cond, x_gt_swap, x_swap_cond, x_swap_target in batches:
         # Extraction of S
         _, _, s_code, _ = sep_net.get_forecast(x_cond, nt_test)
 
         # Content swap
-        cond_swap.append(to_host_u8(x_cond))
-        target_swap.append(to_host_u8(x_swap_target))
+        cond_swap.append(x_cond)
+        target_swap.append(x_swap_target)
         x_swap_pred = sep_net.get_forecast(x_swap_cond, nt_test, init_s_code=s_code)[0]
         x_swap_pred = x_swap_pred[:, nt_cond:].float().contiguous()
-        content_swap.append(to_host_u8(x_swap_pred))
-        gt_swap.append(to_host_u8(x_gt_swap[:, 0]))
+        content_swap.append(x_swap_pred)
+        gt_swap.append(x_gt_swap[:, 0])
 
         # Pixelwise quantitative eval: every candidate scored, best per sample
         metrics_batch = best_of_permutations(x_swap_pred, x_gt_swap.float())
@@ -176,9 +223,9 @@ def run_content_swap(xp_dir, sep_net, nt_cond, nt_test, batches):
 
     results = print_results(results)
 
-    np.savez_compressed(os.path.join(xp_dir, 'results_swap.npz'), **results)
-    np.savez_compressed(os.path.join(xp_dir, 'content_swap_gt.npz'), gt_swap=torch.cat(gt_swap).numpy())
-    np.savez_compressed(os.path.join(xp_dir, 'content_swap_test.npz'), content_swap=torch.cat(content_swap).numpy())
-    np.savez_compressed(os.path.join(xp_dir, 'cond_swap_test.npz'), cond_swap=torch.cat(cond_swap).numpy())
-    np.savez_compressed(os.path.join(xp_dir, 'target_swap_test.npz'), target_swap=torch.cat(target_swap).numpy())
+    savez.savez_compressed(os.path.join(xp_dir, 'results_swap.npz'), results, compress)
+    savez.savez_compressed(os.path.join(xp_dir, 'content_swap_gt.npz'), {'gt_swap': gt_swap.cat()}, compress)
+    savez.savez_compressed(os.path.join(xp_dir, 'content_swap_test.npz'), {'content_swap': content_swap.cat()}, compress)
+    savez.savez_compressed(os.path.join(xp_dir, 'cond_swap_test.npz'), {'cond_swap': cond_swap.cat()}, compress)
+    savez.savez_compressed(os.path.join(xp_dir, 'target_swap_test.npz'), {'target_swap': target_swap.cat()}, compress)
     return results
