@@ -338,7 +338,9 @@ int vs_frame_metrics(const float* pred, const float* target, int64_t planes, int
  * digits [n_digits_total, digit_h, digit_w] uint8 in HBM; init [batch, num_digits, 5] int32 = (digit index, start row, start column,
  * row speed, column speed) per digit, i.e. the five np.random.randint draws of the reference in its order; out [batch, seq_len, 1,
  * frame, frame] (fp32 or a 16-bit type): digits added at their bounced positions, clipped at 255, divided by 255.
- * Trajectories are computed in IEEE double, operation for operation as the reference does in Python floats: bit-identical frames. */
+ * Trajectories are computed in IEEE double, operation for operation as the reference does in Python floats: bit-identical frames.
+ * The kernel, plan and refusals of vs_moving_mnist_testset below (a workgroup takes a chunk of >= 1 frames of a video; a digit index outside
+ * [0, n_digits_total) is never read: that digit is not drawn; VS_ERR_UNSUPPORTED when the digit images exceed the LDS).               */
 int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
                           int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream);
 
@@ -527,12 +529,12 @@ int vs_mmnist_stochastic_trajectories(uint32_t* state, const int32_t* lows, cons
                                       int x_max, int y_max, int max_speed, const int32_t* start, int32_t* pre, int32_t* positions,
                                       int32_t* latents, int32_t* desc, int desc_nd, int32_t* bad, void* stream);
 
-/* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip).
+/* Evaluation scripts (test/mnist/test.py, test/mnist/test_disentanglement.py, csrc/vs_eval.hip; vs_moving_mnist_place: csrc/vs_data.hip).
  * vs_moving_mnist_place: videos composited from digits at STORED positions (test_disentanglement.py:66-86 `SwapDataset`).
  * digits [n_digits_total, digit_h, digit_w] uint8; positions [>= seq_len, n_seq, num_digits, 2] int32 = (row, column) of each object's
  * top-left corner per frame (the (sx, sy) of the test file's `latents`); desc [n_videos, 1 + num_digits] int32 = (sequence, digit index of
  * object 0 .. num_digits-1).  out [n_videos, seq_len, 1, frame, frame] (fp32 or a 16-bit type): sum of the digits, min(., 255) / 255, the
- * arithmetic of vs_moving_mnist_batch.  A sequence / digit index out of range or a digit not wholly inside the frame is not drawn and sets
+ * arithmetic, kernel and plan of vs_moving_mnist_batch.  A sequence / digit index out of range or a digit not wholly inside the frame is not drawn and sets
  * *bad = 1 (bad may be NULL); the launch never reads or writes out of bounds.                                                          */
 int vs_moving_mnist_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions, int n_seq,
                           int num_digits, const int32_t* desc, int n_videos, int seq_len, int frame_size, void* out, int out_dtype,

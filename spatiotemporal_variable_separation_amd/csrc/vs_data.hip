@@ -1,116 +1,77 @@
-// vs_data.hip -- input pipeline on the device: Moving-MNIST sequence generation (reference: data/moving_mnist.py:112-253) and the
-// Moving-MNIST test set in one launch (reference: preprocessing/mnist/make_test_set.py; below the training generator; walked in the launch,
-// or -- the stochastic set -- rendered from positions that vs_mmnist_walk.hip walked), the 3D
-// Chairs batch gather (reference: data/chairs.py:45-64) and the table-driven window gather of the TaxiBJ timeline (reference:
-// data/taxibj.py:74-100), both at the end of this file.
+// vs_data.hip -- input pipeline on the device: the Moving-MNIST renderers (reference: data/moving_mnist.py:112-253 for training batches,
+// preprocessing/mnist/make_test_set.py for the test set, test_disentanglement.py:66-86 for the content-swap videos), the 3D Chairs batch
+// gather (reference: data/chairs.py:45-64) and the table-driven window gather of the TaxiBJ timeline (reference: data/taxibj.py:74-100),
+// both at the end of this file.
 //
-// The reference builds every training sequence on the host: per digit five draws from the global NumPy stream (digit index, start
+// The reference builds every Moving-MNIST sequence on the host: per digit five draws from the global NumPy stream (digit index, start
 // position, speed), a trajectory of `seq_len` positions with elastic bounces off the frame borders computed in Python floats
-// (= IEEE double), and a compositing loop that adds the 28x28 digit into a 64x64 frame per time step, clips at 255 and divides by
-// 255.  At MI355X step rates (Moving-MNIST B=128: > 100 k frames/s) a 4-worker host generator is the bottleneck, so here only the
-// five integers per digit cross PCIe (drawn by the host from the same NumPy stream, in the reference's order) and one launch
-// renders the whole batch:
-//   * trajectory: thread d < num_digits of every workgroup replays moving_mnist.py:154-237 for its digit in double arithmetic,
-//     operation for operation (deterministic mode: no draws inside the bounce loop), and leaves the rounded positions
-//     (Python round() = round-half-even = rint) of frame t in LDS;
-//   * compositing: the workgroup of (sample b, frame t) writes the 64x64 frame: sum of the digits' pixels at their positions,
-//     min(., 255), / 255 (IEEE division: same bits as NumPy's float32 division), as fp32 or a 16-bit type.
-// Digits live in HBM as uint8 [n_digits_total, h, w] (MNIST: 47 MB).
+// (= IEEE double), and a compositing loop that adds the 28x28 digit into a 64x64 frame per time step and clips at 255; training batches
+// are divided by 255, the test file keeps the bytes.  At MI355X step rates (Moving-MNIST B=128: > 100 k frames/s) a 4-worker host
+// generator is the bottleneck, so here only integers reach the device (the five per digit, or tables of positions) and one launch
+// renders all videos.  Four entry points, ONE body.  A workgroup owns (video, chunk of `chunk_len` frames) and
+//   1. a LOADER leaves the digits' (row, column) per frame of the chunk in LDS.  WALK (vs_moving_mnist_batch, vs_moving_mnist_testset):
+//      thread d < nd walks digit d from `init` with the deterministic sampler of vs_mmnist_bounce_core.h (double arithmetic, operation for
+//      operation the reference's; frames before the chunk are replayed, not recorded) and, if asked, writes (row, column, row speed,
+//      column speed) to `latents`.  TABLE (vs_moving_mnist_place, vs_moving_mnist_testset_place): a copy from positions
+//      [T][n_seq][nd][2], the video's sequence and digits named by a row of an index table; a sequence or digit index out of range, or a
+//      digit not wholly inside the frame, raises *bad and gets a position that no pixel of any frame meets, so it is not drawn;
+//   2. the workgroup copies its nd digit images into LDS once (a digit index outside [0, n_digits_total) is never read: zeros);
+//   3. the COMPOSITOR (mm_compose): per frame every thread builds G consecutive pixels (16 bytes: G = 16 as uint8, 8 as a 16-bit type, 4
+//      as fp32) from the LDS digits -- sum, min(., 255), and for the normalised forms / 255 (IEEE division: same bits as NumPy's float32
+//      division) -- and stores them as one 16-byte vector: at F = 64 as uint8 a frame is exactly one store per thread, a wave writes
+//      1 KiB contiguous.  When the G pixels share a row (F % G == 0) the row is tested once per digit, and most rows miss a digit.
+// Frame (t, v) starts at element t * st + v * sv.  VEC needs F * F % G == 0 and 16-byte aligned frame starts (mm_plan decides from the
+// entry point's arguments); otherwise the same arithmetic goes element by element.  LDS: int2 pos[chunk_len][nd], then nd * dh * dw
+// digit bytes.  Digits live in HBM as uint8 [n_digits_total, h, w] (MNIST: 47 MB).
 #include "vs_common.h"
+#include "vs_mmnist_bounce_core.h"
 
 namespace {
 
 constexpr int MM_MAXD = 8;          // digits per video (reference default 2)
+constexpr int MM_AWAY = 1 << 24;    // r - MM_AWAY < 0 for every row of a frame that passed mm_plan's size checks
 
-struct Traj { double sx, sy; int dx, dy; };
+// the output forms: raw values 0..255 as uint8 / fp32 (the test file), values / 255 as fp32 / a 16-bit type (training)
+enum { MM_U8, MM_F32, MM_NORM32, MM_NORM16 };
+__host__ __device__ constexpr int mm_esize(int form) { return form == MM_U8 ? 1 : form == MM_NORM16 ? 2 : 4; }
 
-// moving_mnist.py:257-299: intersection of the line y = a x + b with a vertical / horizontal border
-__device__ __forceinline__ bool inter_x(double a, double b, double x_lim, double lo, double hi, double eps, double& cx, double& cy) {
-    const double y = a * x_lim + b;
-    cx = x_lim; cy = y;
-    return (y >= lo - eps) && (y <= hi + eps);
+// what the two kernels share: sizes, the split of a video over workgroups (mm_plan) and the output.  od: VS_BF16 / VS_F16 for MM_NORM16
+struct MmJob {
+    const unsigned char* digits;
+    int64_t n_total;
+    int dh, dw, n_videos, nd, T, F, chunks, chunk_len;
+    void* frames;
+    int od;
+    int64_t st, sv;
+};
+
+// the workgroup's share: video v, frames t0 .. t0 + len - 1, and its LDS
+struct MmSlice {
+    int v, t0, len;
+    int2* pos;
+    unsigned char* dig;
+};
+
+__device__ __forceinline__ MmSlice mm_slice(const MmJob& j, int2* lds) {
+    MmSlice s;
+    s.v = blockIdx.x / j.chunks;
+    s.t0 = (blockIdx.x - s.v * j.chunks) * j.chunk_len;
+    s.len = j.T - s.t0 < j.chunk_len ? j.T - s.t0 : j.chunk_len;
+    s.pos = lds;
+    s.dig = reinterpret_cast<unsigned char*>(lds + (size_t)j.chunk_len * j.nd);
+    return s;
 }
-__device__ __forceinline__ bool inter_y(double a, double b, double y_lim, double lo, double hi, double eps, double& cx, double& cy) {
-    const double x = (y_lim - b) / a;
-    cx = x; cy = y_lim;
-    return (x >= lo - eps) && (x <= hi + eps);
-}
 
-// moving_mnist.py:177-255 (`_process_collision`, deterministic: the speed is mirrored, never redrawn)
-__device__ void process_collision(Traj& s, double x_min, double x_max, double y_min, double y_max) {
-    const double eps = 1e-8;
-    bool left = s.sx < x_min - eps, upper = s.sy < y_min - eps, right = s.sx > x_max + eps, bottom = s.sy > y_max + eps;
-    int guard = 0;
-    while ((left || right || upper || bottom) && ++guard < 64) {
-        double cx = 0.0, cy = 0.0;
-        if (s.dx == 0) {
-            cx = s.sx; cy = upper ? y_min : y_max;
-        } else if (s.dy == 0) {
-            cx = left ? x_min : x_max; cy = s.sy;
-        } else {
-            const double a = (double)s.dy / (double)s.dx;
-            const double b = s.sy - a * s.sx;
-            double tx, ty;
-            if (left) { left = inter_x(a, b, x_min, y_min, y_max, eps, tx, ty); if (left) { cx = tx; cy = ty; } }
-            if (right) { right = inter_x(a, b, x_max, y_min, y_max, eps, tx, ty); if (right) { cx = tx; cy = ty; } }
-            if (upper) { upper = inter_y(a, b, y_min, x_min, x_max, eps, tx, ty); if (upper) { cx = tx; cy = ty; } }
-            if (bottom) { bottom = inter_y(a, b, y_max, x_min, x_max, eps, tx, ty); if (bottom) { cx = tx; cy = ty; } }
-        }
-        const double p = s.dx != 0 ? (s.sx - cx) / (double)s.dx : (s.sy - cy) / (double)s.dy;
-        if (left) s.dx = abs(s.dx);
-        if (right) s.dx = -abs(s.dx);
-        if (upper) s.dy = abs(s.dy);
-        if (bottom) s.dy = -abs(s.dy);
-        s.sx = cx + (double)s.dx * p;
-        s.sy = cy + (double)s.dy * p;
-        left = s.sx < x_min - eps; upper = s.sy < y_min - eps; right = s.sx > x_max + eps; bottom = s.sy > y_max + eps;
+// step 2: idx[d] is the index of the video's digit d
+__device__ __forceinline__ void mm_load_digits(const MmJob& j, unsigned char* dig, const int* idx, int idx_step) {
+    const int dsz = j.dh * j.dw;
+    for (int i = threadIdx.x; i < j.nd * dsz; i += 256) {
+        const int d = i / dsz;
+        const int64_t n = idx[d * idx_step];
+        dig[i] = (n >= 0 && n < j.n_total) ? j.digits[n * dsz + (i - d * dsz)] : (unsigned char)0;
     }
 }
 
-// grid (T, B): one workgroup per frame.  init[b][d] = (digit index, sx, sy, dx, dy)
-__global__ __launch_bounds__(256) void moving_mnist_kernel(const unsigned char* __restrict__ digits, int dh, int dw, const int* __restrict__ init,
-                                                           int nd, int T, int F, void* out, int od) {
-    __shared__ int pos[MM_MAXD][3];            // digit index, row offset, column offset of this frame
-    const int t = blockIdx.x, b = blockIdx.y;
-    if ((int)threadIdx.x < nd) {
-        const int* q = init + ((int64_t)b * nd + threadIdx.x) * 5;
-        Traj s{(double)q[1], (double)q[2], q[3], q[4]};
-        const double x_max = (double)(F - dh), y_max = (double)(F - dw);
-        int px = 0, py = 0;
-        for (int tt = 0; tt <= t; ++tt) {      // moving_mnist.py:166-175: bounce, record the rounded position, then move
-            process_collision(s, 0.0, x_max, 0.0, y_max);
-            px = (int)rint(s.sx); py = (int)rint(s.sy);
-            s.sy += (double)s.dy;
-            s.sx += (double)s.dx;
-        }
-        pos[threadIdx.x][0] = q[0]; pos[threadIdx.x][1] = px; pos[threadIdx.x][2] = py;
-    }
-    __syncthreads();
-    const int64_t base = ((int64_t)b * T + t) * F * F;
-    for (int i = threadIdx.x; i < F * F; i += 256) {
-        const int r = i / F, c = i - r * F;
-        float v = 0.f;
-        for (int d = 0; d < nd; ++d) {
-            const int rr = r - pos[d][1], cc = c - pos[d][2];
-            if (rr >= 0 && rr < dh && cc >= 0 && cc < dw) v += (float)digits[((int64_t)pos[d][0] * dh + rr) * dw + cc];
-        }
-        v = v > 255.f ? 255.f : v;
-        vs_st(out, od, base + i, v / 255.f);
-    }
-}
-
-// ---- the Moving-MNIST TEST set (reference: preprocessing/mnist/make_test_set.py:58-91) ---------------------------------------------------
-// Thousands of long videos (5 000 x 100 frames), raw bytes instead of normalised floats, the latents (rounded position and speed per frame)
-// as a second output, and the file's time-major layout.  One workgroup per (video, chunk of `chunk_len` frames); with enough videos a chunk
-// is the whole video, so each trajectory is walked exactly once:
-//   1. thread d < nd walks digit d's trajectory with the arithmetic of moving_mnist_kernel (frames before the chunk are replayed, not
-//      recorded) and leaves (row, column) per frame in LDS and (row, column, row speed, column speed) in `latents`;
-//   2. the workgroup copies its nd digit images into LDS once (a digit index outside [0, n_digits_total) is never read: zeros);
-//   3. per frame every thread builds G consecutive pixels (16 bytes: G = 16 as uint8, 4 as fp32) from the LDS digits and stores them as one
-//      16-byte vector: at F = 64 as uint8 a frame is exactly one store per thread, a wave writes 1 KiB contiguous.  When the G pixels
-//      share a row (F % G == 0) the row is tested once per digit, and most rows miss a digit.
-// Frame (t, v) starts at element t * st + v * sv.  VEC needs F * F % G == 0 and 16-byte aligned frame starts (the entry point decides);
-// otherwise the same arithmetic goes element by element.  LDS: int2 pos[chunk_len][nd], then nd * dh * dw digit bytes.
 __device__ __forceinline__ unsigned mm_pixel(const int2* pos, const unsigned char* dig, int nd, int dh, int dw, int r, int c) {
     unsigned v = 0;
     for (int d = 0; d < nd; ++d) {
@@ -120,19 +81,20 @@ __device__ __forceinline__ unsigned mm_pixel(const int2* pos, const unsigned cha
     return v > 255u ? 255u : v;
 }
 
-// Step 3 for one workgroup: frames t0 .. t0 + len - 1 of video v from the positions and digit images in LDS.  Shared by the walking kernel
-// and the placing kernel below, which differ only in where the positions come from.
-template <bool FP32, bool VEC>
-__device__ __forceinline__ void mm_compose(const int2* pos, const unsigned char* dig, int nd, int dh, int dw, int F, int len, int t0, int v,
-                                           void* frames, int64_t st, int64_t sv) {
-    const int tid = threadIdx.x;
+template <int OUT>
+__device__ __forceinline__ float mm_value(unsigned px) { return OUT == MM_NORM32 || OUT == MM_NORM16 ? __fdiv_rn((float)px, 255.f) : (float)px; }
+
+// step 3 for one workgroup, from the positions and digit images in LDS
+template <int OUT, bool VEC>
+__device__ __forceinline__ void mm_compose(const MmJob& j, const MmSlice& s) {
+    const int tid = threadIdx.x, nd = j.nd, dh = j.dh, dw = j.dw, F = j.F;
     const int FF = F * F;
     if constexpr (VEC) {
-        constexpr int G = FP32 ? 4 : 16;
+        constexpr int G = 16 / mm_esize(OUT);
         const int gpf = FF / G;
-        for (int g = tid; g < len * gpf; g += 256) {
+        for (int g = tid; g < s.len * gpf; g += 256) {
             const int f = g / gpf, p0 = (g - f * gpf) * G;
-            const int2* pf = pos + f * nd;
+            const int2* pf = s.pos + f * nd;
             int r = p0 / F, c = p0 - r * F;
             unsigned px[G];
             if (F % G == 0) {                        // the G pixels share a row: one row test per digit, and most rows miss a digit
@@ -141,7 +103,7 @@ __device__ __forceinline__ void mm_compose(const int2* pos, const unsigned char*
                 for (int d = 0; d < nd; ++d) {
                     const int rr = r - pf[d].x, c0 = c - pf[d].y;
                     if ((unsigned)rr >= (unsigned)dh || c0 >= dw || c0 + G <= 0) continue;
-                    const unsigned char* row = dig + (d * dh + rr) * dw;
+                    const unsigned char* row = s.dig + (d * dh + rr) * dw;
 #pragma unroll
                     for (int k = 0; k < G; ++k)
                         if ((unsigned)(c0 + k) < (unsigned)dw) px[k] += row[c0 + k];
@@ -151,103 +113,88 @@ __device__ __forceinline__ void mm_compose(const int2* pos, const unsigned char*
             } else {
 #pragma unroll
                 for (int k = 0; k < G; ++k) {
-                    px[k] = mm_pixel(pf, dig, nd, dh, dw, r, c);
+                    px[k] = mm_pixel(pf, s.dig, nd, dh, dw, r, c);
                     if (++c == F) { c = 0; ++r; }
                 }
             }
-            const int64_t o = (int64_t)(t0 + f) * st + (int64_t)v * sv + p0;
-            if constexpr (FP32) {
-                const f32x4 w = {(float)px[0], (float)px[1], (float)px[2], (float)px[3]};
-                *reinterpret_cast<f32x4*>((float*)frames + o) = w;
-            } else {
+            const int64_t o = (int64_t)(s.t0 + f) * j.st + (int64_t)s.v * j.sv + p0;
+            if constexpr (OUT == MM_U8) {
                 u32x4 w;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] = px[4 * j] | (px[4 * j + 1] << 8) | (px[4 * j + 2] << 16) | (px[4 * j + 3] << 24);
-                *reinterpret_cast<u32x4*>((unsigned char*)frames + o) = w;
+                for (int q = 0; q < 4; ++q) w[q] = px[4 * q] | (px[4 * q + 1] << 8) | (px[4 * q + 2] << 16) | (px[4 * q + 3] << 24);
+                *reinterpret_cast<u32x4*>((unsigned char*)j.frames + o) = w;
+            } else if constexpr (OUT == MM_NORM16) {
+                u16x8 w;
+#pragma unroll
+                for (int k = 0; k < G; ++k) w[k] = vs_f2h(mm_value<OUT>(px[k]), j.od);
+                *reinterpret_cast<u16x8*>((unsigned short*)j.frames + o) = w;
+            } else {
+                const f32x4 w = {mm_value<OUT>(px[0]), mm_value<OUT>(px[1]), mm_value<OUT>(px[2]), mm_value<OUT>(px[3])};
+                *reinterpret_cast<f32x4*>((float*)j.frames + o) = w;
             }
         }
     } else {
-        for (int i = tid; i < len * FF; i += 256) {
+        for (int i = tid; i < s.len * FF; i += 256) {
             const int f = i / FF, p = i - f * FF;
             const int r = p / F, c = p - r * F;
-            const unsigned val = mm_pixel(pos + f * nd, dig, nd, dh, dw, r, c);
-            const int64_t o = (int64_t)(t0 + f) * st + (int64_t)v * sv + p;
-            if constexpr (FP32) ((float*)frames)[o] = (float)val;
-            else ((unsigned char*)frames)[o] = (unsigned char)val;
+            const unsigned val = mm_pixel(s.pos + f * nd, s.dig, nd, dh, dw, r, c);
+            const int64_t o = (int64_t)(s.t0 + f) * j.st + (int64_t)s.v * j.sv + p;
+            if constexpr (OUT == MM_U8) ((unsigned char*)j.frames)[o] = (unsigned char)val;
+            else if constexpr (OUT == MM_NORM16) ((unsigned short*)j.frames)[o] = vs_f2h(mm_value<OUT>(val), j.od);
+            else ((float*)j.frames)[o] = mm_value<OUT>(val);
         }
     }
 }
 
-template <bool FP32, bool VEC>
-__global__ __launch_bounds__(256) void moving_mnist_testset_kernel(const unsigned char* __restrict__ digits, int64_t n_total, int dh, int dw,
-                                                                   const int* __restrict__ init, int n_videos, int nd, int T, int F, int chunks,
-                                                                   int chunk_len, void* frames, int64_t st, int64_t sv, int* latents) {
+// The WALK loader.  init [n_videos][nd][5] = (digit index, start row, start column, row speed, column speed); latents
+// [T][n_videos][nd][4] or null.
+template <int OUT, bool VEC>
+__global__ __launch_bounds__(256) void mm_walk_kernel(MmJob j, const int* __restrict__ init, int* latents) {
     extern __shared__ int2 mm_lds[];
-    const int v = blockIdx.x / chunks, t0 = (blockIdx.x - v * chunks) * chunk_len;
-    const int len = T - t0 < chunk_len ? T - t0 : chunk_len;
-    int2* pos = mm_lds;
-    unsigned char* dig = reinterpret_cast<unsigned char*>(mm_lds + (size_t)chunk_len * nd);
-    const int tid = threadIdx.x, dsz = dh * dw;
-    if (tid < nd) {
-        const int* q = init + ((int64_t)v * nd + tid) * 5;
-        Traj s{(double)q[1], (double)q[2], q[3], q[4]};
-        const double x_max = (double)(F - dh), y_max = (double)(F - dw);
-        for (int tt = 0; tt < t0 + len; ++tt) {      // moving_mnist.py:166-175: bounce, record the rounded position and the speed, then move
-            process_collision(s, 0.0, x_max, 0.0, y_max);
-            if (tt >= t0) {
-                const int px = (int)rint(s.sx), py = (int)rint(s.sy);
-                pos[(tt - t0) * nd + tid] = make_int2(px, py);
-                if (latents) {
-                    int* l = latents + (((int64_t)tt * n_videos + v) * nd + tid) * 4;
-                    l[0] = px; l[1] = py; l[2] = s.dx; l[3] = s.dy;
-                }
+    const MmSlice s = mm_slice(j, mm_lds);
+    const int d = threadIdx.x;
+    const int* mine = init + (int64_t)s.v * j.nd * 5;
+    if (d < j.nd) {
+        const int* q = mine + d * 5;
+        vsw_walk_deterministic(j.F - j.dh, j.F - j.dw, q[1], q[2], q[3], q[4], s.t0, s.t0 + s.len, [&](int t, const int32_t* row) {
+            s.pos[(t - s.t0) * j.nd + d] = make_int2(row[0], row[1]);
+            if (latents) {
+                int* l = latents + (((int64_t)t * j.n_videos + s.v) * j.nd + d) * 4;
+                l[0] = row[0]; l[1] = row[1]; l[2] = row[2]; l[3] = row[3];
             }
-            s.sy += (double)s.dy;
-            s.sx += (double)s.dx;
-        }
+        });
     }
-    for (int i = tid; i < nd * dsz; i += 256) {
-        const int d = i / dsz;
-        const int64_t idx = init[((int64_t)v * nd + d) * 5];
-        dig[i] = (idx >= 0 && idx < n_total) ? digits[idx * dsz + (i - d * dsz)] : (unsigned char)0;
-    }
+    mm_load_digits(j, s.dig, mine, 5);
     __syncthreads();
-    mm_compose<FP32, VEC>(pos, dig, nd, dh, dw, F, len, t0, v, frames, st, sv);
+    mm_compose<OUT, VEC>(j, s);
 }
 
-// The same frames from STORED positions (the stochastic test set: its trajectories consume the random stream as they go, so one workgroup
-// walks them all first, vs_mmnist_walk.hip).  Step 1 becomes a copy: the workgroup's slice of positions [T][n_videos][nd][2] goes to LDS.
-// A digit whose index is outside [0, n_total), or which is not wholly inside the frame at a frame of the slice, raises *bad and gets a
-// position that no pixel of any frame meets, so it is not drawn there; nothing is read outside `digits` or `positions`.
-constexpr int MM_AWAY = 1 << 24;    // r - MM_AWAY < 0 for every row of a frame that passed the entry point's size checks
-
-template <bool FP32, bool VEC>
-__global__ __launch_bounds__(256) void moving_mnist_testset_place_kernel(const unsigned char* __restrict__ digits, int64_t n_total, int dh, int dw,
-                                                                         const int* __restrict__ positions, const int* __restrict__ digit_idx,
-                                                                         int n_videos, int nd, int T, int F, int chunks, int chunk_len, void* frames,
-                                                                         int64_t st, int64_t sv, int* bad) {
+// The TABLE loader.  positions [>= T][n_seq][nd][2]; row v of idx [n_videos][idx_row] names the video's digits, after its sequence if
+// idx_seq (vs_moving_mnist_place's desc), else the sequence is v itself.  Nothing is read outside `digits` or `positions`.
+template <int OUT, bool VEC>
+__global__ __launch_bounds__(256) void mm_table_kernel(MmJob j, const int* __restrict__ positions, int n_seq, const int* __restrict__ idx,
+                                                       int idx_row, int idx_seq, int* bad) {
     extern __shared__ int2 mm_lds[];
-    const int v = blockIdx.x / chunks, t0 = (blockIdx.x - v * chunks) * chunk_len;
-    const int len = T - t0 < chunk_len ? T - t0 : chunk_len;
-    int2* pos = mm_lds;
-    unsigned char* dig = reinterpret_cast<unsigned char*>(mm_lds + (size_t)chunk_len * nd);
-    const int tid = threadIdx.x, dsz = dh * dw;
-    for (int i = tid; i < len * nd; i += 256) {
-        const int f = i / nd, d = i - f * nd;
-        const int* q = positions + (((int64_t)(t0 + f) * n_videos + v) * nd + d) * 2;
-        const int px = q[0], py = q[1];
-        const int64_t idx = digit_idx[(int64_t)v * nd + d];
-        const bool ok = idx >= 0 && idx < n_total && px >= 0 && py >= 0 && px <= F - dh && py <= F - dw;
+    const MmSlice s = mm_slice(j, mm_lds);
+    const int* mine = idx + (int64_t)s.v * idx_row;
+    const int seq = idx_seq ? mine[0] : s.v;
+    mine += idx_seq;
+    for (int i = threadIdx.x; i < s.len * j.nd; i += 256) {
+        const int f = i / j.nd, d = i - f * j.nd;
+        const int64_t n = mine[d];
+        bool ok = seq >= 0 && seq < n_seq && n >= 0 && n < j.n_total;
+        int px = 0, py = 0;
+        if (ok) {
+            const int* q = positions + (((int64_t)(s.t0 + f) * n_seq + seq) * j.nd + d) * 2;
+            px = q[0]; py = q[1];
+            ok = px >= 0 && py >= 0 && px <= j.F - j.dh && py <= j.F - j.dw;
+        }
         if (!ok && bad) *bad = 1;
-        pos[i] = ok ? make_int2(px, py) : make_int2(MM_AWAY, MM_AWAY);
+        s.pos[i] = ok ? make_int2(px, py) : make_int2(MM_AWAY, MM_AWAY);
     }
-    for (int i = tid; i < nd * dsz; i += 256) {
-        const int d = i / dsz;
-        const int64_t idx = digit_idx[(int64_t)v * nd + d];
-        dig[i] = (idx >= 0 && idx < n_total) ? digits[idx * dsz + (i - d * dsz)] : (unsigned char)0;
-    }
+    mm_load_digits(j, s.dig, mine, 1);
     __syncthreads();
-    mm_compose<FP32, VEC>(pos, dig, nd, dh, dw, F, len, t0, v, frames, st, sv);
+    mm_compose<OUT, VEC>(j, s);
 }
 
 // ---- 3D Chairs: batch gather from the decoded views resident in HBM (data/chairs.py:45-64) ----------------------------------------
@@ -399,80 +346,105 @@ extern "C" int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int vi
     return VS_OK;
 }
 
-extern "C" int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
-                                     int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream) {
-    VS_CHECK_ARG(digits && init && out && n_digits_total > 0 && digit_h > 0 && digit_w > 0 && batch > 0 && seq_len > 0, "vs_moving_mnist_batch: bad argument");
-    VS_CHECK_ARG(num_digits >= 1 && num_digits <= MM_MAXD, "vs_moving_mnist_batch: 1..%d digits per video", MM_MAXD);
-    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "vs_moving_mnist_batch: the digit does not fit the frame");
-    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "vs_moving_mnist_batch: bad out_dtype");
-    hipLaunchKernelGGL(moving_mnist_kernel, dim3((unsigned)seq_len, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, digits, digit_h, digit_w, init,
-                       num_digits, seq_len, frame_size, out, out_dtype);
-    VS_CHECK_LAUNCH("vs_moving_mnist_batch");
-    return VS_OK;
-}
-
 namespace {
 
-// What vs_moving_mnist_testset and vs_moving_mnist_testset_place check and decide alike: the sizes, the strides, the split of a video over
-// workgroups, the LDS of a workgroup and whether frame starts allow 16-byte stores.  VS_OK, or the code vs_fail returned (nothing launched).
-struct MmTestsetPlan { int chunks, chunk_len, vec; size_t lds; };
+// What the four Moving-MNIST entry points check and decide alike: the sizes, the strides, the split of a video over workgroups, the LDS of
+// a workgroup and whether frame starts allow 16-byte stores.  Fills j.chunks and j.chunk_len.  VS_OK, or the code vs_fail returned.
+struct MmPlan { int vec; size_t lds; unsigned grid; };
 
-int mm_testset_plan(const char* me, int64_t n_digits_total, int digit_h, int digit_w, int n_videos, int num_digits, int seq_len, int frame_size,
-                    const void* frames, int frames_fp32, int64_t st, int64_t sv, MmTestsetPlan& plan) {
-    VS_CHECK_ARG(n_digits_total > 0 && digit_h > 0 && digit_w > 0 && n_videos > 0 && seq_len > 0, "%s: sizes must be positive", me);
-    VS_CHECK_ARG(num_digits >= 1 && num_digits <= MM_MAXD, "%s: 1..%d digits per video (got %d)", me, MM_MAXD, num_digits);
-    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "%s: a %d x %d digit does not fit a frame of %d", me, digit_h, digit_w, frame_size);
-    const int64_t FF = (int64_t)frame_size * frame_size;
+// The test set: few videos get several workgroups each, over chunks of >= 8 frames, until about two workgroups per CU are in flight.
+// Training batches are few short videos (B = 128 x 15 frames) and one launch is all the GPU has to do: chunks from one frame up until
+// about eight workgroups per CU, which at B = 128 is one workgroup per frame (fp32: 16.7 us, against 19.7 us with chunks of 4 and 27.2 us
+// with chunks of 8, profiles/mmnist_render_timing.md).
+constexpr int MM_TESTSET_CHUNK = 8, MM_TESTSET_GROUPS = 512, MM_TRAIN_CHUNK = 1, MM_TRAIN_GROUPS = 2048;
+
+int mm_plan(const char* me, MmJob& j, int form, int chunk_min, int groups, MmPlan& plan) {
+    VS_CHECK_ARG(j.n_total > 0 && j.dh > 0 && j.dw > 0 && j.n_videos > 0 && j.T > 0, "%s: sizes must be positive", me);
+    VS_CHECK_ARG(j.nd >= 1 && j.nd <= MM_MAXD, "%s: 1..%d digits per video (got %d)", me, MM_MAXD, j.nd);
+    VS_CHECK_ARG(j.F >= j.dh && j.F >= j.dw, "%s: a %d x %d digit does not fit a frame of %d", me, j.dh, j.dw, j.F);
+    const int64_t FF = (int64_t)j.F * j.F, st = j.st, sv = j.sv;
     // frames must not overlap: the faster-varying index steps over whole frames, the slower one over the whole extent of the faster one
     bool apart = st > 0 && sv > 0;
-    if (apart && seq_len > 1 && n_videos > 1) apart = st <= sv ? (st >= FF && sv >= (int64_t)seq_len * st) : (sv >= FF && st >= (int64_t)n_videos * sv);
-    else if (apart && seq_len > 1) apart = st >= FF;
-    else if (apart && n_videos > 1) apart = sv >= FF;
-    VS_CHECK_ARG(apart, "%s: strides (%lld, %lld) make the %d x %d frames of %lld elements overlap", me, (long long)st, (long long)sv, seq_len,
-                 n_videos, (long long)FF);
-    // few videos: several workgroups per video, each over a chunk of >= 8 frames, until about two workgroups per CU are in flight
+    if (apart && j.T > 1 && j.n_videos > 1) apart = st <= sv ? (st >= FF && sv >= (int64_t)j.T * st) : (sv >= FF && st >= (int64_t)j.n_videos * sv);
+    else if (apart && j.T > 1) apart = st >= FF;
+    else if (apart && j.n_videos > 1) apart = sv >= FF;
+    VS_CHECK_ARG(apart, "%s: strides (%lld, %lld) make the %d x %d frames of %lld elements overlap", me, (long long)st, (long long)sv, j.T,
+                 j.n_videos, (long long)FF);
     int chunks = 1;
-    if (n_videos < 512) {
-        const int64_t want = vs_cdiv(512, n_videos), most = vs_cdiv(seq_len, 8);
+    if (j.n_videos < groups) {
+        const int64_t want = vs_cdiv(groups, j.n_videos), most = vs_cdiv(j.T, chunk_min);
         chunks = (int)(want < most ? want : most);
     }
-    const int chunk_len = (int)vs_cdiv(seq_len, chunks);
-    chunks = (int)vs_cdiv(seq_len, chunk_len);
-    VS_CHECK_ARG((int64_t)chunk_len * FF < (1ll << 31) && (int64_t)n_videos * chunks < (1ll << 31),
-                 "%s: %d frames of %d x %d per workgroup, or %d x %d workgroups, exceed 2^31", me, chunk_len, frame_size, frame_size, n_videos, chunks);
-    const size_t table = (size_t)chunk_len * num_digits * sizeof(int2), images = (size_t)num_digits * digit_h * digit_w;
+    j.chunk_len = (int)vs_cdiv(j.T, chunks);
+    j.chunks = (int)vs_cdiv(j.T, j.chunk_len);
+    VS_CHECK_ARG((int64_t)j.chunk_len * FF < (1ll << 31) && (int64_t)j.n_videos * j.chunks < (1ll << 31),
+                 "%s: %d frames of %d x %d per workgroup, or %d x %d workgroups, exceed 2^31", me, j.chunk_len, j.F, j.F, j.n_videos, j.chunks);
+    const size_t table = (size_t)j.chunk_len * j.nd * sizeof(int2), images = (size_t)j.nd * j.dh * j.dw;
     if (table + images > 64 * 1024)
         return vs_fail(VS_ERR_UNSUPPORTED, "%s: the position table (%d frames x %d digits: %zu B) and the digit images (%zu B) exceed the 65536 B "
-                       "of LDS of a workgroup", me, chunk_len, num_digits, table, images);
-    const int esize = frames_fp32 ? 4 : 1;
-    plan.chunks = chunks;
-    plan.chunk_len = chunk_len;
-    plan.vec = FF % (16 / esize) == 0 && (uintptr_t)frames % 16 == 0 && (st * esize) % 16 == 0 && (sv * esize) % 16 == 0;
+                       "of LDS of a workgroup", me, j.chunk_len, j.nd, table, images);
+    const int esize = mm_esize(form);
+    plan.vec = FF % (16 / esize) == 0 && (uintptr_t)j.frames % 16 == 0 && (st * esize) % 16 == 0 && (sv * esize) % 16 == 0;
     plan.lds = table + images;
+    plan.grid = (unsigned)((int64_t)j.n_videos * j.chunks);
     return VS_OK;
 }
 
+int mm_norm_form(int out_dtype) { return out_dtype == VS_F32 ? MM_NORM32 : MM_NORM16; }
+
 }  // namespace
+
+// KERNEL<form, plan.vec> on the plan's grid
+#define MM_CASE(KERNEL, FORM, VEC, ...) \
+    case 2 * FORM + VEC: hipLaunchKernelGGL((KERNEL<FORM, VEC != 0>), dim3(plan.grid), dim3(256), plan.lds, (hipStream_t)stream, __VA_ARGS__); break;
+#define MM_LAUNCH(KERNEL, ...)                                                                                                      \
+    switch (2 * form + plan.vec) {                                                                                                  \
+        MM_CASE(KERNEL, MM_U8, 0, __VA_ARGS__) MM_CASE(KERNEL, MM_U8, 1, __VA_ARGS__) MM_CASE(KERNEL, MM_F32, 0, __VA_ARGS__)        \
+        MM_CASE(KERNEL, MM_F32, 1, __VA_ARGS__) MM_CASE(KERNEL, MM_NORM32, 0, __VA_ARGS__) MM_CASE(KERNEL, MM_NORM32, 1, __VA_ARGS__) \
+        MM_CASE(KERNEL, MM_NORM16, 0, __VA_ARGS__) MM_CASE(KERNEL, MM_NORM16, 1, __VA_ARGS__)                                        \
+    }                                                                                                                               \
+    VS_CHECK_LAUNCH(me);                                                                                                            \
+    return VS_OK
+
+extern "C" int vs_moving_mnist_batch(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int batch,
+                                     int num_digits, int seq_len, int frame_size, void* out, int out_dtype, void* stream) {
+    const char* me = "vs_moving_mnist_batch";
+    VS_CHECK_ARG(digits && init && out, "%s: null pointer", me);
+    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "%s: bad out_dtype", me);
+    const int64_t FF = (int64_t)frame_size * frame_size;
+    MmJob job = {digits, n_digits_total, digit_h, digit_w, batch, num_digits, seq_len, frame_size, 0, 0, out, out_dtype, FF, seq_len * FF};
+    MmPlan plan;
+    const int form = mm_norm_form(out_dtype), rc = mm_plan(me, job, form, MM_TRAIN_CHUNK, MM_TRAIN_GROUPS, plan);
+    if (rc != VS_OK) return rc;
+    MM_LAUNCH(mm_walk_kernel, job, (const int*)init, (int*)nullptr);
+}
+
+extern "C" int vs_moving_mnist_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions, int n_seq,
+                                     int num_digits, const int32_t* desc, int n_videos, int seq_len, int frame_size, void* out, int out_dtype,
+                                     int32_t* bad, void* stream) {
+    const char* me = "vs_moving_mnist_place";
+    VS_CHECK_ARG(digits && positions && desc && out, "%s: null pointer", me);
+    VS_CHECK_ARG(n_seq > 0, "%s: sizes must be positive", me);
+    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "%s: bad out_dtype", me);
+    const int64_t FF = (int64_t)frame_size * frame_size;
+    MmJob job = {digits, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, 0, 0, out, out_dtype, FF, seq_len * FF};
+    MmPlan plan;
+    const int form = mm_norm_form(out_dtype), rc = mm_plan(me, job, form, MM_TRAIN_CHUNK, MM_TRAIN_GROUPS, plan);
+    if (rc != VS_OK) return rc;
+    MM_LAUNCH(mm_table_kernel, job, (const int*)positions, n_seq, (const int*)desc, 1 + num_digits, 1, (int*)bad);
+}
 
 extern "C" int vs_moving_mnist_testset(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* init, int n_videos,
                                        int num_digits, int seq_len, int frame_size, void* frames, int frames_fp32, int64_t frame_stride_t,
                                        int64_t frame_stride_v, int32_t* latents, void* stream) {
     const char* me = "vs_moving_mnist_testset";
     VS_CHECK_ARG(digits && init && frames, "%s: null pointer", me);
-    MmTestsetPlan plan;
-    const int rc = mm_testset_plan(me, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, frames, frames_fp32,
-                                   frame_stride_t, frame_stride_v, plan);
+    MmJob job = {digits, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, 0, 0, frames, 0, frame_stride_t,
+                 frame_stride_v};
+    MmPlan plan;
+    const int form = frames_fp32 ? MM_F32 : MM_U8, rc = mm_plan(me, job, form, MM_TESTSET_CHUNK, MM_TESTSET_GROUPS, plan);
     if (rc != VS_OK) return rc;
-    const dim3 grid((unsigned)((int64_t)n_videos * plan.chunks)), block(256);
-#define MM_TESTSET_LAUNCH(FP, VEC)                                                                                                                    \
-    hipLaunchKernelGGL((moving_mnist_testset_kernel<FP, VEC>), grid, block, plan.lds, (hipStream_t)stream, digits, n_digits_total, digit_h, digit_w, \
-                       (const int*)init, n_videos, num_digits, seq_len, frame_size, plan.chunks, plan.chunk_len, frames, frame_stride_t,             \
-                       frame_stride_v, (int*)latents)
-    if (frames_fp32) { if (plan.vec) MM_TESTSET_LAUNCH(true, true); else MM_TESTSET_LAUNCH(true, false); }
-    else { if (plan.vec) MM_TESTSET_LAUNCH(false, true); else MM_TESTSET_LAUNCH(false, false); }
-#undef MM_TESTSET_LAUNCH
-    VS_CHECK_LAUNCH(me);
-    return VS_OK;
+    MM_LAUNCH(mm_walk_kernel, job, (const int*)init, (int*)latents);
 }
 
 extern "C" int vs_moving_mnist_testset_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions,
@@ -480,18 +452,10 @@ extern "C" int vs_moving_mnist_testset_place(const uint8_t* digits, int64_t n_di
                                              int frames_fp32, int64_t frame_stride_t, int64_t frame_stride_v, int32_t* bad, void* stream) {
     const char* me = "vs_moving_mnist_testset_place";
     VS_CHECK_ARG(digits && positions && digit_idx && frames, "%s: null pointer", me);
-    MmTestsetPlan plan;
-    const int rc = mm_testset_plan(me, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, frames, frames_fp32,
-                                   frame_stride_t, frame_stride_v, plan);
+    MmJob job = {digits, n_digits_total, digit_h, digit_w, n_videos, num_digits, seq_len, frame_size, 0, 0, frames, 0, frame_stride_t,
+                 frame_stride_v};
+    MmPlan plan;
+    const int form = frames_fp32 ? MM_F32 : MM_U8, rc = mm_plan(me, job, form, MM_TESTSET_CHUNK, MM_TESTSET_GROUPS, plan);
     if (rc != VS_OK) return rc;
-    const dim3 grid((unsigned)((int64_t)n_videos * plan.chunks)), block(256);
-#define MM_PLACE_LAUNCH(FP, VEC)                                                                                                                      \
-    hipLaunchKernelGGL((moving_mnist_testset_place_kernel<FP, VEC>), grid, block, plan.lds, (hipStream_t)stream, digits, n_digits_total, digit_h,    \
-                       digit_w, (const int*)positions, (const int*)digit_idx, n_videos, num_digits, seq_len, frame_size, plan.chunks, plan.chunk_len, \
-                       frames, frame_stride_t, frame_stride_v, (int*)bad)
-    if (frames_fp32) { if (plan.vec) MM_PLACE_LAUNCH(true, true); else MM_PLACE_LAUNCH(true, false); }
-    else { if (plan.vec) MM_PLACE_LAUNCH(false, true); else MM_PLACE_LAUNCH(false, false); }
-#undef MM_PLACE_LAUNCH
-    VS_CHECK_LAUNCH(me);
-    return VS_OK;
+    MM_LAUNCH(mm_table_kernel, job, (const int*)positions, n_videos, (const int*)digit_idx, num_digits, 0, (int*)bad);
 }

@@ -1,9 +1,6 @@
-// vs_eval.hip -- the device side of the evaluation scripts (reference: test/mnist/test.py, test/mnist/test_disentanglement.py).
+// vs_eval.hip -- the device side of the evaluation scripts (reference: test/mnist/test.py, test/mnist/test_disentanglement.py).  The
+// content-swap videos are rendered by vs_moving_mnist_place, which lives with the other Moving-MNIST renderers in vs_data.hip.
 //
-//   * vs_moving_mnist_place: the content-swap videos of `SwapDataset.__getitem__` (test_disentanglement.py:66-86).  Digits are added at
-//     the test file's stored trajectory positions (no bouncing to replay), clipped at 255 and divided by 255 -- the arithmetic of
-//     moving_mnist_kernel (vs_data.hip), so the frames are bit-identical to NumPy's `x[...] += img; x[x > 255] = 255; x / 255`.  One
-//     launch renders a whole batch of B x (1 + n!) videos; the host only builds the [V, 1 + nd] descriptor table.
 //   * vs_frame_metrics_multi: per-plane MSE and mean SSIM of one prediction against P candidate targets (the best-of-permutations
 //     scoring of test_disentanglement.py:153-161).  The window, constants and operation order are those of frame_metrics_kernel
 //     (vs_metrics.hip); the prediction plane and its two row-filtered maps stay in LDS across all P targets.
@@ -16,46 +13,9 @@
 
 namespace {
 
-constexpr int PL_MAXD = 8;           // digits per video
 constexpr int MM_WIN = 11;           // SSIM window (vs_metrics.hip)
 
 struct MmWindow { float g[MM_WIN]; };
-
-// grid (T, V): one workgroup per frame.  pos [Tp][n_seq][nd][2] = (row, column) of each object's top-left corner; desc [V][1 + nd] =
-// (sequence, digit of object 0 .. nd-1).  A sequence or digit index out of range, or a digit that would not lie inside the frame, is
-// not drawn and raises *bad (if given): nothing is read or written out of bounds.
-__global__ __launch_bounds__(256) void place_kernel(const unsigned char* __restrict__ digits, int64_t n_digits, int dh, int dw,
-                                                    const int* __restrict__ pos, int n_seq, int nd, const int* __restrict__ desc, int T, int F,
-                                                    void* out, int od, int* bad) {
-    __shared__ int sp[PL_MAXD][3];       // digit index, row offset, column offset (digit index -1: not drawn)
-    const int t = blockIdx.x, v = blockIdx.y;
-    if ((int)threadIdx.x < nd) {
-        const int d = threadIdx.x;
-        const int* q = desc + (int64_t)v * (1 + nd);
-        const int seq = q[0], dig = q[1 + d];
-        int ok = seq >= 0 && seq < n_seq && dig >= 0 && (int64_t)dig < n_digits;
-        int sx = 0, sy = 0;
-        if (ok) {
-            const int* p = pos + (((int64_t)t * n_seq + seq) * nd + d) * 2;
-            sx = p[0]; sy = p[1];
-            ok = sx >= 0 && sy >= 0 && sx + dh <= F && sy + dw <= F;
-        }
-        if (!ok && bad) *bad = 1;
-        sp[d][0] = ok ? dig : -1; sp[d][1] = sx; sp[d][2] = sy;
-    }
-    __syncthreads();
-    const int64_t base = ((int64_t)v * T + t) * F * F;
-    for (int i = threadIdx.x; i < F * F; i += 256) {
-        const int r = i / F, c = i - r * F;
-        float acc = 0.f;
-        for (int d = 0; d < nd; ++d) {
-            const int rr = r - sp[d][1], cc = c - sp[d][2];
-            if (sp[d][0] >= 0 && rr >= 0 && rr < dh && cc >= 0 && cc < dw) acc += (float)digits[((int64_t)sp[d][0] * dh + rr) * dw + cc];
-        }
-        acc = acc > 255.f ? 255.f : acc;
-        vs_st(out, od, base + i, acc / 255.f);
-    }
-}
 
 // one workgroup per prediction plane; loops over the P targets of that plane.  LDS: the prediction [H][W], one target [H][W], the
 // prediction's two row-filtered maps (mu, E[x^2]) [2][H][OW] and the target's three (mu, E[y^2], E[xy]) [3][H][OW] -- the footprint of
@@ -268,21 +228,6 @@ __global__ __launch_bounds__(256) void sst_frame_metrics_kernel(const float* pre
 }
 
 }  // namespace
-
-extern "C" int vs_moving_mnist_place(const uint8_t* digits, int64_t n_digits_total, int digit_h, int digit_w, const int32_t* positions, int n_seq,
-                                     int num_digits, const int32_t* desc, int n_videos, int seq_len, int frame_size, void* out, int out_dtype,
-                                     int32_t* bad, void* stream) {
-    VS_CHECK_ARG(digits && positions && desc && out && n_digits_total > 0 && digit_h > 0 && digit_w > 0 && n_seq > 0 && n_videos > 0 && seq_len > 0,
-                 "vs_moving_mnist_place: bad argument");
-    VS_CHECK_ARG(n_videos < 65536 && seq_len < (1 << 30), "vs_moving_mnist_place: at most 65535 videos per launch");
-    VS_CHECK_ARG(num_digits >= 1 && num_digits <= PL_MAXD, "vs_moving_mnist_place: 1..%d digits per video", PL_MAXD);
-    VS_CHECK_ARG(frame_size >= digit_h && frame_size >= digit_w, "vs_moving_mnist_place: the digit does not fit the frame");
-    VS_CHECK_ARG(vs_dtype_ok(out_dtype), "vs_moving_mnist_place: bad out_dtype");
-    hipLaunchKernelGGL(place_kernel, dim3((unsigned)seq_len, (unsigned)n_videos), dim3(256), 0, (hipStream_t)stream, digits, n_digits_total, digit_h,
-                       digit_w, positions, n_seq, num_digits, desc, seq_len, frame_size, out, out_dtype, (int*)bad);
-    VS_CHECK_LAUNCH("vs_moving_mnist_place");
-    return VS_OK;
-}
 
 extern "C" int vs_frame_metrics_multi(const float* pred, const float* targets, int64_t batch, int n_targets, int64_t planes_per_sample, int H, int W,
                                       float max_val, float k1, float k2, float sigma, float* mse, float* ssim, void* stream) {

@@ -6,11 +6,10 @@
 //
 // One trajectory: n_pre scalar draws randint(low[j], high[j]) (training: digit index, start row, start column, row speed, column speed;
 // n_pre == 4: the last four alone; n_pre < 4: the start state is row i of a caller's table int32 [n_traj, 4]), then seq_len steps: the
-// collision passes, record (rint(sx), rint(sy), dx, dy), sy += dy, sx += dx.  A collision pass (vsw_pass) is the arithmetic of
-// `process_collision` of csrc/vs_data.hip in double, on the same values in the same order (no contraction into fused multiply-adds),
-// except that between computing p and mirroring the speed it draws dx = randint(-max_speed, max_speed + 1), then dy likewise; that
-// (cx, cy) live across the passes of one call; and that the edge flags which the intersection tests cleared stay cleared for the
-// mirroring.  Passes and steps share one loop (vsw_trajectory).  A draw with high - 1 - low == 0 consumes nothing.
+// collision passes, record (rint(sx), rint(sy), dx, dy), sy += dy, sx += dx.  The walker -- body, collision pass, record, move -- is
+// vs_mmnist_bounce_core.h, which the deterministic sampler of csrc/vs_data.hip shares; this sampler's passes draw dx = randint(-max_speed,
+// max_speed + 1), then dy likewise, between computing p and mirroring the speed (VswRedraw).  Passes and steps share one loop
+// (vsw_trajectory).  A draw with high - 1 - low == 0 consumes nothing.
 //
 // Two forms over the same `vsw_trajectory`:
 //   * vsw_walk_serial -- ONE lane walks the trajectories one after the other.  The host's default build and the checker of the other.
@@ -30,10 +29,10 @@
 // column accepts with probability above 1/2); a speculative walk reads raw[o] with o < VSW_WINDOW only.  Rows are stored for t < seq_len,
 // i < n_traj only.  On every non-zero status the state is not advanced (outputs may be partly written, except for VSM_STATUS_POS).
 #pragma once
+#include "vs_mmnist_bounce_core.h"
 #include "vs_mt19937_core.h"
 
 #define VSW_STATUS_BOUNCE 3                         /* a collision pass count above VSW_MAX_PASSES: the state is not advanced */
-#define VSW_MAX_PASSES 64
 #define VSW_DRAW_TRIES 4096
 #define VSW_BLOCKS 4
 #define VSW_WINDOW (VSW_BLOCKS * VSM_N)             /* 2496 outputs */
@@ -150,76 +149,17 @@ VSM_HD int vsw_draw_speeds(VswReader* r, const VswGeom* g, int32_t* pdx, int32_t
     return 0;
 }
 
-VSM_HD int32_t vsw_abs(int32_t v) { return v < 0 ? -v : v; }
-
-// the walker between two collision passes: position, speed, the collision point of the call in progress, the edges that are hit
-struct VswBody {
-    double sx, sy, cx, cy;
-    int32_t dx, dy, passes;
-    bool left, upper, right, bottom;
+// what a collision pass of this sampler does between computing p and mirroring the speed (vs_mmnist_bounce_core.h)
+struct VswRedraw {
+    VswReader* r;
+    const VswGeom* g;
+    VSM_HD int operator()(int32_t* pdx, int32_t* pdy) const { return vsw_draw_speeds(r, g, pdx, pdy); }
 };
-
-// the edges the position lies beyond (moving_mnist.py:196-199, 248-251); with it a new call of the collision function begins or goes on
-VSM_HD void vsw_edges(const VswGeom* g, VswBody* s) {
-    const double eps = 1e-8;
-    s->left = s->sx < 0.0 - eps; s->upper = s->sy < 0.0 - eps; s->right = s->sx > (double)g->x_max + eps; s->bottom = s->sy > (double)g->y_max + eps;
-}
-
-// ONE pass of the while loop of moving_mnist.py:201-251 with deterministic=False (some edge is hit).  left / right exclude each other, and
-// so do upper / bottom (x_max, y_max >= 1), so the reference's four intersection tests are two here, in its order, and its two forms of
-// p one division of the selected operands: the same operations on the same values.  0, VSW_RC_PAST, VSM_STATUS_BUDGET or VSW_STATUS_BOUNCE
-VSM_HD int vsw_pass(const VswGeom* g, VswReader* r, VswBody* s) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-    const double eps = 1e-8, x_min = 0.0, y_min = 0.0, x_max = (double)g->x_max, y_max = (double)g->y_max;
-    if (++s->passes > VSW_MAX_PASSES) return VSW_STATUS_BOUNCE;
-    if (s->dx == 0) {
-        s->cx = s->sx; s->cy = s->upper ? y_min : y_max;
-    } else if (s->dy == 0) {
-        s->cx = s->left ? x_min : x_max; s->cy = s->sy;
-    } else {
-        const double a = (double)s->dy / (double)s->dx;
-        const double b = s->sy - a * s->sx;
-        if (s->left || s->right) {
-            const double x_lim = s->left ? x_min : x_max, y = a * x_lim + b;
-            const bool hit = (y >= y_min - eps) && (y <= y_max + eps);
-            if (s->left) s->left = hit; else s->right = hit;
-            if (hit) { s->cx = x_lim; s->cy = y; }
-        }
-        if (s->upper || s->bottom) {
-            const double y_lim = s->upper ? y_min : y_max, x = (y_lim - b) / a;
-            const bool hit = (x >= x_min - eps) && (x <= x_max + eps);
-            if (s->upper) s->upper = hit; else s->bottom = hit;
-            if (hit) { s->cx = x; s->cy = y_lim; }
-        }
-    }
-    const double p = (s->dx != 0 ? s->sx - s->cx : s->sy - s->cy) / (double)(s->dx != 0 ? s->dx : s->dy);
-    const int rc = vsw_draw_speeds(r, g, &s->dx, &s->dy);
-    if (rc != 0) return rc;
-    if (s->left) s->dx = vsw_abs(s->dx);
-    if (s->right) s->dx = -vsw_abs(s->dx);
-    if (s->upper) s->dy = vsw_abs(s->dy);
-    if (s->bottom) s->dy = -vsw_abs(s->dy);
-    s->sx = s->cx + (double)s->dx * p;
-    s->sy = s->cy + (double)s->dy * p;
-    vsw_edges(g, s);
-    return 0;
-}
-
-// Python's int(round(v)) for a coordinate the collision pass left inside the frame (a NaN, which no stream gives, becomes 0)
-VSM_HD int32_t vsw_round(double v, int32_t hi) {
-    if (!(v >= -1.0 && v <= (double)hi + 1.0)) return 0;
-    return (int32_t)__builtin_rint(v);
-}
 
 // Trajectory i from the reader.  With store != 0 its rows go to pre [n_traj, n_pre], positions [seq_len, n_traj, 2], latents [seq_len,
 // n_traj, 4] (may be null) and desc [n_traj / nd, 1 + nd] (may be null; n_pre == 5).  start: int32 [n_traj, 4], read when n_pre < 4.
 VSM_HD int vsw_trajectory(const VswGeom* g, VswReader* r, int64_t i, int64_t n_traj, const int32_t* start, int store, int32_t* pre,
                           int32_t* positions, int32_t* latents, int32_t* desc, int nd) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
     int32_t q[5] = {0, 0, 0, 0, 0};                 // constant indices only: registers, not scratch
 #if defined(__clang__)
 #pragma unroll
@@ -243,28 +183,27 @@ VSM_HD int vsw_trajectory(const VswGeom* g, VswReader* r, int64_t i, int64_t n_t
         }
     }
     const bool five = g->n_pre == 5, table = g->n_pre < 4;
-    double sx = (double)(table ? start[i * 4] : five ? q[1] : q[0]), sy = (double)(table ? start[i * 4 + 1] : five ? q[2] : q[1]);
-    int32_t dx = table ? start[i * 4 + 2] : five ? q[3] : q[2], dy = table ? start[i * 4 + 3] : five ? q[4] : q[3];
+    const double sx = (double)(table ? start[i * 4] : five ? q[1] : q[0]), sy = (double)(table ? start[i * 4 + 1] : five ? q[2] : q[1]);
+    const int32_t dx = table ? start[i * 4 + 2] : five ? q[3] : q[2], dy = table ? start[i * 4 + 3] : five ? q[4] : q[3];
     // One loop over passes AND steps: a turn is one collision pass while an edge is hit, else record and move.  Lanes of a wave that are at
     // different steps or passes of their trajectories share the turns instead of waiting for the longest collision of every step.
-    VswBody s = {sx, sy, 0.0, 0.0, dx, dy, 0, false, false, false, false};
-    vsw_edges(g, &s);
+    VswBody s = vsw_body(g->x_max, g->y_max, sx, sy, dx, dy);
+    const VswRedraw redraw = {r, g};
     for (int t = 0; t < g->seq_len;) {
         if (s.left || s.right || s.upper || s.bottom) {
-            const int rc = vsw_pass(g, r, &s);
+            if (s.passes >= VSW_MAX_PASSES) return VSW_STATUS_BOUNCE;
+            const int rc = vsw_pass(g->x_max, g->y_max, &s, redraw);
             if (rc != 0) return rc;
             continue;
         }
         if (store) {
-            const int32_t px = vsw_round(s.sx, g->x_max), py = vsw_round(s.sy, g->y_max);
+            int32_t rec[4];
+            vsw_record(g->x_max, g->y_max, &s, rec);
             const int64_t row = (int64_t)t * n_traj + i;
-            positions[row * 2] = px; positions[row * 2 + 1] = py;
-            if (latents) { latents[row * 4] = px; latents[row * 4 + 1] = py; latents[row * 4 + 2] = s.dx; latents[row * 4 + 3] = s.dy; }
+            positions[row * 2] = rec[0]; positions[row * 2 + 1] = rec[1];
+            if (latents) { latents[row * 4] = rec[0]; latents[row * 4 + 1] = rec[1]; latents[row * 4 + 2] = rec[2]; latents[row * 4 + 3] = rec[3]; }
         }
-        s.sy += (double)s.dy;
-        s.sx += (double)s.dx;
-        s.passes = 0; s.cx = 0.0; s.cy = 0.0;       // the next call of the collision function
-        vsw_edges(g, &s);
+        vsw_move(g->x_max, g->y_max, &s);
         ++t;
     }
     return 0;

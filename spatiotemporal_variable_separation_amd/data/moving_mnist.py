@@ -22,8 +22,6 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
-from .._lib import check, dtype_code, require_cuda, stream_ptr
 from .numpy_stream import DeviceRandomState
 
 
@@ -226,14 +224,8 @@ class MovingMNIST:
         """init int32 [B, num_digits, 5] (host array or device tensor) -> videos [B, seq_len, 1, nx, nx] on the device."""
         if not isinstance(init, torch.Tensor):
             init = torch.from_numpy(np.ascontiguousarray(init, dtype=np.int32)).to(self.device, non_blocking=True)
-        require_cuda(init, self.data)
-        B = init.shape[0]
-        out = torch.empty((B, self.seq_len, 1, self.frame_size, self.frame_size), dtype=out_dtype, device=self.device)
-        h, w = self.digit_shape
-        check(_lib.load_library().vs_moving_mnist_batch(self.data.data_ptr(), self.n_source, h, w, init.data_ptr(), B, self.num_digits,
-                                                        self.seq_len, self.frame_size, out.data_ptr(), dtype_code(out), stream_ptr()),
-              'vs_moving_mnist_batch')
-        return out
+        from .. import ops
+        return ops.moving_mnist_batch(self.data, init, self.seq_len, self.frame_size, out_dtype)
 
     def draw_stochastic(self, batch):
         """The stochastic variant's draws AND walks for `batch` consecutive items (moving_mnist.py:119-123, 153-170, 230-234): (desc int32

@@ -2428,6 +2428,21 @@ def sst_frame_metrics(pred, target, consts, day0, zone, zone_range, k1=0.01, k2=
     return mse, ssim
 
 
+def moving_mnist_batch(digits, init, seq_len, frame_size, out_dtype=torch.float32):
+    """Training videos [B, seq_len, 1, F, F] with values in [0, 1] from the draws `init` int32 [B, nd, 5] = (digit index, start row, start
+    column, row speed, column speed) in ONE launch (vs_moving_mnist_batch).  digits uint8 [N, h, w]; both on the device, nothing is read
+    back.  A digit index outside [0, N) draws nothing."""
+    require_cuda(digits, init)
+    if digits.dtype != torch.uint8 or digits.dim() != 3 or init.dtype != torch.int32 or init.dim() != 3 or init.shape[2] != 5:
+        raise _lib.VarsepHipError('moving_mnist_batch: digits uint8 [N, h, w] and init int32 [B, nd, 5] expected')
+    digits, init = digits.contiguous(), init.contiguous()
+    out = torch.empty((init.shape[0], seq_len, 1, frame_size, frame_size), dtype=out_dtype, device=digits.device)
+    check(_lib.load_library().vs_moving_mnist_batch(digits.data_ptr(), digits.shape[0], digits.shape[1], digits.shape[2], init.data_ptr(),
+                                                    init.shape[0], init.shape[1], seq_len, frame_size, out.data_ptr(), dtype_code(out),
+                                                    stream_ptr()), 'vs_moving_mnist_batch')
+    return out
+
+
 def moving_mnist_place(digits, positions, desc, seq_len, frame_size, out_dtype=torch.float32, validate=True):
     """Videos [V, seq_len, 1, F, F] with the digits `desc[v, 1 + i]` at `positions[t, desc[v, 0], i]` (vs_moving_mnist_place).
     digits uint8 [N, h, w], positions int32 [T >= seq_len, n_seq, nd, 2], desc int32 [V, 1 + nd], all on the device.
@@ -2479,16 +2494,22 @@ def moving_mnist_testset(digits, init, seq_len, frame_size, *, fp32=False, time_
     device = digits.device
     dev_init = init.to(device).contiguous() if isinstance(init, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(host)).to(device)
     with torch.cuda.device(device):
-        dtype = torch.float32 if fp32 else torch.uint8
-        frames = torch.empty((seq_len, V, 1, F, F) if time_major else (V, seq_len, 1, F, F), dtype=dtype, device=device)
-        latents = torch.empty((seq_len, V, nd, 4), dtype=torch.int32, device=device)
-        stride_t, stride_v = (frames.stride(0), frames.stride(1)) if time_major else (frames.stride(1), frames.stride(0))
-        e0 = _pb()
-        check(_lib.load_library().vs_moving_mnist_testset(digits.data_ptr(), N, h, w, dev_init.data_ptr(), V, nd, seq_len, F, frames.data_ptr(),
-                                                          1 if fp32 else 0, stride_t, stride_v, latents.data_ptr(), stream_ptr()),
-              'vs_moving_mnist_testset')
-        _pe(e0, 'vs_moving_mnist_testset', nbytes=float(frames.numel() * frames.element_size() + latents.numel() * 4))
-    return frames, latents
+        return _mmnist_testset_launch('vs_moving_mnist_testset', seq_len, V, F, fp32, time_major, device, seq_len * V * nd * 16,
+                                      lambda: torch.empty((seq_len, V, nd, 4), dtype=torch.int32, device=device),
+                                      lambda *out: (digits.data_ptr(), N, h, w, dev_init.data_ptr(), V, nd, seq_len, F, *out, stream_ptr()))
+
+
+def _mmnist_testset_launch(entry, T, V, F, fp32, time_major, device, other_bytes, second, args):
+    """What the two test-set renderers do alike -> (frames, second output): the raw frames, uint8 or (fp32) float32, [T, V, 1, F, F]
+    (time_major) or [V, T, 1, F, F]; then second() (the latents / the error word or None); then the entry point `entry` with args(frames
+    pointer, fp32 flag, stride of t, stride of v, pointer of the second output).  other_bytes: what the launch moves beside the frames."""
+    frames = torch.empty((T, V, 1, F, F) if time_major else (V, T, 1, F, F), dtype=torch.float32 if fp32 else torch.uint8, device=device)
+    other = second()
+    stride_t, stride_v = (frames.stride(0), frames.stride(1)) if time_major else (frames.stride(1), frames.stride(0))
+    e0 = _pb()
+    check(getattr(_lib.load_library(), entry)(*args(frames.data_ptr(), 1 if fp32 else 0, stride_t, stride_v, _ptr(other))), entry)
+    _pe(e0, entry, nbytes=float(frames.numel() * frames.element_size() + other_bytes))
+    return frames, other
 
 
 def moving_mnist_testset_place(digits, positions, digit_idx, frame_size, *, fp32=False, time_major=True, validate=True):
@@ -2510,14 +2531,10 @@ def moving_mnist_testset_place(digits, positions, digit_idx, frame_size, *, fp32
     F = int(frame_size)
     device = digits.device
     with torch.cuda.device(device):
-        frames = torch.empty((T, V, 1, F, F) if time_major else (V, T, 1, F, F), dtype=torch.float32 if fp32 else torch.uint8, device=device)
-        bad = torch.zeros((1,), dtype=torch.int32, device=device) if validate else None
-        stride_t, stride_v = (frames.stride(0), frames.stride(1)) if time_major else (frames.stride(1), frames.stride(0))
-        e0 = _pb()
-        check(_lib.load_library().vs_moving_mnist_testset_place(digits.data_ptr(), N, h, w, positions.data_ptr(), digit_idx.data_ptr(), V, nd, T, F,
-                                                                frames.data_ptr(), 1 if fp32 else 0, stride_t, stride_v, _ptr(bad), stream_ptr()),
-              'vs_moving_mnist_testset_place')
-        _pe(e0, 'vs_moving_mnist_testset_place', nbytes=float(frames.numel() * frames.element_size() + positions.numel() * 4))
+        frames, bad = _mmnist_testset_launch(
+            'vs_moving_mnist_testset_place', T, V, F, fp32, time_major, device, positions.numel() * 4,
+            lambda: torch.zeros((1,), dtype=torch.int32, device=device) if validate else None,
+            lambda *out: (digits.data_ptr(), N, h, w, positions.data_ptr(), digit_idx.data_ptr(), V, nd, T, F, *out, stream_ptr()))
     if validate and int(bad.item()):
         raise _lib.VarsepHipError('moving_mnist_testset_place: a digit index is outside [0, %d) or a digit does not lie inside the %d x %d frame'
                                   % (N, F, F))

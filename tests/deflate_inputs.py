@@ -2,13 +2,12 @@
 build of csrc/vs_deflate_core.h and the kernel see the same bytes.  L is the encoder's chunk length, taken from the package."""
 import functools
 import os
-import shutil
 import struct
 import subprocess
 
 import numpy as np
-import pytest
 
+import host_build
 import mmnist_testset_inputs as MI
 import mmnist_testset_ref as MR
 from spatiotemporal_variable_separation_amd import ops
@@ -125,24 +124,8 @@ def bound(n, chunk=None):
 
 
 def compile_host_check(tmp_path):
-    """tests/host/deflate_host_check.cpp with the host compiler: with -fsanitize=address,undefined where that links and starts, without
-    otherwise.  (exe, sanitized)."""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('clang++') or shutil.which('c++')
-    if cxx is None:
-        pytest.fail('no host C++ compiler (g++, clang++ or c++) to compile tests/host/deflate_host_check.cpp')
-    src, exe = os.path.join(ROOT, 'tests', 'host', 'deflate_host_check.cpp'), str(tmp_path / 'deflate_host_check')
-    base = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-o', exe, src]
-    empty, nothing = str(tmp_path / 'empty.bin'), str(tmp_path / 'empty.out')
-    with open(empty, 'wb') as f:
-        f.write(struct.pack('<q', 0))
-    sanitize = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    for extra in (sanitize + ['-static-libasan', '-static-libubsan'], sanitize + ['-static-libsan'], sanitize):
-        r = subprocess.run(base + extra, capture_output=True, text=True)   # the runtimes inside the program where the compiler can
-        if r.returncode == 0 and subprocess.run([exe, empty, nothing, str(L)], capture_output=True).returncode == 0:   # it links AND starts
-            return exe, True
-    r = subprocess.run(base, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, False
+    """tests/host/deflate_host_check.cpp.  (exe, sanitized)."""
+    return host_build.compile_host_check(tmp_path, 'deflate_host_check', start_args=[str(tmp_path / 'empty.out'), str(L)])
 
 
 def run_host_check(exe, arrays, tmp_path, chunk=None, tag='corpus'):

@@ -4,12 +4,12 @@ of RandomState(seed), `pos` set by hand: every key / pos pair is a state of the 
 a number of rows; the oracle is NumPy itself: set_state, then the scalar randint calls in order."""
 import functools
 import os
-import shutil
 import struct
 import subprocess
 
 import numpy as np
-import pytest
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, STATE_WORDS, MAX_COLS = 624, 625, 8
@@ -117,25 +117,9 @@ def numpy_results():
 
 
 def compile_host_check(tmp_path, lanes=False):
-    """tests/host/mt19937_host_check.cpp with the host compiler, the plain build or (lanes=True) the one in which threads play the lanes: with
-    -fsanitize=address,undefined where that links and starts, without otherwise.  (exe, sanitized)."""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('clang++') or shutil.which('c++')
-    if cxx is None:
-        pytest.fail('no host C++ compiler (g++, clang++ or c++) to compile tests/host/mt19937_host_check.cpp')
-    src = os.path.join(ROOT, 'tests', 'host', 'mt19937_host_check.cpp')
-    exe = str(tmp_path / ('mt19937_host_check' + ('_lanes' if lanes else '')))
-    base = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-o', exe, src] + (['-pthread', '-DVSM_HOST_LANES'] if lanes else [])
-    empty, nothing = str(tmp_path / 'empty.bin'), str(tmp_path / 'empty.out')
-    with open(empty, 'wb') as f:
-        f.write(struct.pack('<q', 0))
-    sanitize = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    for extra in (sanitize + ['-static-libasan', '-static-libubsan'], sanitize + ['-static-libsan'], sanitize):
-        r = subprocess.run(base + extra, capture_output=True, text=True)   # the runtimes inside the program where the compiler can
-        if r.returncode == 0 and subprocess.run([exe, empty, nothing, '1'], capture_output=True).returncode == 0:   # it links AND starts
-            return exe, True
-    r = subprocess.run(base, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, False
+    """tests/host/mt19937_host_check.cpp, the plain build or (lanes=True) the one in which threads play the lanes.  (exe, sanitized)."""
+    return host_build.compile_host_check(tmp_path, 'mt19937_host_check', ['-pthread', '-DVSM_HOST_LANES'] if lanes else [],
+                                         [str(tmp_path / 'empty.out'), '1'], '_lanes' if lanes else '')
 
 
 def run_host_check(exe, case_list, tmp_path, lanes=1, tag='cases'):

@@ -5,13 +5,12 @@ start state (the key of RandomState(seed), `pos` set by hand), a geometry, the n
 trajectories; with fewer than four prefix draws every call also has its table of start states."""
 import functools
 import os
-import shutil
 import struct
 import subprocess
 
 import numpy as np
-import pytest
 
+import host_build
 import smnist_ref
 from mmnist_draws_inputs import N, ROOT, STATE_WORDS, random_state_at, start_state, state_words
 
@@ -189,25 +188,10 @@ def desc_nd(c):
 
 
 def compile_host_check(tmp_path, lanes=False):
-    """tests/host/mmnist_walk_host_check.cpp with the host compiler, the plain build (the core's one-lane form) or (lanes=True) the lanes form
-    with threads as lanes: with -fsanitize=address,undefined where that links and starts, without otherwise.  (exe, sanitized)."""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('clang++') or shutil.which('c++')
-    if cxx is None:
-        pytest.fail('no host C++ compiler (g++, clang++ or c++) to compile tests/host/mmnist_walk_host_check.cpp')
-    src = os.path.join(ROOT, 'tests', 'host', 'mmnist_walk_host_check.cpp')
-    exe = str(tmp_path / ('mmnist_walk_host_check' + ('_lanes' if lanes else '')))
-    base = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-ffp-contract=off', '-o', exe, src] + (['-pthread', '-DVSW_HOST_LANES'] if lanes else [])
-    empty, nothing = str(tmp_path / 'empty.bin'), str(tmp_path / 'empty.out')
-    with open(empty, 'wb') as f:
-        f.write(struct.pack('<q', 0))
-    sanitize = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    for extra in (sanitize + ['-static-libasan', '-static-libubsan'], sanitize + ['-static-libsan'], sanitize):
-        r = subprocess.run(base + extra, capture_output=True, text=True)   # the runtimes inside the program where the compiler can
-        if r.returncode == 0 and subprocess.run([exe, empty, nothing, '1'], capture_output=True).returncode == 0:   # it links AND starts
-            return exe, True
-    r = subprocess.run(base, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, False
+    """tests/host/mmnist_walk_host_check.cpp, the plain build (the core's one-lane form) or (lanes=True) the lanes form with threads as lanes.
+    (exe, sanitized)."""
+    return host_build.compile_host_check(tmp_path, 'mmnist_walk_host_check', ['-ffp-contract=off'] + (['-pthread', '-DVSW_HOST_LANES'] if lanes else []),
+                                         [str(tmp_path / 'empty.out'), '1'], '_lanes' if lanes else '')
 
 
 def run_host_check(exe, case_list, tmp_path, lanes=1, tag='cases'):

@@ -5,7 +5,6 @@ the corpus plus 2 000 seeded mutations."""
 import ctypes
 import os
 import re
-import shutil
 import struct
 import subprocess
 import zlib
@@ -14,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import host_build
 import png_inputs as P
 import resample_inputs as I
 import resample_ref as R
@@ -290,23 +290,8 @@ def test_generate_takes_the_decoder_from_the_environment(tmp_path, standins, mon
 
 # ---- the stream logic of the kernel on the host ---------------------------------------------------------------------------------
 def _compile_host_check(tmp_path):
-    """tests/host/inflate_host_check.cpp with the host compiler: with -fsanitize=address,undefined where that links, without otherwise."""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('clang++') or shutil.which('c++')
-    if cxx is None:
-        pytest.fail('no host C++ compiler (g++, clang++ or c++) to compile tests/host/inflate_host_check.cpp')
-    src, exe = os.path.join(ROOT, 'tests', 'host', 'inflate_host_check.cpp'), str(tmp_path / 'inflate_host_check')
-    base = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-Werror', '-o', exe, src]
-    empty = str(tmp_path / 'empty.bin')
-    with open(empty, 'wb') as f:
-        f.write(struct.pack('<q', 0))
-    sanitize = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    for extra in (sanitize + ['-static-libasan', '-static-libubsan'], sanitize + ['-static-libsan'], sanitize):
-        r = subprocess.run(base + extra, capture_output=True, text=True)   # the runtimes inside the program where the compiler can
-        if r.returncode == 0 and subprocess.run([exe, empty], capture_output=True).returncode == 0:      # it links AND starts here
-            return exe, True
-    r = subprocess.run(base, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, False
+    """tests/host/inflate_host_check.cpp.  (exe, sanitized)."""
+    return host_build.compile_host_check(tmp_path, 'inflate_host_check')
 
 
 def test_inflate_core_on_the_host_agrees_with_zlib_on_the_corpus_and_2000_mutations(tmp_path):

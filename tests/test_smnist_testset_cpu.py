@@ -110,8 +110,7 @@ def test_entry_point_is_declared_bound_and_exported():
     assert NAME in _lib.SIGNATURES and len(_lib.SIGNATURES[NAME][1]) == 16
     assert hasattr(_lib.load_library(), NAME)
     source = open(os.path.join(ROOT, 'spatiotemporal_variable_separation_amd', 'csrc', 'vs_data.hip')).read()
-    assert source.count('mm_compose<FP32, VEC>(') == 2                          # one compositing body for the walking and the placing kernel
-
+    assert source.count('mm_compose<OUT, VEC>(') == 2                           # one compositing body for the walking and the placing kernel
 
 def test_entry_point_checks_its_arguments_and_launches_nothing():
     lib = _lib.load_library()

@@ -1,7 +1,7 @@
 """Time of the Moving-MNIST test set on the device at the reference's size (10 000 stand-in digits -> 5 000 videos of 100 frames of 64 x 64,
 seed 42): the one vs_moving_mnist_testset launch as uint8 (the file's layout) and as fp32 (the layout kept in HBM); the same videos through
-vs_moving_mnist_batch (fp32, one workgroup per frame), the launch shape the new kernel replaces; the fill rate of buffers of the outputs'
-sizes (what the frame stores alone could cost); the NumPy restatement of the same set (tests/mmnist_testset_ref.py) on the host; and the
+the training renderer (ops.moving_mnist_batch: normalised fp32, the same kernel body and at this size the same one workgroup per video);
+the fill rate of buffers of the outputs' sizes (what the frame stores alone could cost); the NumPy restatement of the same set (tests/mmnist_testset_ref.py) on the host; and the
 stages of the command line (preprocessing/mnist/make_test_set.py), np.savez_compressed among them.  Every device time is the median over
 REPS windows of LAUNCHES launches between two events, warm.  Writes the note given by --out (default profiles/mmnist_testset_timing.md).
 
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 import mmnist_testset_inputs as I  # noqa: E402
 import mmnist_testset_ref as R  # noqa: E402
-from spatiotemporal_variable_separation_amd import _lib  # noqa: E402
+from spatiotemporal_variable_separation_amd import _lib, ops  # noqa: E402
 from spatiotemporal_variable_separation_amd.data.moving_mnist import draw_test_set, synthetic_digits  # noqa: E402
 from spatiotemporal_variable_separation_amd.preprocessing.mnist import make_test_set  # noqa: E402
 
@@ -59,7 +59,7 @@ def main():
     d_img, d_init = torch.from_numpy(images).to(dev), torch.from_numpy(init).to(dev)
     u8 = torch.empty((T, V, 1, F, F), dtype=torch.uint8, device=dev)
     f32 = torch.empty((V, T, 1, F, F), dtype=torch.float32, device=dev)
-    old = torch.empty((V, T, 1, F, F), dtype=torch.float32, device=dev)
+    old, made = torch.empty((V, T, 1, F, F), dtype=torch.float32, device=dev), {}     # `old`: a buffer of the batch's size for the fill
     lat = torch.empty((T, V, ND, 4), dtype=torch.int32, device=dev)
 
     def testset(out, fp32, st, sv):
@@ -67,8 +67,7 @@ def main():
                                                lat.data_ptr(), _lib.stream_ptr()), 'vs_moving_mnist_testset')
 
     def batch():
-        _lib.check(lib.vs_moving_mnist_batch(d_img.data_ptr(), N_IMAGES, 28, 28, d_init.data_ptr(), V, ND, T, F, old.data_ptr(), _lib.F32,
-                                             _lib.stream_ptr()), 'vs_moving_mnist_batch')
+        made['batch'] = ops.moving_mnist_batch(d_img, d_init, T, F)
 
     lines = []
 
@@ -78,7 +77,7 @@ def main():
 
     rows = [('vs_moving_mnist_testset, uint8 [T, N, 1, F, F]', lambda: testset(u8, 0, V * F * F, F * F), u8),
             ('vs_moving_mnist_testset, fp32 [N, T, 1, F, F]', lambda: testset(f32, 1, F * F, T * F * F), f32),
-            ('vs_moving_mnist_batch, fp32 [N, T, 1, F, F] (one workgroup per frame)', batch, old)]
+            ('vs_moving_mnist_batch, fp32 / 255 [N, T, 1, F, F] (the training renderer)', batch, old)]
     say('# The Moving-MNIST test set at the reference\'s size (one MI355X, `tools/mmnist_testset_bench.py`)')
     say('')
     say('%d stand-in digits -> %d videos x %d frames of %d x %d, %d digits, speed %d, seed %d.  Median (min - max) per launch over %d windows '
@@ -96,11 +95,11 @@ def main():
             % (name, nbytes / 1e9, ms[0], ms[1], ms[2], nbytes / ms[0] / 1e9, fill[0], nbytes / fill[0] / 1e9))
         fn()                                                              # the fill overwrote the frames
     torch.cuda.synchronize()
-    same = bool(torch.equal(old, f32.div(torch.tensor(255., device=dev)))) and bool(torch.equal(f32, u8.transpose(0, 1).float()))
+    same = bool(torch.equal(made['batch'], f32.div(torch.tensor(255., device=dev)))) and bool(torch.equal(f32, u8.transpose(0, 1).float()))
     say('')
-    say('* The three outputs describe the same videos (fp32 = uint8, per-frame kernel = fp32 / 255 bit for bit): %s.' % same)
+    say('* The three outputs describe the same videos (fp32 = uint8, training renderer = fp32 / 255 bit for bit): %s.' % same)
     names = [r[0] for r in rows]
-    say('* One workgroup per video against one per frame (fp32, same bytes written): %.3f ms against %.3f ms = %.2f x.'
+    say('* Raw against normalised fp32 (same bytes written, same launch shape here): %.3f ms against %.3f ms = %.2f x.'
         % (times[names[1]], times[names[2]], times[names[2]] / times[names[1]]))
 
     n_host = min(args.host_videos, V)
