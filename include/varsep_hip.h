@@ -467,17 +467,33 @@ int vs_png_unfilter(const uint8_t* raw, int64_t raw_stride, int64_t n, int H, in
 /* DEFLATE compression on the device (csrc/vs_deflate.hip; the logic is csrc/vs_deflate_core.h): the encoder that writes .npz members from
  * arrays in HBM.  The input is cut into independent chunks; every chunk becomes one stored, fixed or dynamic block (the smallest by exact
  * bit count) with literals and distance-1 run matches, and ends with an empty stored block (00 00 FF FF on a byte boundary), so chunks
- * concatenate by bytes into a raw RFC 1951 stream WITHOUT a final block: the writer of the stream appends 03 00.  There is no window
- * search: content without byte runs is Huffman-coded only.                                                                            */
+ * concatenate by bytes into a raw RFC 1951 stream WITHOUT a final block: the writer of the stream appends 03 00.  Two matchers: RUNS
+ * (vs_deflate_chunks, the default) has no window search -- content without byte runs is Huffman-coded only; WINDOW
+ * (vs_deflate_chunks_window, opt-in; the logic is csrc/vs_deflate_window_core.h) also matches up to 32768 bytes back, across chunk borders. */
 #define VS_DEFLATE_MIN_CHUNK 1024
 #define VS_DEFLATE_MAX_CHUNK 32768    /* also the default (the size against zlib by chunk length) */
 #define VS_DEFLATE_SLOT_EXTRA 10      /* worst case of a chunk: its bytes + 5 of a stored block's header + 5 of the closing marker */
+#define VS_DEFLATE_MAX_HISTORY 32768  /* bytes before src that vs_deflate_chunks_window may match against: DEFLATE's window */
+#define VS_DEFLATE_WINDOW_GROUP_BYTES (4 * VS_DEFLATE_MAX_CHUNK)   /* workspace of one workgroup of vs_deflate_chunks_window */
 /* src [n_bytes] uint8 (no alignment, any length; the last chunk is short) -> chunk c compressed into the slot slots + c * slot_stride, its
  * byte count into sizes[c] (int64 [ceil(n_bytes / chunk_bytes)]).  One wave per chunk; nothing is written past sizes[c] bytes of a slot,
  * and sizes[c] <= chunk length + VS_DEFLATE_SLOT_EXTRA.  n_bytes == 0 launches nothing.  VS_ERR_ARG (and nothing launched) for a null
  * pointer, n_bytes < 0, chunk_bytes outside VS_DEFLATE_MIN_CHUNK .. VS_DEFLATE_MAX_CHUNK, slot_stride < chunk_bytes + VS_DEFLATE_SLOT_EXTRA
  * or more chunks than a grid holds.                                                                                                    */
 int vs_deflate_chunks(const uint8_t* src, int64_t n_bytes, int chunk_bytes, uint8_t* slots, int64_t slot_stride, int64_t* sizes, void* stream);
+/* vs_deflate_chunks with the WINDOW matcher: a token is a literal or a match (length 3..258, distance 1..32768), the distance code is a real
+ * dynamic code, and a match's source may lie before its chunk -- in earlier chunks and in the history_bytes (0 .. VS_DEFLATE_MAX_HISTORY)
+ * bytes BEFORE src, which must be readable and must be what a decoder of the concatenated stream has produced before src[0] (the bytes of
+ * the same array: the next slab of an array passes min(32768, its offset)).  Never before src - history_bytes, never past a chunk's end.
+ * Per chunk the exact bits of the window parse compete with those of the runs parse: sizes[c] is never above vs_deflate_chunks's for the
+ * same bytes, and where the runs parse wins the slot holds vs_deflate_chunks's bytes.  Same slots, sizes and bounds as vs_deflate_chunks.
+ * workspace [workspace_bytes]: VS_DEFLATE_WINDOW_GROUP_BYTES per workgroup (4-byte aligned; the per-position length and distance); the grid
+ * is min(chunks, workspace_bytes / VS_DEFLATE_WINDOW_GROUP_BYTES) workgroups of one wave that loop over the chunks, so the workspace is
+ * bounded by the grid, not by n_bytes, and its size changes no byte of the output.  n_bytes == 0 launches nothing.  VS_ERR_ARG (and
+ * nothing launched) for vs_deflate_chunks's reasons, history_bytes outside 0 .. VS_DEFLATE_MAX_HISTORY, a null or misaligned workspace or
+ * workspace_bytes below one workgroup's.                                                                                              */
+int vs_deflate_chunks_window(const uint8_t* src, int64_t history_bytes, int64_t n_bytes, int chunk_bytes, uint8_t* slots, int64_t slot_stride,
+                             int64_t* sizes, void* workspace, int64_t workspace_bytes, void* stream);
 /* The used part of every slot to its place in one buffer: dst[offsets[c] .. offsets[c] + sizes[c]) = slot c (offsets int64 [n_chunks]: the
  * exclusive prefix sum of sizes).  A chunk whose size is outside 0 .. slot_stride or whose bytes would leave dst [dst_bytes] is not copied.
  * VS_ERR_ARG for a null pointer, n_chunks < 1 or above the grid limit, slot_stride < 1 or dst_bytes < 0.                               */

@@ -153,6 +153,7 @@ SIGNATURES = {
     'vs_inflate_zlib': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     'vs_png_unfilter': (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     'vs_deflate_chunks': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    'vs_deflate_chunks_window': (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     'vs_deflate_pack': (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     'vs_crc32': (_i32, [_vp, _i64, _i64, ctypes.c_uint32, _vp, _vp]),
     'vs_mt19937_randint': (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),

@@ -2573,6 +2573,10 @@ DEFLATE_MIN_CHUNK = 1024          # VS_DEFLATE_MIN_CHUNK
 DEFLATE_SLOT_EXTRA = 10           # VS_DEFLATE_SLOT_EXTRA: worst case of a chunk beyond its own bytes
 DEFLATE_SLAB_BYTES = 256 << 20    # input bytes compressed per pass: slots + packed output stay below about 1 GiB whatever the array's size
 CRC_PIECE = 1 << 16               # bytes per wave of vs_crc32
+DEFLATE_MATCHERS = ('runs', 'window')
+DEFLATE_MAX_HISTORY = 32768       # VS_DEFLATE_MAX_HISTORY: bytes before a slab that the window matcher may match against
+DEFLATE_WINDOW_GROUP_BYTES = 4 * DEFLATE_CHUNK   # VS_DEFLATE_WINDOW_GROUP_BYTES: workspace of one workgroup of vs_deflate_chunks_window
+DEFLATE_WINDOW_GROUPS = 512       # workgroups of vs_deflate_chunks_window at most (one per CU is resident: 256 CUs, two rounds): 64 MiB
 
 
 def _as_bytes(t, what):
@@ -2582,10 +2586,13 @@ def _as_bytes(t, what):
     return t.reshape(-1).view(torch.uint8)
 
 
-def deflate_raw_slabs(t, chunk_bytes=None, slab_bytes=None):
+def deflate_raw_slabs(t, chunk_bytes=None, slab_bytes=None, match='runs'):
     """Iterator form of deflate_raw: yields (packed uint8 [bytes] on the device, n_chunks) for one slab of at most `slab_bytes` of input
     after the other (default DEFLATE_SLAB_BYTES, rounded down to whole chunks), so that a writer can stream an array of any size to a file
-    with a bounded workspace.  The pieces concatenate by bytes.  An empty tensor yields nothing."""
+    with a bounded workspace.  The pieces concatenate by bytes.  An empty tensor yields nothing.  match='window': every slab after the
+    first passes the min(32768, its offset) bytes before it as history, so matches cross slab borders as they cross chunk borders."""
+    if match not in DEFLATE_MATCHERS:
+        raise _lib.VarsepHipError("deflate_raw: match=%r: 'runs' or 'window' expected" % (match,))
     data = _as_bytes(t, 'deflate_raw')
     chunk = DEFLATE_CHUNK if chunk_bytes is None else int(chunk_bytes)
     if chunk < DEFLATE_MIN_CHUNK or chunk > DEFLATE_CHUNK:
@@ -2603,9 +2610,16 @@ def deflate_raw_slabs(t, chunk_bytes=None, slab_bytes=None):
             slots = torch.empty((n_chunks, stride), dtype=torch.uint8, device=device)
             sizes = torch.empty((n_chunks,), dtype=torch.int64, device=device)
             e0 = _pb()
-            check(lib.vs_deflate_chunks(part.data_ptr(), part.numel(), chunk, slots.data_ptr(), stride, sizes.data_ptr(), stream_ptr()),
-                  'vs_deflate_chunks')
-            _pe(e0, 'vs_deflate_chunks', nbytes=float(part.numel()))
+            if match == 'window':
+                groups = min(n_chunks, DEFLATE_WINDOW_GROUPS)
+                work = torch.empty((groups * DEFLATE_WINDOW_GROUP_BYTES // 4,), dtype=torch.int32, device=device)
+                check(lib.vs_deflate_chunks_window(part.data_ptr(), min(DEFLATE_MAX_HISTORY, lo), part.numel(), chunk, slots.data_ptr(), stride,
+                                                   sizes.data_ptr(), work.data_ptr(), work.numel() * 4, stream_ptr()), 'vs_deflate_chunks_window')
+                _pe(e0, 'vs_deflate_chunks_window', nbytes=float(part.numel()))
+            else:
+                check(lib.vs_deflate_chunks(part.data_ptr(), part.numel(), chunk, slots.data_ptr(), stride, sizes.data_ptr(), stream_ptr()),
+                      'vs_deflate_chunks')
+                _pe(e0, 'vs_deflate_chunks', nbytes=float(part.numel()))
             ends = torch.cumsum(sizes, 0)
             offsets = ends - sizes
             total = int(ends[-1].item())
@@ -2617,13 +2631,14 @@ def deflate_raw_slabs(t, chunk_bytes=None, slab_bytes=None):
             yield packed, n_chunks
 
 
-def deflate_raw(t, chunk_bytes=None, slab_bytes=None):
+def deflate_raw(t, chunk_bytes=None, slab_bytes=None, match='runs'):
     """`t` (any contiguous device tensor, taken as bytes) as a raw DEFLATE stream (RFC 1951) WITHOUT its final block: (packed uint8 [bytes]
     on the device, n_chunks).  Every chunk of `chunk_bytes` (default DEFLATE_CHUNK) is compressed on its own by one wave (vs_deflate_chunks:
     literals and distance-1 run matches, stored / fixed / dynamic by exact cost) and ends on a byte boundary with an empty stored block, so
     `packed + b'\\x03\\x00'` is a complete stream that zlib inflates to t's bytes.  vs_deflate_pack gathers the chunks.  An empty tensor gives
-    (empty, 0).  For arrays above DEFLATE_SLAB_BYTES prefer deflate_raw_slabs, which bounds the workspace."""
-    pieces = list(deflate_raw_slabs(t, chunk_bytes, slab_bytes))
+    (empty, 0).  For arrays above DEFLATE_SLAB_BYTES prefer deflate_raw_slabs, which bounds the workspace.  match='window' adds the window
+    search (vs_deflate_chunks_window: matches up to 32768 bytes back, across chunk borders; per chunk never larger than 'runs')."""
+    pieces = list(deflate_raw_slabs(t, chunk_bytes, slab_bytes, match))
     if not pieces:
         return torch.empty((0,), dtype=torch.uint8, device=t.device), 0
     if len(pieces) == 1:
