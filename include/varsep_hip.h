@@ -505,6 +505,40 @@ int vs_deflate_pack(const uint8_t* slots, int64_t slot_stride, const int64_t* si
  * a null pointer, n_bytes < 0, chunk_bytes outside 256 .. 2^24 or more pieces than a grid holds.                                         */
 int vs_crc32(const uint8_t* src, int64_t n_bytes, int64_t chunk_bytes, uint32_t init, uint32_t* partial, void* stream);
 
+/* PNG encoding on the device (csrc/vs_png_encode.hip; the logic is csrc/vs_png_encode_core.h on top of the two DEFLATE cores): a batch of
+ * images in HBM becomes one complete PNG file per image in three launches -- the forward row filters, one DEFLATE stream per image, the
+ * framing -- so that only compressed bytes are copied to the host.  S = H * (1 + W * C) is the filtered size of one image.             */
+/* pixels uint8 [n, H, W, C], C in 1..4 -> raw slot i (raw + i * raw_stride, raw_stride >= S): H rows of 1 + W * C bytes, the first byte of
+ * a row its filter type.  mode 0..4: every row gets that type; mode 5: adaptive -- per row the type with the least sum of |residual|, each
+ * residual read as a signed byte (0x80 counts 128), a tie to the lowest type.  bpp = C; the row above row 0 of EVERY image and the pixel
+ * left of column 0 are zeros.  One wave per row, four bytes per lane along the row; bytes of a slot beyond S are not written.  No
+ * alignment is required of pixels or raw.  VS_ERR_ARG (and nothing launched) for a null pointer, a non-positive size, C outside 1..4, mode
+ * outside 0..5, raw_stride < S, a row (1 + W * C) above 65536 bytes or more rows than a grid of four-row workgroups holds.              */
+int vs_png_filter(const uint8_t* pixels, int64_t n, int H, int W, int C, int mode, uint8_t* raw, int64_t raw_stride, void* stream);
+/* n_streams streams of stream_bytes >= 1 bytes each, stream s at src + s * stream_stride (stream_stride >= stream_bytes; the padding is
+ * never read), every one compressed INDEPENDENTLY of the others: stream s is cut into K = ceil(stream_bytes / chunk_bytes) chunks (the
+ * last one short), chunk k goes to slot s * K + k (slots + (s * K + k) * slot_stride) and its byte count to sizes[s * K + k] (int64
+ * [n_streams * K]).  The K chunks of one stream, concatenated and closed with 03 00, are a raw RFC 1951 stream that inflates on its own.
+ * match 0: the RUNS parse of vs_deflate_chunks (workspace may be null).  match 1: the WINDOW parse of vs_deflate_chunks_window, whose
+ * history for chunk k is min(32768, k * chunk_bytes): the stream's own bytes, never before its first byte; workspace as there
+ * (VS_DEFLATE_WINDOW_GROUP_BYTES per workgroup, 4-byte aligned, the grid bounded by it; its size changes no output byte).  Per stream the
+ * bytes are those of vs_deflate_chunks / vs_deflate_chunks_window (history 0) on that stream alone.  VS_ERR_ARG (and nothing launched)
+ * for a null pointer, a non-positive size, stream_stride < stream_bytes, match outside 0..1, chunk_bytes outside VS_DEFLATE_MIN_CHUNK ..
+ * VS_DEFLATE_MAX_CHUNK, slot_stride < chunk_bytes + VS_DEFLATE_SLOT_EXTRA, more chunks than a grid holds or, with match 1, a null,
+ * misaligned or too small workspace.                                                                                                  */
+int vs_deflate_streams(const uint8_t* src, int64_t n_streams, int64_t stream_bytes, int64_t stream_stride, int chunk_bytes, int match,
+                       uint8_t* slots, int64_t slot_stride, int64_t* sizes, void* workspace, int64_t workspace_bytes, void* stream);
+/* One complete PNG file per image into files + i * file_stride: the 8-byte signature, IHDR (bit depth 8, colour type 0 / 4 / 2 / 6 for
+ * C = 1 / 2 / 3 / 4, no interlace), ONE IDAT chunk (78 9C, the chunks_per_image slots of image i back to back -- slots and sizes as
+ * vs_deflate_streams left them --, 03 00, the Adler-32 of the S filtered bytes at raw + i * raw_stride, big-endian) and IEND;
+ * file_bytes[i] (int64 [n]) = 57 + 8 + the sum of the image's sizes.  A size outside 0 .. slot_stride (or a sum that would leave the
+ * file's stride) sets file_bytes[i] = -1 and writes nothing for that image; nothing is ever written past file_stride.  One workgroup per
+ * image.  VS_ERR_ARG (and nothing launched) for a null pointer, a non-positive size, C outside 1..4, raw_stride < S, chunks_per_image
+ * above S, file_stride < 57 + 8 + S + VS_DEFLATE_SLOT_EXTRA * chunks_per_image, an IDAT body that could reach 2^31 bytes, or n above the
+ * grid limit.                                                                                                                         */
+int vs_png_assemble(const uint8_t* raw, int64_t raw_stride, const uint8_t* slots, int64_t slot_stride, const int64_t* sizes, int64_t n, int H,
+                    int W, int C, int64_t chunks_per_image, uint8_t* files, int64_t file_stride, int64_t* file_bytes, void* stream);
+
 /* NumPy's legacy random stream on the device (csrc/vs_mt19937.hip; the logic is csrc/vs_mt19937_core.h): np.random.RandomState is MT19937,
  * and its scalar randint(low, high) is masked rejection on the 32-bit outputs.  The Moving-MNIST training loader draws its table of five
  * integers per digit from a state that lives in HBM, in the order and with the values of the host loop it replaces.                     */

@@ -225,6 +225,31 @@ def chairs_decoder(decode=None, device=None):
     return decode
 
 
+ENCODE_ENV = 'VARSEP_CHAIRS_ENCODE'
+
+
+def chairs_encoder(encode=None):
+    """'host' or 'device': who encodes the prepared views of gen_chairs.  The keyword wins; None reads the environment variable
+    VARSEP_CHAIRS_ENCODE; unset (or empty) means 'host' on every machine: the device route is opt-in."""
+    source = 'encode'
+    if encode is None:
+        encode, source = os.environ.get(ENCODE_ENV) or 'host', ENCODE_ENV
+    if encode not in ('host', 'device'):
+        raise ValueError("%s must be 'host' or 'device' (got %r)" % (source, encode))
+    return encode
+
+
+def write_files(paths, files, sizes):
+    """files uint8 [n, stride] and sizes int64 [n] (host arrays): files[i, :sizes[i]] into paths[i], on at most MAX_DECODE_WORKERS threads."""
+    def write(i):
+        with open(paths[i], 'wb') as f:
+            f.write(memoryview(files[i, :sizes[i]]))
+
+    with ThreadPoolExecutor(max_workers=min(MAX_DECODE_WORKERS, len(paths))) as pool:
+        for _ in pool.map(write, range(len(paths)), chunksize=1):
+            pass
+
+
 def read_files(paths):
     """The bytes of every file, read on at most MAX_DECODE_WORKERS threads; ValueError naming a file that is missing."""
     def read(path):

@@ -2664,6 +2664,127 @@ def crc32(t, init=0):
     return int(np.bitwise_xor.reduce(partial.cpu().numpy().view(np.uint32))) ^ 0xFFFFFFFF
 
 
+# ---- PNG encoding on the device (csrc/vs_png_encode.hip) ---------------------------------------------------------------------------
+PNG_FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': 5}
+PNG_FIXED_BYTES = 65              # 57 + 8: everything of a file but its compressed chunks
+
+
+def _png_filter_mode(mode, what):
+    if isinstance(mode, str) and mode in PNG_FILTERS:
+        return PNG_FILTERS[mode]
+    if isinstance(mode, int) and not isinstance(mode, bool) and 0 <= mode <= 5:
+        return mode
+    raise _lib.VarsepHipError('%s: filter %r: one of %s or a type 0..4 (5: adaptive) expected' % (what, mode, ', '.join(PNG_FILTERS)))
+
+
+def _deflate_match_chunk(match, chunk_bytes, what):
+    if match not in DEFLATE_MATCHERS:
+        raise _lib.VarsepHipError("%s: match=%r: 'runs' or 'window' expected" % (what, match))
+    chunk = DEFLATE_CHUNK if chunk_bytes is None else int(chunk_bytes)
+    if chunk < DEFLATE_MIN_CHUNK or chunk > DEFLATE_CHUNK:
+        raise _lib.VarsepHipError('%s: chunk_bytes %d outside %d .. %d' % (what, chunk, DEFLATE_MIN_CHUNK, DEFLATE_CHUNK))
+    return DEFLATE_MATCHERS.index(match), chunk
+
+
+def png_filter(pixels, mode='adaptive', out=None):
+    """pixels: uint8 [n, H, W, C] on the device (contiguous, any alignment), C in 1..4 -> raw uint8 [n, H * (1 + W * C)]: the filtered rows of
+    every image, each row behind its filter-type byte, in one launch of vs_png_filter.  mode: 'none' | 'sub' | 'up' | 'average' | 'paeth'
+    (or 0..4) gives every row that type; 'adaptive' (5) takes per row the type with the least sum of absolute signed residuals, a tie to
+    the lowest type.  out: optional uint8 [n, stride >= H * (1 + W * C)] view with contiguous rows to write into; bytes of a row of `out`
+    beyond the image's are not written."""
+    require_cuda(pixels, out)
+    if pixels.dtype != torch.uint8 or pixels.dim() != 4 or not pixels.is_contiguous() or pixels.numel() == 0 or not 1 <= pixels.shape[3] <= 4:
+        raise _lib.VarsepHipError('png_filter: a non-empty contiguous uint8 [n, H, W, C] tensor with C in 1..4 is expected (got %s %s)'
+                                  % (pixels.dtype, tuple(pixels.shape)))
+    code = _png_filter_mode(mode, 'png_filter')
+    n, H, W, C = pixels.shape
+    S = H * (1 + W * C)
+    if out is not None and (out.dtype != torch.uint8 or out.dim() != 2 or out.shape != (n, S) or out.stride(1) != 1
+                            or (n > 1 and out.stride(0) < S) or out.device != pixels.device):
+        raise _lib.VarsepHipError('png_filter: out must be uint8 [%d, %d] with contiguous rows on %s' % (n, S, pixels.device))
+    with torch.cuda.device(pixels.device):
+        if out is None:
+            out = torch.empty((n, S), dtype=torch.uint8, device=pixels.device)
+        e0 = _pb()
+        check(_lib.load_library().vs_png_filter(pixels.data_ptr(), n, H, W, C, code, out.data_ptr(), max(out.stride(0), S) if n > 1 else S,
+                                                stream_ptr()), 'vs_png_filter')
+        _pe(e0, 'vs_png_filter', nbytes=float(n) * (S + (2 if code == 5 else 1) * H * W * C))
+    return out
+
+
+def deflate_streams(raw, stream_bytes, chunk_bytes=None, match='window', groups=None):
+    """raw: uint8 [n, stride >= stream_bytes] on the device with contiguous rows; the first `stream_bytes` of every row are one stream, and
+    every stream is compressed on its own in ONE launch of vs_deflate_streams.  Returns (slots uint8 [n * K, slot_stride], sizes int64
+    [n * K]) with K = ceil(stream_bytes / chunk_bytes): slots[s * K + k, :sizes[s * K + k]] for k < K, concatenated and closed with
+    b'\\x03\\x00', is a raw DEFLATE stream that inflates to stream s.  match: 'runs' or 'window' (matches up to 32768 bytes back, inside the
+    stream only).  groups: workgroups (and workspace slices) of the window parse; no output byte depends on it."""
+    require_cuda(raw)
+    stream_bytes = int(stream_bytes)
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.shape[0] < 1 or stream_bytes < 1 or raw.shape[1] < stream_bytes \
+            or (raw.shape[1] > 1 and raw.stride(1) != 1) or (raw.shape[0] > 1 and raw.stride(0) < stream_bytes):
+        raise _lib.VarsepHipError('deflate_streams: raw uint8 [n >= 1, stride >= stream_bytes >= 1] with contiguous rows expected (got %s %s, '
+                                  'stream_bytes %d)' % (raw.dtype, tuple(raw.shape), stream_bytes))
+    code, chunk = _deflate_match_chunk(match, chunk_bytes, 'deflate_streams')
+    n, device = raw.shape[0], raw.device
+    K = -(-stream_bytes // chunk)
+    stride = (chunk + DEFLATE_SLOT_EXTRA + 15) // 16 * 16
+    with torch.cuda.device(device):
+        slots = torch.empty((n * K, stride), dtype=torch.uint8, device=device)
+        sizes = torch.empty((n * K,), dtype=torch.int64, device=device)
+        work, work_bytes = None, 0
+        if code == 1:
+            groups = min(n * K, DEFLATE_WINDOW_GROUPS) if groups is None else max(1, int(groups))
+            work = torch.empty((groups * DEFLATE_WINDOW_GROUP_BYTES // 4,), dtype=torch.int32, device=device)
+            work_bytes = work.numel() * 4
+        e0 = _pb()
+        check(_lib.load_library().vs_deflate_streams(raw.data_ptr(), n, stream_bytes, raw.stride(0) if n > 1 else stream_bytes, chunk, code,
+                                                     slots.data_ptr(), stride, sizes.data_ptr(), None if work is None else work.data_ptr(),
+                                                     work_bytes, stream_ptr()), 'vs_deflate_streams')
+        _pe(e0, 'vs_deflate_streams', nbytes=float(n) * stream_bytes)
+    return slots, sizes
+
+
+def png_assemble(raw, slots, sizes, H, W, C):
+    """The framing launch (vs_png_assemble): raw uint8 [n, stride >= S] (png_filter's), slots / sizes of deflate_streams over it -> (files
+    uint8 [n, file_stride], file_bytes int64 [n]); file i is files[i, :file_bytes[i]].  file_bytes[i] == -1 flags sizes that are none."""
+    require_cuda(raw, slots, sizes)
+    n, S = raw.shape[0], int(H) * (1 + int(W) * int(C))
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or n < 1 or raw.shape[1] < S or (raw.shape[1] > 1 and raw.stride(1) != 1) \
+            or slots.dtype != torch.uint8 or slots.dim() != 2 or not slots.is_contiguous() or sizes.dtype != torch.int64 or sizes.dim() != 1 \
+            or not sizes.is_contiguous() or sizes.numel() != slots.shape[0] or sizes.numel() % n or sizes.numel() == 0:
+        raise _lib.VarsepHipError('png_assemble: raw uint8 [n, >= %d], contiguous slots uint8 [n * K, slot_stride] and sizes int64 [n * K] expected' % S)
+    K = sizes.numel() // n
+    stride = (PNG_FIXED_BYTES + S + DEFLATE_SLOT_EXTRA * K + 15) // 16 * 16
+    with torch.cuda.device(raw.device):
+        files = torch.empty((n, stride), dtype=torch.uint8, device=raw.device)
+        file_bytes = torch.empty((n,), dtype=torch.int64, device=raw.device)
+        e0 = _pb()
+        check(_lib.load_library().vs_png_assemble(raw.data_ptr(), raw.stride(0) if n > 1 else S, slots.data_ptr(), slots.stride(0), sizes.data_ptr(), n,
+                                                  int(H), int(W), int(C), K, files.data_ptr(), stride, file_bytes.data_ptr(), stream_ptr()),
+              'vs_png_assemble')
+        _pe(e0, 'vs_png_assemble', nbytes=float(n) * (S + 2.0 * stride))
+    return files, file_bytes
+
+
+def png_encode_u8(images, filter='adaptive', match='window', chunk_bytes=None):
+    """images: uint8 [n, H, W, C] on the device, C in 1..4 (grey, grey + alpha, RGB, RGBA) -> (files uint8 [n, stride] on the device, sizes
+    int64 [n]): files[i, :sizes[i]] is a complete non-interlaced 8-bit PNG file of image i.  Three launches with no synchronisation in
+    between -- vs_png_filter (`filter`: see png_filter), vs_deflate_streams (`match`, `chunk_bytes`: see deflate_streams; one zlib stream
+    per image, independent of its neighbours) and vs_png_assemble (signature, IHDR, one IDAT with its Adler-32 and CRC-32, IEND).  Copy
+    `files` and `sizes` to the host once each and write files[i, :sizes[i]]."""
+    require_cuda(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.numel() == 0 or not 1 <= images.shape[3] <= 4:
+        raise _lib.VarsepHipError('png_encode_u8: a non-empty uint8 [n, H, W, C] tensor with C in 1..4 is expected (got %s %s)'
+                                  % (images.dtype, tuple(images.shape)))
+    _png_filter_mode(filter, 'png_encode_u8')
+    _deflate_match_chunk(match, chunk_bytes, 'png_encode_u8')
+    images = images.contiguous()
+    n, H, W, C = images.shape
+    raw = png_filter(images, filter)
+    slots, chunk_sizes = deflate_streams(raw, raw.shape[1], chunk_bytes, match)
+    return png_assemble(raw, slots, chunk_sizes, H, W, C)
+
+
 # ---- NumPy's legacy random stream on the device (csrc/vs_mt19937.hip) ----------------------------------------------------------------
 MT19937_STATE_WORDS = 625         # VS_MT19937_STATE_WORDS: key[624], pos
 MT19937_MAX_COLS = 8              # VS_MT19937_MAX_COLS

@@ -8,7 +8,10 @@ loader and test/chairs/test_disentanglement.py read.  The reference does this wi
 crop and the resize of a batch of whole objects are ONE launch (ops.resample_lanczos_u8, csrc/vs_resample.hip), which reproduces PIL's
 8-bit arithmetic bit for bit.  The PNG files are decoded on the host (PIL when it imports, data/chairs.py's own reader otherwise) or on the
 device (ops.png_decode_rgb8: only the compressed bytes are uploaded; two more launches, the same bytes).  The environment variable
-VARSEP_CHAIRS_DECODE=host|device selects the decoder; unset, the device decodes where PIL does not import.  One deviation from the reference: names of the form <digits>.png are left out of an object's listing, so a second
+VARSEP_CHAIRS_DECODE=host|device selects the decoder; unset, the device decodes where PIL does not import.  The resized views are
+encoded on the host (PIL's `save` or data/chairs.py's writer, one by one on a thread pool) or, with VARSEP_CHAIRS_ENCODE=device, on the
+device (ops.png_encode_u8: row filters, one zlib stream per view, framing; only the finished files are downloaded); unset means host.
+One deviation from the reference: names of the form <digits>.png are left out of an object's listing, so a second
 run reproduces the first (the reference would feed its own outputs back in).  There is no CPU mode: --device is required.
 `--chairs_raw` of main.py and test/chairs/test_disentanglement_raw.py build the same set straight in HBM, without files (`Chairs.from_raw`).
 """
@@ -20,6 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from ... import ops
 from ...data import chairs as C
 
 
@@ -36,15 +40,19 @@ def _save_all(paths, images, image_module):
             pass
 
 
-def generate(data_dir, image_size, device, box=C.RAW_BOX, timings=None, decode=None):
+def generate(data_dir, image_size, device, box=C.RAW_BOX, timings=None, decode=None, encode=None):
     """The reference's `generate` (gen_chairs.py:23-33) plus the device and the crop box.  Works in batches of whole objects: decode, one
     upload, one launch, one download, write.  Returns the number of files written.  timings: optional dict that receives the seconds
     spent in 'decode', 'upload', 'kernel', 'download' and 'write' (the device is then synchronised after every stage).  decode: 'host',
-    'device' or None (the environment variable VARSEP_CHAIRS_DECODE, then the default rule of data/chairs.py's `chairs_decoder`)."""
+    'device' or None (the environment variable VARSEP_CHAIRS_DECODE, then the default rule of data/chairs.py's `chairs_decoder`).
+    encode: 'host' (PIL or data/chairs.py's writer, on the thread pool), 'device' or None (the environment variable VARSEP_CHAIRS_ENCODE,
+    then 'host').  With 'device' the resized batch stays in HBM, ops.png_encode_u8 makes the files there (three launches), the files and
+    their sizes come down in one copy each and the thread pool only opens and writes; timings then also receives 'encode'."""
     device = C.require_gpu('Chairs preprocessing', device)
     box = tuple(int(v) for v in box)
     root, objects = C.list_objects(data_dir)
-    image_module = C._pil_image()
+    on_device = C.chairs_encoder(encode) == 'device'
+    image_module = C._pil_image()                        # (the host decoder's; the device encoder needs none)
     written = 0
     for start in range(0, len(objects), C.OBJECTS_PER_BATCH):
         sources, targets = [], []
@@ -57,9 +65,21 @@ def generate(data_dir, image_size, device, box=C.RAW_BOX, timings=None, decode=N
             continue
         out = C.prepare_renders(sources, box, image_size, device, image_module, timings, decode)
         t0 = time.perf_counter()
-        host = out.cpu().numpy()
-        t1 = time.perf_counter()
-        _save_all(targets, host, image_module)
+        if on_device:
+            files, sizes = ops.png_encode_u8(out)
+            if timings is not None:
+                torch.cuda.synchronize(device)
+                timings['encode'] = timings.get('encode', 0.0) + time.perf_counter() - t0
+                t0 = time.perf_counter()
+            files, sizes = files.cpu().numpy(), sizes.cpu().numpy()
+            if sizes.min() < 0:
+                raise RuntimeError('%s: the device encoder left no file' % targets[int(sizes.argmin())])
+            t1 = time.perf_counter()
+            C.write_files(targets, files, sizes)
+        else:
+            host = out.cpu().numpy()
+            t1 = time.perf_counter()
+            _save_all(targets, host, image_module)
         if timings is not None:
             timings['download'] = timings.get('download', 0.0) + t1 - t0
             timings['write'] = timings.get('write', 0.0) + time.perf_counter() - t1
