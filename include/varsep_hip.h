@@ -396,6 +396,10 @@ int vs_chairs_gather(const uint8_t* frames, int64_t n_objects, int views_per_obj
  * as zeros and sets *bad = 1 (bad may be NULL); the launch never reads out of bounds.  At most 65535 rows per launch.              */
 int vs_gather_timeline(const float* frames, int64_t n_frames, int64_t frame_elems, const int32_t* first, int64_t n_windows, int step,
                        const int32_t* item_idx, int64_t rows, int seq_len, void* out, int out_dtype, int32_t* bad, void* stream);
+/* dst fp32 [N, T, inner] = (float) src uint8 [T, N, inner]: the time-major videos of a test-set file, as decoded, into the video-major fp32
+ * tensor the dataset keeps (exact: every uint8 is an fp32).  VS_ERR_ARG for a null pointer, a negative size, T * N above the grid limit or
+ * dst off a 16-byte boundary; an empty tensor launches nothing (csrc/vs_data.hip).                                                                         */
+int vs_u8_tn_to_f32_nt(const uint8_t* src, int64_t T, int64_t N, int64_t inner, float* dst, void* stream);
 
 /* The WaveEq data set simulated on the device (reference: preprocessing/wave/gen_wave.py:37-92 and :121-135; csrc/vs_wave_sim.hip
  * states the equations, the border rule and torchdiffeq's 3/8-rule tableau).  One workgroup integrates one sequence of frame_size x
@@ -504,6 +508,45 @@ int vs_deflate_pack(const uint8_t* slots, int64_t slot_stride, const int64_t* si
  * zlib.crc32(data, init) == ~(XOR of the partials).  One wave per piece.  n_bytes == 0 launches nothing (the CRC is init).  VS_ERR_ARG for
  * a null pointer, n_bytes < 0, chunk_bytes outside 256 .. 2^24 or more pieces than a grid holds.                                         */
 int vs_crc32(const uint8_t* src, int64_t n_bytes, int64_t chunk_bytes, uint32_t init, uint32_t* partial, void* stream);
+
+/* Chunk-parallel DEFLATE decoding on the device (csrc/vs_inflate_chunks.hip; the logic is csrc/vs_inflate_chunks_core.h on top of
+ * csrc/vs_inflate_core.h): the reader of the .npz members the encoder above writes.  Such a member is a raw RFC 1951 stream cut at
+ * byte-aligned empty stored blocks (00 00 FF FF); the byte after a marker is a CANDIDATE start of a SEGMENT, every candidate is decoded by
+ * one wave without knowing what came before it, and the host chains the segments from offset 0 by where each one ends (ops.inflate_raw).
+ * A byte whose source lies before its segment is EXTERNAL: it is left as a mark and filled in chain order by vs_inflate_resolve.          */
+#define VS_INFLATE_SLOT_BYTES 32768   /* = VS_DEFLATE_MAX_CHUNK: the most a segment may produce, and the least a slot holds */
+#define VS_INFLATE_REPORT_WORDS 6     /* per candidate: status (VS_INFLATE_*), end, final, bytes produced, external bytes, largest reach */
+#define VS_INFLATE_MAX_BATCH 2147483647ll   /* candidates or segments per launch: the grid limit */
+/* Appends to cand int64 [cap], in no particular order, offset 0 and every offset p + 4 <= comp_bytes with comp[p .. p + 3] = 00 00 FF FF.
+ * *count (device, zeroed by the caller) is advanced by the number found even where it exceeds cap (entries beyond cap are not written): a
+ * call with cand null and cap 0 only counts.  VS_ERR_ARG (and nothing launched) for a null comp or count, a null cand with cap != 0, a
+ * negative comp_bytes or cap, or more bytes than a grid covers.                                                                        */
+int vs_inflate_sync_scan(const uint8_t* comp, int64_t comp_bytes, int64_t* cand, int64_t cap, int64_t* count, void* stream);
+/* One wave per candidate c < n_cand (a batch: the workspace is n_cand slots, whatever the member's size): the segment of comp
+ * [comp_bytes] that starts at cand[c] is decoded until an empty stored block has been consumed (end: the byte after it), a block with
+ * BFINAL = 1 has ended (final = 1, end: the next byte boundary) or an error (status != 0: a VS_INFLATE_* code; VS_INFLATE_OUT_LONG for more
+ * than VS_INFLATE_SLOT_BYTES of output, VS_INFLATE_INPUT for a start outside 0 .. comp_bytes or a segment not over after 65536 bytes of
+ * input).  words int64 [n_cand, VS_INFLATE_REPORT_WORDS] always receives the report.  With status 0, slots + c * slot_stride receives the
+ * `produced` bytes (0 where a byte is external) and, only when the segment has external bytes, marks uint16 [n_cand, VS_INFLATE_SLOT_BYTES]
+ * row c receives per byte 0 or o + 1, the source being the byte o + 1 before the segment's first output byte.  Nothing else in global
+ * memory is written, on any input.  VS_ERR_ARG (and nothing launched) for a null pointer, a negative size, n_cand above
+ * VS_INFLATE_MAX_BATCH, slot_stride < VS_INFLATE_SLOT_BYTES or marks off a 2-byte boundary; n_cand == 0 launches nothing.            */
+int vs_inflate_segments(const uint8_t* comp, int64_t comp_bytes, const int64_t* cand, int64_t n_cand, uint8_t* slots, int64_t slot_stride,
+                        uint16_t* marks, int64_t* words, void* stream);
+/* The mirror of vs_deflate_pack: out[offsets[c] .. offsets[c] + sizes[c]) = the first sizes[c] bytes of slot slot_index[c], c < n (int64
+ * [n] each; the chain segments of a batch, offsets their prefix sum along the chain).  A segment whose slot is outside 0 .. n_slots - 1,
+ * whose size is outside 0 .. VS_INFLATE_SLOT_BYTES or whose bytes would leave out [out_bytes] is not copied.  VS_ERR_ARG for a null
+ * pointer, a negative size, n or n_slots above VS_INFLATE_MAX_BATCH or slot_stride < VS_INFLATE_SLOT_BYTES; n == 0 launches nothing.    */
+int vs_inflate_place(const uint8_t* slots, int64_t slot_stride, int64_t n_slots, const int64_t* slot_index, const int64_t* sizes,
+                     const int64_t* offsets, int64_t n, uint8_t* out, int64_t out_bytes, void* stream);
+/* Fills the external bytes of the listed segments (those of a batch's chain that have any, IN CHAIN ORDER; arguments as vs_inflate_place,
+ * marks as vs_inflate_segments left them): out[offsets[c] + i] = out[offsets[c] - marks[slot_index[c]][i]] for every non-zero mark not
+ * above offsets[c].  ONE workgroup, one barrier per segment: a source lies before its segment, so it was placed by the launch before or
+ * filled for an earlier segment.  Launch it after vs_inflate_place of the same batch, batches in chain order.  A segment outside the
+ * bounds vs_inflate_place checks is passed over.  VS_ERR_ARG for a null pointer, a negative size, n or n_slots above
+ * VS_INFLATE_MAX_BATCH or marks off a 2-byte boundary; n == 0 launches nothing.                                                         */
+int vs_inflate_resolve(const uint16_t* marks, int64_t n_slots, const int64_t* slot_index, const int64_t* sizes, const int64_t* offsets, int64_t n,
+                       uint8_t* out, int64_t out_bytes, void* stream);
 
 /* PNG encoding on the device (csrc/vs_png_encode.hip; the logic is csrc/vs_png_encode_core.h on top of the two DEFLATE cores): a batch of
  * images in HBM becomes one complete PNG file per image in three launches -- the forward row filters, one DEFLATE stream per image, the

@@ -459,3 +459,38 @@ extern "C" int vs_moving_mnist_testset_place(const uint8_t* digits, int64_t n_di
     if (rc != VS_OK) return rc;
     MM_LAUNCH(mm_table_kernel, job, (const int*)positions, n_videos, (const int*)digit_idx, num_digits, 0, (int*)bad);
 }
+
+// ---- the test-set file's videos, as loaded: uint8 [T, N, ...] -> the fp32 [N, T, ...] that MovingMNIST keeps ----------------------------
+namespace {
+
+// dst fp32 [N, T, inner] = src uint8 [T, N, inner]: one workgroup per (t, n) row, four bytes per thread and turn when src allows word loads.
+__global__ __launch_bounds__(256) void u8_tn_to_f32_nt_kernel(const uint8_t* __restrict__ src, int64_t T, int64_t N, int64_t inner,
+                                                              float* __restrict__ dst) {
+    const int64_t row = blockIdx.x, t = row / N, n = row % N;
+    const uint8_t* s = src + row * inner;
+    float* d = dst + (n * T + t) * inner;
+    if ((((uintptr_t)s) & 3) == 0 && (inner & 3) == 0) {
+        for (int64_t w = threadIdx.x; w < (inner >> 2); w += 256) {
+            const uint32_t v = reinterpret_cast<const uint32_t*>(s)[w];
+            f32x4 o;
+            o[0] = (float)(v & 255u); o[1] = (float)((v >> 8) & 255u); o[2] = (float)((v >> 16) & 255u); o[3] = (float)(v >> 24);
+            *reinterpret_cast<f32x4*>(d + 4 * w) = o;                      // d is 16-byte aligned: dst is, and inner is a multiple of 4
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < inner; i += 256) d[i] = (float)s[i];
+    }
+}
+
+}  // namespace
+
+extern "C" int vs_u8_tn_to_f32_nt(const uint8_t* src, int64_t T, int64_t N, int64_t inner, float* dst, void* stream) {
+    VS_CHECK_ARG(src && dst, "vs_u8_tn_to_f32_nt: null pointer");
+    VS_CHECK_ARG(T >= 0 && N >= 0 && inner >= 0, "vs_u8_tn_to_f32_nt: sizes must not be negative (T %lld, N %lld, inner %lld)", (long long)T, (long long)N,
+                 (long long)inner);
+    VS_CHECK_ARG(T == 0 || N <= 2147483647ll / T, "vs_u8_tn_to_f32_nt: %lld x %lld rows exceed the grid limit", (long long)T, (long long)N);
+    VS_CHECK_ARG(((uintptr_t)dst & 15) == 0, "vs_u8_tn_to_f32_nt: dst %p is not at a 16-byte boundary", (void*)dst);
+    if (T * N == 0 || inner == 0) return VS_OK;
+    hipLaunchKernelGGL(u8_tn_to_f32_nt_kernel, dim3((unsigned)(T * N)), dim3(256), 0, (hipStream_t)stream, src, T, N, inner, dst);
+    VS_CHECK_LAUNCH("vs_u8_tn_to_f32_nt");
+    return VS_OK;
+}

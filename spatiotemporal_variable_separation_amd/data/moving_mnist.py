@@ -280,14 +280,28 @@ class MovingMNIST:
         return cond[0], target[0]
 
     @classmethod
-    def make_dataset(cls, data_dir, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device='cuda', seed=None):
+    def make_dataset(cls, data_dir, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device='cuda', seed=None, load=None, report=None):
+        """load: who decompresses the test-set file (utils/loadz.npz_loader: the keyword, then VARSEP_NPZ_LOAD, then 'host').  'host' is
+        np.load and the host conversion, as before; 'device' inflates `sequences` in HBM (utils/loadz.load), where it stays uint8 until the
+        [T, N, ...] -> fp32 [N, T, ...] step, also done there.  `.data` is the same bit for bit.  report: optional dict for
+        utils/loadz.load's record of the route `sequences` took."""
         if train:
             data = synthetic_digits(seed=seed or 1234) if data_dir == 'synthetic_digits' else read_mnist_images(data_dir, train=True)
         else:
+            from ..utils import loadz
             prefix = '' if deterministic else 's'
-            dataset = np.load(os.path.join(data_dir, f'{prefix}mmnist_test_{num_digits}digits_{nx}.npz'), allow_pickle=True)
-            sequences = dataset['sequences']
-            data = [sequences[:, i].astype(np.single) for i in range(sequences.shape[1])]
+            path = os.path.join(data_dir, f'{prefix}mmnist_test_{num_digits}digits_{nx}.npz')
+            if loadz.npz_loader(load) == 'device':
+                sequences = loadz.load(path, device, keys=('sequences',), load='device', report=report)['sequences']
+                if sequences.dtype == torch.uint8:
+                    from .. import ops
+                    data = ops.u8_tn_to_f32_nt(sequences)
+                else:                                                       # (a file of another dtype: `astype(np.single)` as the host does it)
+                    data = sequences.transpose(0, 1).to(torch.float32).contiguous()
+            else:
+                dataset = np.load(path, allow_pickle=True)
+                sequences = dataset['sequences']
+                data = [sequences[:, i].astype(np.single) for i in range(sequences.shape[1])]
         return cls(data, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device=device)
 
     @staticmethod

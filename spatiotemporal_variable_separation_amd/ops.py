@@ -2664,6 +2664,150 @@ def crc32(t, init=0):
     return int(np.bitwise_xor.reduce(partial.cpu().numpy().view(np.uint32))) ^ 0xFFFFFFFF
 
 
+# ---- chunk-parallel DEFLATE decoding on the device (csrc/vs_inflate_chunks.hip) ------------------------------------------------------
+INFLATE_SLOT_BYTES = 32768        # VS_INFLATE_SLOT_BYTES: the most a segment may produce
+INFLATE_REPORT_WORDS = 6          # VS_INFLATE_REPORT_WORDS: status, end, final, produced, externals, reach
+INFLATE_MAX_BATCH = 2147483647    # VS_INFLATE_MAX_BATCH
+INFLATE_BATCH = 4096              # candidates per launch of vs_inflate_segments: 96 KiB of workspace each, 384 MiB whatever the member's size
+
+
+class InflateNotChunked:
+    """What inflate_raw returns for a stream whose segments do not chain: `reason` says why, and the caller takes another route."""
+
+    def __init__(self, reason):
+        self.reason = reason
+
+    def __repr__(self):
+        return 'InflateNotChunked(%r)' % (self.reason,)
+
+
+def inflate_sync_scan(comp):
+    """The candidate segment starts of a raw DEFLATE stream: int64 [n] on the device, sorted -- offset 0 and every offset behind the four
+    bytes 00 00 FF FF (vs_inflate_sync_scan, once to count and once to list; the sort of the short list is torch's)."""
+    require_cuda(comp)
+    if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous():
+        raise _lib.VarsepHipError('inflate_sync_scan: a contiguous uint8 [bytes] tensor expected')
+    lib, device, n = _lib.load_library(), comp.device, comp.numel()
+    with torch.cuda.device(device):
+        count = torch.zeros((2,), dtype=torch.int64, device=device)
+        keep = comp if n else torch.zeros((1,), dtype=torch.uint8, device=device)
+        e0 = _pb()
+        check(lib.vs_inflate_sync_scan(keep.data_ptr(), n, None, 0, count.data_ptr(), stream_ptr()), 'vs_inflate_sync_scan')
+        _pe(e0, 'vs_inflate_sync_scan', nbytes=float(n))
+        found = int(count[0].item())
+        cand = torch.empty((found,), dtype=torch.int64, device=device)
+        e0 = _pb()
+        check(lib.vs_inflate_sync_scan(keep.data_ptr(), n, cand.data_ptr(), found, count[1:].data_ptr(), stream_ptr()), 'vs_inflate_sync_scan')
+        _pe(e0, 'vs_inflate_sync_scan', nbytes=float(n))
+        return torch.sort(cand).values
+
+
+def inflate_raw(comp, out_bytes, crc=None, batch=None, trace=None):
+    """The `out_bytes` bytes of the raw DEFLATE stream `comp` (uint8 [bytes] on the device), decoded in parallel at its sync markers: uint8
+    [out_bytes] on the device, or an InflateNotChunked when the segments do not chain (the caller then decodes the stream another way).
+    Every candidate start (inflate_sync_scan) is decoded by one wave without knowing what came before it (vs_inflate_segments), `batch`
+    candidates per launch (default INFLATE_BATCH) with one download of the report words per batch.  The chain is walked here: from
+    candidate 0 the next segment is the candidate that starts where the last one ended; every step needs status 0, an end that is a
+    candidate and no reference further back than the bytes produced so far, and the chain must close with a final segment that ends at
+    the stream's last byte after exactly out_bytes.  Candidates off the chain (00 00 FF FF inside data) are decoded and ignored.  The
+    chain's segments are copied to their prefix-sum offsets (vs_inflate_place) and their external bytes filled in chain order
+    (vs_inflate_resolve).  crc: the CRC-32 the result must have (ops.crc32); a mismatch after a valid chain raises zipfile.BadZipFile.
+    trace: optional list that receives (first candidate index, report words int64 [n, 6] as a host array) per decoded batch."""
+    import numpy as np
+    require_cuda(comp)
+    out_bytes = int(out_bytes)
+    batch = INFLATE_BATCH if batch is None else int(batch)
+    if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous() or out_bytes < 0 or batch < 1 or batch > INFLATE_MAX_BATCH:
+        raise _lib.VarsepHipError('inflate_raw: comp uint8 [bytes] contiguous, out_bytes >= 0 and batch in 1 .. %d expected' % INFLATE_MAX_BATCH)
+    lib, device, n = _lib.load_library(), comp.device, comp.numel()
+    S, RW = INFLATE_SLOT_BYTES, INFLATE_REPORT_WORDS
+    with torch.cuda.device(device):
+        cand = inflate_sync_scan(comp)
+        starts = cand.cpu().numpy()
+        n_cand = starts.size
+        rows = min(batch, n_cand)
+        out = torch.empty((max(out_bytes, 1),), dtype=torch.uint8, device=device)[:out_bytes]
+        slots = torch.empty((rows, S), dtype=torch.uint8, device=device)
+        marks = torch.empty((rows, S), dtype=torch.int16, device=device)
+        words = torch.empty((rows, RW), dtype=torch.int64, device=device)
+        total, nxt, final = 0, 0, False                                     # bytes produced, the candidate the chain is at, closed
+        for lo in range(0, n_cand, batch):
+            if final:
+                break
+            if nxt >= lo + batch:                                           # a batch of off-chain candidates only: nothing of it is needed
+                continue
+            m = min(batch, n_cand - lo)
+            e0 = _pb()
+            check(lib.vs_inflate_segments(comp.data_ptr(), n, cand[lo:].data_ptr(), m, slots.data_ptr(), S, marks.data_ptr(), words.data_ptr(),
+                                          stream_ptr()), 'vs_inflate_segments')
+            _pe(e0, 'vs_inflate_segments', nbytes=float(n) / max(1, -(-n_cand // batch)) + float(m) * S)
+            w = words[:m].cpu().numpy()
+            if trace is not None:
+                trace.append((lo, w.copy()))
+            plan, ext = [], []                                              # (slot, size, offset) of the chain's segments in this batch
+            follow = np.searchsorted(starts, w[:, 1])                       # per candidate: the candidate that starts where it ends, if any
+            is_start = (starts[np.minimum(follow, n_cand - 1)] == w[:, 1]) & (follow < n_cand)
+            rows_w, follow, is_start = w.tolist(), follow.tolist(), is_start.tolist()
+            while not final and lo <= nxt < lo + m:
+                status, end, fin, produced, externals, reach = rows_w[nxt - lo]
+                if status != 0:
+                    why = 'more than %d bytes before a sync marker' % S if status == 8 else INFLATE_STATUS.get(status, 'status %d' % status)
+                    return InflateNotChunked('segment at %d: %s' % (starts[nxt], why))
+                if reach > total:
+                    return InflateNotChunked('segment at %d reaches %d bytes back, %d bytes into the stream' % (starts[nxt], reach, total))
+                if total + produced > out_bytes:
+                    return InflateNotChunked('more than the %d bytes of the record' % out_bytes)
+                plan.append((nxt - lo, produced, total))
+                if externals:
+                    ext.append(plan[-1])
+                total += produced
+                if fin:
+                    final = True
+                    if end != n:
+                        return InflateNotChunked('the final block ends at %d of %d bytes' % (end, n))
+                    break
+                k = follow[nxt - lo]
+                if not is_start[nxt - lo] or k <= nxt:
+                    return InflateNotChunked('segment at %d ends at %d, which is no sync marker' % (starts[nxt], end))
+                nxt = k
+            for entry, table in (('vs_inflate_place', plan), ('vs_inflate_resolve', ext)):
+                if not table:
+                    continue
+                t = torch.from_numpy(np.ascontiguousarray(np.asarray(table, dtype=np.int64).T)).to(device)
+                e0 = _pb()
+                if entry == 'vs_inflate_place':
+                    check(lib.vs_inflate_place(slots.data_ptr(), S, m, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), len(table), out.data_ptr(),
+                                               out_bytes, stream_ptr()), entry)
+                else:
+                    check(lib.vs_inflate_resolve(marks.data_ptr(), m, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), len(table), out.data_ptr(),
+                                                 out_bytes, stream_ptr()), entry)
+                _pe(e0, entry, nbytes=2.0 * sum(r[1] for r in table))
+        if not final:
+            return InflateNotChunked('the chain leaves the candidates before a final block')
+        if total != out_bytes:
+            return InflateNotChunked('%d bytes where the record says %d' % (total, out_bytes))
+    if crc is not None and crc32(out) != (int(crc) & 0xFFFFFFFF):
+        import zipfile
+        raise zipfile.BadZipFile('inflate_raw: bad CRC-32 of %d decoded bytes' % out_bytes)
+    return out
+
+
+def u8_tn_to_f32_nt(x):
+    """uint8 [T, N, ...] on the device -> fp32 [N, T, ...] (vs_u8_tn_to_f32_nt, csrc/vs_data.hip): what `[x[:, i].astype(np.single) for i ...]` stacks on the host."""
+    require_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() < 2 or not x.is_contiguous():
+        raise _lib.VarsepHipError('u8_tn_to_f32_nt: a contiguous uint8 tensor of at least two dimensions expected')
+    T, N = int(x.shape[0]), int(x.shape[1])
+    inner = x.numel() // (T * N) if T * N else 0
+    with torch.cuda.device(x.device):
+        out = torch.empty((N, T) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        if out.numel():
+            e0 = _pb()
+            check(_lib.load_library().vs_u8_tn_to_f32_nt(x.data_ptr(), T, N, inner, out.data_ptr(), stream_ptr()), 'vs_u8_tn_to_f32_nt')
+            _pe(e0, 'vs_u8_tn_to_f32_nt', nbytes=5.0 * x.numel())
+    return out
+
+
 # ---- PNG encoding on the device (csrc/vs_png_encode.hip) ---------------------------------------------------------------------------
 PNG_FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': 5}
 PNG_FIXED_BYTES = 65              # 57 + 8: everything of a file but its compressed chunks

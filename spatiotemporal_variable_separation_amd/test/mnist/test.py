@@ -14,13 +14,15 @@ Who compresses the six frame files: the environment variable VARSEP_NPZ_COMPRESS
 `main`.  `host` (the default) copies every batch's uint8 frames to the host and writes with np.savez_compressed, as before; `device` keeps
 them in HBM, compresses them there and downloads only the compressed bytes.  Names, keys, dtypes, shapes and the arrays np.load gives are
 the same; measurements and the sizes of the device-written files: profiles/eval_npz_timing.md.
+Who decompresses the test-set file D/[s]mmnist_test_*.npz: VARSEP_NPZ_LOAD=host|device (utils/loadz.py), read once at the same place.
+`host` (the default) is np.load and the host conversion, as before; `device` uploads the compressed bytes and inflates them in HBM.
 """
 import os
 
 import torch
 
 from ...data.moving_mnist import MovingMNIST
-from ...utils import savez
+from ...utils import loadz, savez
 from ...utils.metrics import frame_metrics
 from ..utils import U8Frames, add_precision_flag, base_parser, load_model, load_xp_config, print_results, seed_all, setup_device
 
@@ -33,15 +35,17 @@ def split_data_dir(data_dir):
     return (data_dir[len(GENERATED):], True) if data_dir.startswith(GENERATED) else (data_dir, False)
 
 
-def load_dataset(args, train=False, device='cuda', stochastic=False):
+def load_dataset(args, train=False, device='cuda', stochastic=False, load=None):
     """stochastic: the command line's --mnist_stochastic, never the `mnist_stochastic` that training saved in params.json (`args` is that
-    configuration): an existing experiment is evaluated on what it was evaluated on before."""
+    configuration): an existing experiment is evaluated on what it was evaluated on before.  load: who decompresses the test-set file
+    (utils/loadz.npz_loader), handed on only when it was given."""
     data_dir, generated = split_data_dir(args.data_dir)
     if generated and not train:      # make_test_set.py's defaults: seed 42, 100 frames, frame size 64, speed 4
         return MovingMNIST.generated(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, args.n_object, device,
                                      deterministic=not stochastic)
+    extra = {} if load is None or train else {'load': load}
     return MovingMNIST.make_dataset(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, not stochastic, args.n_object, train,
-                                    device=device)
+                                    device=device, **extra)
 
 
 def add_stochastic_flag(p):
@@ -67,13 +71,14 @@ def test_batches(test_dataset, batch_size):
 
 def main(args):
     compress = savez.npz_compressor()         # who compresses the six frame files: read once, a bad value is refused before any work
+    load = loadz.npz_loader()                 # who decompresses the test-set file (VARSEP_NPZ_LOAD): read once, here
     device = setup_device(args)
     seed_all(args.test_seed)
     xp_config = load_xp_config(args, device, args.nt_pred)
 
     print('Loading data...')
     stochastic = bool(getattr(args, 'mnist_stochastic', False))
-    test_dataset = load_dataset(xp_config, train=False, device=device, stochastic=stochastic)
+    test_dataset = load_dataset(xp_config, train=False, device=device, stochastic=stochastic, load=load)
     train_dataset = load_dataset(xp_config, train=True, device=device, stochastic=stochastic)
     nc = 1
     size = 64

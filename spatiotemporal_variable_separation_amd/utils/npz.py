@@ -8,10 +8,15 @@ is over header + data, so a producer that computes the data's CRC elsewhere star
 written into the local header by seeking back once the pieces are consumed (no data descriptors).  ZIP64 extra fields and end records are
 written when a size or an offset needs them (np.savez allows zip64; `--seq_len 250` of the Moving-MNIST test set is a 5.1 GB member), or
 always with force_zip64=True.
+
+The reader's half, host-only as well: `read_directory` lists a file's members from its central directory (methods 0 and 8, the ZIP64
+fields above) with the offset of each member's data, and `parse_npy_header` reads the .npy 1.0 / 2.0 header in front of an array's bytes.
+utils/loadz.py decides from them which members the device decodes.
 """
 import io
 import struct
 import time
+import zipfile
 import zlib
 from collections import namedtuple
 
@@ -117,3 +122,103 @@ def write_npz(path, members, force_zip64=False):
                 count, cd_size, cd_offset = 0xFFFF, _LIMIT, _LIMIT
         f.write(struct.pack('<4sHHHHIIH', b'PK\x05\x06', 0, 0, count, count, cd_size, cd_offset, 0))
     return [(name.decode('utf-8'), usize, csize) for name, _, csize, usize, _, _ in records]
+
+
+# ---- reading ------------------------------------------------------------------------------------------------------------------------
+# name: as in the archive ('sequences.npy'); method: 0 stored, 8 deflated; crc32, csize, usize: of the central record (ZIP64 resolved);
+# data_offset: where the member's csize bytes start in the file
+Entry = namedtuple('Entry', 'name method crc32 csize usize data_offset')
+NpyHeader = namedtuple('NpyHeader', 'shape fortran_order dtype header_bytes')
+
+
+def _zip64_extra(extra, wanted):
+    """The values of the ZIP64 extra field (id 1) for the record fields that are all-ones, in the order of `wanted`."""
+    at = 0
+    while at + 4 <= len(extra):
+        tag, size = struct.unpack_from('<HH', extra, at)
+        if tag == 1:
+            if size < 8 * len(wanted):
+                raise zipfile.BadZipFile('ZIP64 extra field of %d bytes for %d values' % (size, len(wanted)))
+            return struct.unpack_from('<%dQ' % len(wanted), extra, at + 4)
+        at += 4 + size
+    raise zipfile.BadZipFile('a record needs ZIP64 fields that are not there')
+
+
+def read_directory(path):
+    """[Entry] of the zip file `path`, in the order of its central directory.  Covered: methods 0 and 8, ZIP64 end records and extra
+    fields; refused (zipfile.BadZipFile): no end record, several disks, encrypted members, a local record that disagrees on the name."""
+    out = []
+    with open(path, 'rb') as f:
+        f.seek(0, 2)
+        size = f.tell()
+        tail_at = max(0, size - (22 + 65535))
+        f.seek(tail_at)
+        tail = f.read()
+        at = tail.rfind(b'PK\x05\x06')
+        if at < 0 or at + 22 > len(tail):
+            raise zipfile.BadZipFile('%s: no end-of-central-directory record' % path)
+        disk, cd_disk, here, count, cd_size, cd_offset, _ = struct.unpack_from('<HHHHIIH', tail, at + 4)
+        if here == 0xFFFF or count == 0xFFFF or cd_size == _LIMIT or cd_offset == _LIMIT:
+            loc = tail_at + at - 20
+            if loc < 0:
+                raise zipfile.BadZipFile('%s: ZIP64 locator missing' % path)
+            f.seek(loc)
+            sig, _, end64, disks = struct.unpack('<4sIQI', f.read(20))
+            if sig != b'PK\x06\x07' or disks != 1:
+                raise zipfile.BadZipFile('%s: ZIP64 locator missing or several disks' % path)
+            f.seek(end64)
+            rec = f.read(56)
+            sig, _, _, _, disk, cd_disk, here, count, cd_size, cd_offset = struct.unpack('<4sQHHIIQQQQ', rec)
+            if sig != b'PK\x06\x06':
+                raise zipfile.BadZipFile('%s: ZIP64 end record missing' % path)
+        if disk != 0 or cd_disk != 0 or here != count:
+            raise zipfile.BadZipFile('%s: an archive of several disks' % path)
+        if cd_offset + cd_size > size:
+            raise zipfile.BadZipFile('%s: the central directory leaves the file' % path)
+        f.seek(cd_offset)
+        cd = f.read(cd_size)
+        at = 0
+        for _ in range(count):
+            if at + 46 > len(cd) or cd[at:at + 4] != b'PK\x01\x02':
+                raise zipfile.BadZipFile('%s: bad central record' % path)
+            (_, _, flags, method, _, _, crc, csize, usize, n_name, n_extra, n_comment, disk_start, _, _, offset) = \
+                struct.unpack_from('<HHHHHHIIIHHHHHII', cd, at + 4)
+            name = cd[at + 46:at + 46 + n_name]
+            extra = cd[at + 46 + n_name:at + 46 + n_name + n_extra]
+            at += 46 + n_name + n_extra + n_comment
+            wanted = [k for k, v in (('usize', usize), ('csize', csize), ('offset', offset)) if v == _LIMIT]
+            if disk_start == 0xFFFF:
+                wanted.append('disk')
+            if wanted:
+                wide = dict(zip(wanted, _zip64_extra(extra, wanted)))
+                usize, csize, offset = wide.get('usize', usize), wide.get('csize', csize), wide.get('offset', offset)
+            if flags & 1:
+                raise zipfile.BadZipFile('%s: %s is encrypted' % (path, name))
+            if method not in (0, 8):
+                raise zipfile.BadZipFile('%s: %s uses method %d' % (path, name, method))
+            f.seek(offset)
+            local = f.read(30)
+            if len(local) != 30 or local[:4] != b'PK\x03\x04':
+                raise zipfile.BadZipFile('%s: bad local record of %s' % (path, name))
+            l_name, l_extra = struct.unpack_from('<HH', local, 26)
+            if f.read(l_name) != name:
+                raise zipfile.BadZipFile('%s: the local record of %s has another name' % (path, name))
+            data_offset = offset + 30 + l_name + l_extra
+            if data_offset + csize > size:
+                raise zipfile.BadZipFile('%s: %s leaves the file' % (path, name))
+            out.append(Entry(name.decode('utf-8' if flags & 0x800 else 'cp437'), method, crc, csize, usize, data_offset))
+    return out
+
+
+def parse_npy_header(raw):
+    """NpyHeader of the first bytes of a .npy file (versions 1.0 and 2.0; `raw` holds at least the header): numpy's own header readers.
+    ValueError for anything else."""
+    f = io.BytesIO(bytes(raw))
+    version = np.lib.format.read_magic(f)
+    if version == (1, 0):
+        shape, fortran, dtype = np.lib.format.read_array_header_1_0(f)
+    elif version == (2, 0):
+        shape, fortran, dtype = np.lib.format.read_array_header_2_0(f)
+    else:
+        raise ValueError('.npy version %s' % (version,))
+    return NpyHeader(tuple(int(v) for v in shape), bool(fortran), dtype, f.tell())
