@@ -752,6 +752,21 @@ int vs_adam_set_max_blocks(int blocks);
 int vs_gemm_adam(int compute, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int layout_a, const void* B, int64_t ldb,
                  int layout_b, float alpha, float* param, float* exp_avg, float* exp_avg_sq, void* shadow, int shadow_dtype,
                  const int32_t* step, int32_t skipped, double lr, double beta1, double beta2, double eps, void* stream);
+/* vs_gemm_adam as a launch that does NOT fill the chip, for running beside a latency-bound kernel: same operands, same arithmetic, bit
+ * for bit the same result; `ldp` is the leading dimension of param / exp_avg / exp_avg_sq / shadow (>= N, a multiple of 4; those
+ * pointers 16-byte, shadow 8-byte aligned, VS_ERR_UNSUPPORTED otherwise).
+ *   max_workgroups    the grid is at most this many workgroups, each of which walks the 128 x 128 tiles t = b, b + grid, ... in the
+ *                     XCD-aware tile order; each holds all 160 KiB of a CU's LDS, so it shares a CU with no kernel that uses LDS
+ *   pieces_in_flight  1, 2 or 4 row pieces of optimizer state requested ahead of the update (vs_gemm_adam: 4)
+ *   cache_policy      0 plain, 1 non-temporal loads and stores of param, exp_avg, exp_avg_sq and shadow
+ * The exchange guard is read ONCE per workgroup, before its first tile.  An exchange that times out in a kernel running BESIDE this
+ * launch therefore does not stop it, and one that times out just before it stops some workgroups and not others: the parameter of
+ * that one step may be updated in some tiles and not in others (vs_gemm_adam: the whole tensor or nothing).  Later steps are skipped
+ * as a whole either way.                                                                                                        */
+int vs_gemm_adam_paced(int compute, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int layout_a, const void* B, int64_t ldb,
+                       int layout_b, float alpha, float* param, float* exp_avg, float* exp_avg_sq, void* shadow, int64_t ldp,
+                       int shadow_dtype, const int32_t* step, int32_t skipped, double lr, double beta1, double beta2, double eps,
+                       int max_workgroups, int pieces_in_flight, int cache_policy, void* stream);
 int vs_loss_scale_update(float* scale_state, float growth_factor, float backoff_factor, int growth_interval, void* stream);
 
 /* Fused frame losses (train.py:85-86 ae_loss MSE and train.py:139 forecast MSE in one pass over the decoded frames).

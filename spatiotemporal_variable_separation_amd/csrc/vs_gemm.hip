@@ -282,6 +282,38 @@ extern "C" int vs_gemm_adam(int compute, int64_t M, int64_t N, int64_t K, const 
     return launch_plan(compute, call, mp, epi, nullptr);
 }
 
+// vs_gemm_adam as a launch that is deliberately NOT chip-filling (include/varsep_hip.h): the same tiles, the same arithmetic, bit for bit.
+extern "C" int vs_gemm_adam_paced(int compute, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, int layout_a, const void* B, int64_t ldb,
+                                  int layout_b, float alpha, float* param, float* exp_avg, float* exp_avg_sq, void* shadow, int64_t ldp,
+                                  int shadow_dtype, const int32_t* step, int32_t skipped, double lr, double beta1, double beta2, double eps,
+                                  int max_workgroups, int pieces_in_flight, int cache_policy, void* stream_) {
+    VS_CHECK_ARG(compute == VS_BF16 || compute == VS_F16, "vs_gemm_adam_paced: 16-bit compute types only (%d)", compute);
+    VS_CHECK_ARG(M > 0 && N > 0 && K > 0, "vs_gemm_adam_paced: M, N, K must be positive");
+    VS_CHECK_ARG(A && B && param && exp_avg && exp_avg_sq && step, "vs_gemm_adam_paced: null pointer");
+    VS_CHECK_ARG((layout_a == LR || layout_a == LS) && (layout_b == LR || layout_b == LS), "vs_gemm_adam_paced: bad layout");
+    VS_CHECK_ARG(lda >= (layout_a == LR ? K : M) && ldb >= (layout_b == LR ? K : N) && ldp >= N, "vs_gemm_adam_paced: leading dimension too small");
+    VS_CHECK_ARG(!shadow || shadow_dtype == VS_BF16 || shadow_dtype == VS_F16, "vs_gemm_adam_paced: bad shadow dtype");
+    VS_CHECK_ARG(max_workgroups >= 1, "vs_gemm_adam_paced: max_workgroups must be positive (%d)", max_workgroups);
+    VS_CHECK_ARG(pieces_in_flight == 1 || pieces_in_flight == 2 || pieces_in_flight == 4, "vs_gemm_adam_paced: pieces_in_flight is 1, 2 or 4 (%d)", pieces_in_flight);
+    VS_CHECK_ARG(cache_policy == 0 || cache_policy == 1, "vs_gemm_adam_paced: cache_policy is 0 (plain) or 1 (non-temporal) (%d)", cache_policy);
+    if (!dma_operands_ok(GEMM_MID, A, lda, layout_a, 0, B, ldb, layout_b, 0, M, N, K))
+        return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_adam_paced: operands do not fit the LDS-DMA loader (16-byte alignment, multiples of 8)");
+    if ((((uintptr_t)param | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0 || ((uintptr_t)shadow & 7) != 0 || (ldp & 3) != 0)
+        return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_adam_paced: parameter and moments 16-byte aligned, operand copy 8-byte aligned, ldp a multiple of 4");
+    if (vs_cdiv(M, 128) * vs_cdiv(N, 128) > 0x7fffffffll) return vs_fail(VS_ERR_UNSUPPORTED, "vs_gemm_adam_paced: too many tiles");
+    Epi epi = plain_epi(param, ldp, VS_F32, alpha);
+    epi.adam_m = exp_avg; epi.adam_v = exp_avg_sq; epi.adam_shadow = (unsigned short*)shadow; epi.adam_shadow_dtype = shadow_dtype;
+    epi.adam_step = step; epi.adam_skipped = skipped; epi.adam_guard = vs_g_exchange_guard;
+    epi.adam_lr = lr; epi.adam_beta1 = beta1; epi.adam_beta2 = beta2; epi.adam_eps = (float)eps;
+    const int rc = with_types(compute, layout_a, layout_b, [&](auto ct, auto la, auto lb) -> int {
+        return mid_launch_paced<decltype(ct)::value, decltype(la)::value, decltype(lb)::value>(A, lda, B, ldb, M, N, K, epi, max_workgroups, pieces_in_flight,
+                                                                                                cache_policy, (hipStream_t)stream_);
+    });
+    if (rc != VS_OK) return rc;
+    VS_CHECK_LAUNCH("vs_gemm_adam_paced");
+    return VS_OK;
+}
+
 // The decoder's last Linear layer with the frame losses in its epilogue (recorded MLP-family step): frames = act(A W^T + bias) is row
 // r = (b, g) of the decoded stack [B, G, N = D] (reference: networks/mlp_encdec.py:43-50 + train.py:85-86, 139); instead of storing the
 // 54 MB of fp32 frames and reading them back with the targets (vs_train_losses_fwd_grad), the 256 x 256 tile kernel compares its result

@@ -89,18 +89,13 @@ struct MidOperand {
 
 // ST ring slots of 16 KiB: 5 (80 KiB) where two workgroups share a CU, 10 (all 160 KiB) where the launch has at most one per CU --
 // what a CU pulls through LDS-DMA is (bytes in flight) / (1.3-2 us), so the ring is as deep as the LDS allows.
-template <int CT, int LA, int LB, bool NCHW, int ST, bool ADAM>
-__global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap, int64_t lda, const unsigned short* Bp, int64_t ldb, int64_t M, int64_t N,
-                                                          int64_t K, int k_tiles_per_split, int tiles_n, Epi epi_in, float* slabs, int64_t a_chan_hw) {
-    // XCD runs over (split, tile): the workgroups of one XCD share K chunks, so a chunk of A and of B is fetched into ONE L2
-    unsigned tile, bz = blockIdx.z;
-    if (epi_in.xcd_runs) {
-        const unsigned t = big_tile_of(blockIdx.x + gridDim.x * blockIdx.z, gridDim.x * gridDim.z);
-        bz = t / gridDim.x;
-        tile = t - bz * gridDim.x;
-    } else {
-        tile = big_tile_of(blockIdx.x, gridDim.x);
-    }
+//
+// One output tile of one workgroup: `tile` of split / batch slice `bz`.  PIECES / NT belong to the paced form of the fused optimizer
+// launch (gemm_mid_kernel below): PIECES > 0 = the workgroup walks several tiles and calls this once per tile, with that many row
+// pieces of optimizer state requested ahead; NT = parameter, moments and operand copy go through non-temporal loads and stores.
+template <int CT, int LA, int LB, bool NCHW, int ST, bool ADAM, int PIECES, bool NT>
+__device__ __forceinline__ void mid_tile(unsigned tile, unsigned bz, const unsigned short* Ap, int64_t lda, const unsigned short* Bp, int64_t ldb, int64_t M,
+                                         int64_t N, int64_t K, int k_tiles_per_split, int tiles_n, const Epi& epi_in, float* slabs, int64_t a_chan_hw) {
     int zsplit = bz;
     int batch = 0;
     if (epi_in.splits_per_batch > 0) {
@@ -228,7 +223,8 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
     if constexpr (ADAM) {
         // fused optimizer (vs_gemm_adam; an instantiation of its own, so that profiles tell it from the plain GEMM): the tile is
         // a block of the parameter's gradient
-        if (epi.adam_guard && *epi.adam_guard != 0u) return;          // an exchange of this step timed out: no update (vs_common.h)
+        // an exchange of this step timed out: no update (vs_common.h); the paced form has read the word once, before its first tile
+        if (PIECES == 0 && epi.adam_guard && *epi.adam_guard != 0u) return;
         const AdamCoef coef = vs_adam_coef(epi.adam_lr, epi.adam_beta1, epi.adam_beta2, epi.adam_eps, (double)(epi.adam_step[0] + 1 - epi.adam_skipped));
         // The update is a pure HBM stream (24 B in, 26 B out per parameter) and a lane's 16 row pieces are independent: the state of FOUR
         // pieces (12 x 16 B per lane) is requested before the previous four are updated and stored, so a wave keeps 12 KiB of reads in
@@ -237,7 +233,8 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
         // at the next use, which serialises the groups again)
         if (m0 + 128 <= M && nn + 3 < N && ((epi.ldc | nn) & 3) == 0 &&
             (((uintptr_t)epi.C | (uintptr_t)epi.adam_m | (uintptr_t)epi.adam_v) & 15) == 0 && (!epi.adam_shadow || ((uintptr_t)epi.adam_shadow & 7) == 0)) {
-            constexpr int G = 4;
+            constexpr int G = PIECES ? PIECES : 4;                  // a compile-time choice: see above about branches around requests
+            static_assert(G == 1 || G == 2 || G == 4, "row pieces of state in flight: 1, 2 or 4");
             f32x4 p[2][G], mm[2][G], vv[2][G];
             const int64_t idx0 = (m0 + wr * 64 + (lane >> 4)) * epi.ldc + nn;           // row piece (g, t) lies (g * G + t) * 4 rows further
             const int64_t rstep = 4 * epi.ldc;
@@ -245,8 +242,14 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
             const float* __restrict__ Mp = epi.adam_m + idx0;
             const float* __restrict__ Vp = epi.adam_v + idx0;
             const int sdt = epi.adam_shadow_dtype;
-            auto ld4 = [&](const float* q) { return *reinterpret_cast<const f32x4*>(q); };
-            auto st4 = [&](float* q, const f32x4& v) { *reinterpret_cast<f32x4*>(q) = v; };
+            auto ld4 = [&](const float* q) {
+                if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
+                else return *reinterpret_cast<const f32x4*>(q);
+            };
+            auto st4 = [&](float* q, const f32x4& v) {
+                if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(q));
+                else *reinterpret_cast<f32x4*>(q) = v;
+            };
 #pragma unroll
             for (int t = 0; t < G; ++t) {
                 p[0][t] = ld4(Pp + t * rstep);
@@ -281,7 +284,8 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
                     st4(epi.adam_v + idx, ve);
                     if (epi.adam_shadow) {
                         const u16x4 h = {vs_f2h(pe[0], sdt), vs_f2h(pe[1], sdt), vs_f2h(pe[2], sdt), vs_f2h(pe[3], sdt)};
-                        *reinterpret_cast<u16x4*>(epi.adam_shadow + idx) = h;
+                        if constexpr (NT) __builtin_nontemporal_store(h, reinterpret_cast<u16x4*>(epi.adam_shadow + idx));
+                        else *reinterpret_cast<u16x4*>(epi.adam_shadow + idx) = h;
                     }
                 }
             }
@@ -327,6 +331,50 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap,
     }
 }
 
+// PIECES == 0: one tile per workgroup, grid = (tiles, 1, splits x batch).
+// PIECES > 0 (ADAM only, one split, no batch): the paced form, grid = (at most max_workgroups, 1, 1); workgroup b walks the tiles
+// t = b, b + gridDim.x, ... in the same XCD-aware order (b and b + 8 share an XCD whatever the grid: tile index t keeps b's XCD when the
+// grid is a multiple of 8).  Between two tiles the workgroup drains its stores (on this ISA they count in vmcnt, and the counted waits of
+// the ring assume nothing else is outstanding) and meets at a barrier: the epilogue staged the accumulators in the LDS that the next
+// tile's prologue requests into.
+template <int CT, int LA, int LB, bool NCHW, int ST, bool ADAM, int PIECES = 0, bool NT = false>
+__global__ __launch_bounds__(256) void gemm_mid_kernel(const unsigned short* Ap, int64_t lda, const unsigned short* Bp, int64_t ldb, int64_t M, int64_t N,
+                                                          int64_t K, int k_tiles_per_split, int tiles_n, Epi epi_in, float* slabs, int64_t a_chan_hw) {
+    if constexpr (PIECES == 0) {
+        // XCD runs over (split, tile): the workgroups of one XCD share K chunks, so a chunk of A and of B is fetched into ONE L2
+        unsigned tile, bz = blockIdx.z;
+        if (epi_in.xcd_runs) {
+            const unsigned t = big_tile_of(blockIdx.x + gridDim.x * blockIdx.z, gridDim.x * gridDim.z);
+            bz = t / gridDim.x;
+            tile = t - bz * gridDim.x;
+        } else {
+            tile = big_tile_of(blockIdx.x, gridDim.x);
+        }
+        mid_tile<CT, LA, LB, NCHW, ST, ADAM, 0, false>(tile, bz, Ap, lda, Bp, ldb, M, N, K, k_tiles_per_split, tiles_n, epi_in, slabs, a_chan_hw);
+    } else {
+        static_assert(ADAM && !NCHW, "the paced form is the fused optimizer launch");
+        // the guard word, once per workgroup: thread 0 reads it and hands the answer round through the (still unused) ring, so that all
+        // waves leave or none (a wave that left alone would leave the others at the barriers below).  An exchange that times out while
+        // this launch runs stops only the workgroups that have not started yet.
+        extern __shared__ __attribute__((aligned(16))) char smem[];
+        volatile unsigned* raised = reinterpret_cast<volatile unsigned*>(smem);
+        if (threadIdx.x == 0) *raised = (epi_in.adam_guard && *epi_in.adam_guard != 0u) ? 1u : 0u;
+        __syncthreads();
+        const bool skip = *raised != 0u;
+        __syncthreads();                             // all have read it: the first tile's requests may land there
+        if (skip) return;
+        const unsigned tiles = (unsigned)((M + 127) / 128) * (unsigned)tiles_n;
+        for (unsigned t = blockIdx.x; t < tiles; t += gridDim.x) {
+            if (t != blockIdx.x) {
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            mid_tile<CT, LA, LB, false, ST, true, PIECES, NT>(big_tile_of(t, tiles), 0u, Ap, lda, Bp, ldb, M, N, K, k_tiles_per_split, tiles_n, epi_in, slabs,
+                                                              a_chan_hw);
+        }
+    }
+}
+
 // launch (shared by vs_gemm.hip and the convolution weight gradients of vs_conv.hip); a_chan_hw > 0: A is the channel-rows view of an
 // NCHW tensor with M channels and planes of a_chan_hw elements (lda is ignored)
 template <int CT, int LA, int LB, bool NCHW = false>
@@ -360,6 +408,41 @@ int mid_launch(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M
             return epi.adam_m ? go(gemm_mid_kernel<CT, LA, LB, false, 5, true>, 5, set_adam)
                    : stages == 10 ? go(gemm_mid_kernel<CT, LA, LB, false, 10, false>, 10, set10)
                                   : go(gemm_mid_kernel<CT, LA, LB, false, 5, false>, 5, set5);
+        }
+    }
+}
+
+// The paced form of the fused optimizer launch (vs_gemm_adam_paced): at most `max_workgroups` workgroups on the 160 KiB ring -- one per
+// CU, and none beside a workgroup that holds LDS of its own -- with `pieces` (1, 2, 4) row pieces of state in flight and cache policy
+// `policy` (0 plain, 1 non-temporal).
+template <int CT, int LA, int LB>
+int mid_launch_paced(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const Epi& epi, int max_workgroups,
+                     int pieces, int policy, hipStream_t stream) {
+    if constexpr (CT == VS_F32) {
+        return vs_fail(VS_ERR_UNSUPPORTED, "the 128x128 LDS-DMA ring tile is a 16-bit kernel");
+    } else {
+        constexpr int ST = 10, lds = ST * MID_TILE_BYTES;
+        const int64_t tiles_m = vs_cdiv(M, 128), tiles_n = vs_cdiv(N, 128);
+        const int64_t wgs = tiles_m * tiles_n < max_workgroups ? tiles_m * tiles_n : max_workgroups;
+        auto go = [&](auto kfn, bool& attr_set) -> int {
+            if (!attr_set) {
+                if (hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+                    return vs_fail(VS_ERR_LAUNCH, "cannot raise the dynamic LDS limit to %d bytes", lds);
+                attr_set = true;
+            }
+            hipLaunchKernelGGL(kfn, dim3((unsigned)wgs), dim3(256), lds, stream, (const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, N, K,
+                               (int)vs_cdiv(K, BIG_BK), (int)tiles_n, epi, (float*)nullptr, (int64_t)0);
+            return VS_OK;
+        };
+        static bool set[3][2] = {};
+        switch (pieces * 2 + (policy ? 1 : 0)) {
+            case 2: return go(gemm_mid_kernel<CT, LA, LB, false, ST, true, 1, false>, set[0][0]);
+            case 3: return go(gemm_mid_kernel<CT, LA, LB, false, ST, true, 1, true>, set[0][1]);
+            case 4: return go(gemm_mid_kernel<CT, LA, LB, false, ST, true, 2, false>, set[1][0]);
+            case 5: return go(gemm_mid_kernel<CT, LA, LB, false, ST, true, 2, true>, set[1][1]);
+            case 8: return go(gemm_mid_kernel<CT, LA, LB, false, ST, true, 4, false>, set[2][0]);
+            case 9: return go(gemm_mid_kernel<CT, LA, LB, false, ST, true, 4, true>, set[2][1]);
+            default: return vs_fail(VS_ERR_ARG, "pieces in flight: 1, 2 or 4 (%d)", pieces);
         }
     }
 }

@@ -245,10 +245,28 @@ def compute_dtype():
 #     E_s encoder, its backward overlaps the decoder/encoder weight gradients.
 # Only valid when every parameter receives ONE gradient per step (the batched MLP-family step) and without hook-driven
 # gradient all-reduce; `train._compute_losses_mlp_batched` / `GraphedStep` switch it on, everything else leaves it off.
-_SIDE = {'on': False, 'lanes': [], 'next_lane': 0, 'rollout': None, 'hold': False, 'held': [], 'hold_main': None, 'late': []}
+_SIDE = {'on': False, 'lanes': [], 'next_lane': 0, 'rollout': None, 'hold': False, 'held': [], 'hold_main': None, 'late': [], 'pace': None}
 # Deferred gradient work is spread over a few streams ("lanes", one per Linear chain / integrator backward in turn): most of it
 # is GEMMs of 10-50 us that fill a fraction of the chip each, and one stream would run them one after the other.
 N_LANES = 3
+
+# The held fused first-layer update (E_s's 640 MB weight-gradient + Adam launch in the WaveEq step) as a paced launch
+# (ops.gemm_adam_paced) that is released with the other held work instead of behind the integrator's backward kernel:
+# (max_workgroups, pieces_in_flight, cache_policy), chosen from the sweep in profiles/r07_waveeq_paced_update.md.  In the replayed graph
+# its lane shares a hardware queue with that kernel, so it runs 289 us beside E_t's backward chain and the first half of E_t's update,
+# with non-temporal state traffic (WaveEq step, same box, processes alternating: 1.2929-1.2956 vs 1.3095-1.3133 ms).  Caps of 16-64
+# workgroups lose (the launch is 174 GFLOP: 16 us per tile and workgroup).  VS_PACED_UPDATE=0 (read when a step is issued or
+# recorded) restores the chip-filling launch behind the integrator's kernel.
+PACED_UPDATE = (128, 4, 1)
+
+
+def paced_update_enabled():
+    return os.environ.get('VS_PACED_UPDATE', '1') != '0'
+
+
+def current_pace():
+    """(max_workgroups, pieces_in_flight, cache_policy) while release_deferred() issues a held update in the paced form, else None."""
+    return _SIDE['pace']
 
 
 _OWN_STREAMS = []
@@ -367,7 +385,9 @@ def run_deferred(fn, *inputs, outs=None, lane=0, late=False):
     returned in place of fn's result.  `late`: when held, `fn` additionally waits ON ITS OWN LANE for the event recorded after the
     integrator's backward kernel (release_deferred(late_after=...)): a held fused first-layer update (E_s's 20480 x 1200 weight-gradient +
     Adam launch: 640 MB of HBM traffic) then runs beside E_t's input-gradient chain, which leaves HBM idle, instead of beside that
-    latency-bound kernel (WaveEq step, same box: 1.4505 -> 1.4045 ms)."""
+    latency-bound kernel (WaveEq step, same box: 1.4505 -> 1.4045 ms).  With the paced schedule (PACED_UPDATE, paced_update_enabled) that
+    wait is dropped and `fn` is issued while current_pace() names the paced form: the update's operands are complete before the
+    integrator's kernel starts, and a launch of a few workgroups runs beside it."""
     if not _SIDE['on']:
         out = fn()
         return out if outs is None else outs
@@ -419,7 +439,8 @@ def _behind_producer(ws, producer, main, behind):
 def release_deferred(after=None, late_after=None):
     """Launch everything collected since hold_deferred() on the gradient streams, in order, behind the work queued so far on the
     stream the hold was declared on (the producer of every input of the held closures) and behind the event `after`; work held with
-    `late` also behind the event `late_after` (recorded after the integrator's kernel)."""
+    `late` also behind the event `late_after` (recorded after the integrator's kernel) -- or, with the paced schedule, not behind it
+    but in the paced form (see run_deferred)."""
     held, _SIDE['held'] = _SIDE['held'], []
     was, _SIDE['hold'] = _SIDE['hold'], False
     if not held:
@@ -448,9 +469,15 @@ def release_deferred(after=None, late_after=None):
                 started.add(lane)
             _behind_producer(ws, producer, main, behind)
             if late and late_after is not None:
-                ws.wait_event(late_after)
-        with torch.cuda.stream(ws):
-            fn()
+                if paced_update_enabled():
+                    _SIDE['pace'] = PACED_UPDATE      # beside the integrator's kernel, in the form that leaves it the memory system
+                else:
+                    ws.wait_event(late_after)
+        try:
+            with torch.cuda.stream(ws):
+                fn()
+        finally:
+            _SIDE['pace'] = None
         _queued_on_lane(fn, 0 if lane is None else lane)
         _record_on(ws, inputs, outs)
 

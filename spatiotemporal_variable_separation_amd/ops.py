@@ -130,6 +130,38 @@ def gemm_adam(a, layout_a, b, layout_b, M, N, K, param, exp_avg, exp_avg_sq, sha
         nbytes=float((M * K + N * K) * a.element_size() + M * N * (24 + (2 if shadow is not None else 0))))
 
 
+_PACED = {'launches': 0}
+
+
+def gemm_adam_paced_launches():
+    """How many paced fused updates (gemm_adam_paced) this process has issued or recorded."""
+    return _PACED['launches']
+
+
+def gemm_adam_paced(a, layout_a, b, layout_b, M, N, K, param, exp_avg, exp_avg_sq, shadow, step_dev, skipped, lr, betas, eps,
+                    max_workgroups, pieces_in_flight, cache_policy, alpha=1.0):
+    """gemm_adam as a launch of at most `max_workgroups` workgroups that walk the tiles (vs_gemm_adam_paced): bit for bit the same
+    update, for running beside a latency-bound kernel.  param, moments and the 16-bit copy may be row-strided views with ONE leading
+    dimension (param.stride(0))."""
+    require_cuda(a, b, param, exp_avg, exp_avg_sq, step_dev)
+    lib = _lib.load_library()
+    assert a.dtype == b.dtype and a.dtype in (torch.bfloat16, torch.float16) and a.stride(-1) == 1 and b.stride(-1) == 1
+    assert param.dtype == torch.float32 and tuple(param.shape) == (M, N)
+    ldp = param.stride(0)
+    for t in (param, exp_avg, exp_avg_sq, shadow):
+        assert t is None or (t.shape == param.shape and t.stride(1) == 1 and t.stride(0) == ldp)
+    assert shadow is None or shadow.dtype in (torch.bfloat16, torch.float16)
+    e0 = _pb()
+    check(lib.vs_gemm_adam_paced(dtype_code(a), M, N, K, a.data_ptr(), a.stride(0), layout_a, b.data_ptr(), b.stride(0), layout_b, float(alpha),
+                                 param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), _ptr(shadow), ldp,
+                                 code_of(shadow.dtype) if shadow is not None else BF16, step_dev.data_ptr(), int(skipped), float(lr),
+                                 float(betas[0]), float(betas[1]), float(eps), int(max_workgroups), int(pieces_in_flight), int(cache_policy),
+                                 stream_ptr()), 'vs_gemm_adam_paced')
+    _PACED['launches'] += 1
+    _pe(e0, 'vs_gemm_adam<%s,%s%s>paced' % (_DT[dtype_code(a)], _LNAME[layout_a], _LNAME[layout_b]), flops=2.0 * M * N * K,
+        nbytes=float((M * K + N * K) * a.element_size() + M * N * (24 + (2 if shadow is not None else 0))))
+
+
 def gemm_batched(a, layout_a, b, layout_b, M, N, K, out_dtype=torch.float32, out=None):
     """a [batch, ., .], b [batch, ., .] contiguous 3-D tensors of one dtype: out[i] = A_i B_i^T for every i in ONE launch."""
     require_cuda(a, b)

@@ -75,8 +75,13 @@ class Adam(torch.optim.Optimizer):
         self._init_group(0, group)
         st = self.state[p]
         shadow = VF.shadow_buffer_for_update(p)
-        ops.gemm_adam(a, layout_a, b, layout_b, M, N, K, p, st['exp_avg'], st['exp_avg_sq'], shadow, group['step_dev'], st.get('skipped', 0),
-                      group['lr'], group['betas'], group['eps'])
+        pace = VF.current_pace()
+        if pace is not None:                 # held, released beside the integrator's backward kernel (functional.release_deferred)
+            ops.gemm_adam_paced(a, layout_a, b, layout_b, M, N, K, p, st['exp_avg'], st['exp_avg_sq'], shadow, group['step_dev'], st.get('skipped', 0),
+                                group['lr'], group['betas'], group['eps'], *pace)
+        else:
+            ops.gemm_adam(a, layout_a, b, layout_b, M, N, K, p, st['exp_avg'], st['exp_avg_sq'], shadow, group['step_dev'], st.get('skipped', 0),
+                          group['lr'], group['betas'], group['eps'])
         torch.autograd.graph.increment_version(p)
         if shadow is not None:
             VF.shadows_written([p])

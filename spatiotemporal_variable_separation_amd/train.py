@@ -830,9 +830,12 @@ def recover_exchange(device, log=True, grad_sync=None):
         VF.resblock_two_launch_only(True)
     if log:
         # (the fused weight-gradient updates -- vs_gemm_adam -- issued in the SAME backward pass before the exchange timed out have been applied:
-        # that one step is partial (decoder updated, the rest not); every later step was skipped as a whole)
+        # that one step is partial (decoder updated, the rest not); E_s's first layer, whose paced update -- vs_gemm_adam_paced -- runs BESIDE the
+        # integrator's backward kernel and reads the guard once per workgroup, may be updated in some tiles and not in others; every later
+        # step was skipped as a whole)
         sys.stderr.write('varsep: an in-launch exchange timed out (code %d); the optimizer skipped %s (batches consumed, no update; the first of them '
-                         'may have updated the weights whose Adam step runs inside their weight-gradient GEMM).  Continuing with %s\n'
+                         'may have updated the weights whose Adam step runs inside their weight-gradient GEMM, the one that runs beside the '
+                         'integrator\'s backward kernel possibly in some tiles only).  Continuing with %s\n'
                          % (err, ('%d step(s)' % skipped) if skipped else 'the affected step(s)', ' and '.join((['the agent-scope integrator exchange'] if err & 1 else []) +
                                               (['two-launch ConvResBlock layers'] if err & 2 else []))))
     return err
