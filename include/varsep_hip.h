@@ -548,6 +548,54 @@ int vs_inflate_place(const uint8_t* slots, int64_t slot_stride, int64_t n_slots,
 int vs_inflate_resolve(const uint16_t* marks, int64_t n_slots, const int64_t* slot_index, const int64_t* sizes, const int64_t* offsets, int64_t n,
                        uint8_t* out, int64_t out_bytes, void* stream);
 
+/* Block-parallel DEFLATE decoding on the device (csrc/vs_inflate_blocks.hip; the logic is csrc/vs_inflate_blocks_core.h): the reader of raw
+ * RFC 1951 streams WITHOUT sync markers -- what zlib and np.savez_compressed write.  Every block of such a stream is a place to start a
+ * decoder: vs_inflate_block_scan finds the bit positions where a dynamic-Huffman block header reads (the CANDIDATES), vs_inflate_block_probe
+ * decodes from every candidate to the next one with the window unknown (marks as above), the host chains the spans from bit 0 by where each
+ * one ends (ops.inflate_blocks; a false candidate is never the end of a span of the chain, so it is decoded and ignored),
+ * vs_inflate_block_windows turns the spans' last cells into the true 32 KiB before every span of the chain, and vs_inflate_block_decode decodes
+ * each span of the chain again, now with its window, straight into the output.  Positions and ends are in BITS.                        */
+#define VS_INFLATE_WINDOW_BYTES 32768       /* cells a probe keeps and leaves per candidate, bytes of a window */
+#define VS_INFLATE_BLOCKS_MAX_IN 1048576    /* bytes of input one span may read */
+#define VS_INFLATE_CAP 12                   /* status: a span is not over after VS_INFLATE_BLOCKS_MAX_IN bytes of input */
+#define VS_INFLATE_DECODE_WORDS 3           /* per span of vs_inflate_block_decode: status, end, bytes produced */
+/* Appends to cand int64 [cap], in no particular order, bit position 0 and every bit position of comp [comp_bytes] from which a non-final
+ * dynamic block header reads that zlib could have written: BFINAL = 0, BTYPE = 2, HLIT <= 29, HDIST <= 29, a complete code-length code,
+ * lengths that fill HLIT + HDIST entries exactly (repeat code 16 never first), an end-of-block code, a complete literal/length code and a
+ * distance code that is complete or has at most one code of one bit.  *count (device, zeroed by the caller) is advanced by the number found
+ * even where it exceeds cap (entries beyond cap are not written): a call with cand null and cap 0 only counts.  VS_ERR_ARG (and nothing
+ * launched) for a null comp or count, a null cand with cap != 0, a negative comp_bytes or cap, or more bytes than a grid covers.          */
+int vs_inflate_block_scan(const uint8_t* comp, int64_t comp_bytes, int64_t* cand, int64_t cap, int64_t* count, void* stream);
+/* One wave per candidate c in first .. first + n - 1 of the SORTED list cand int64 [n_cand] (a batch: the workspace is n rows whatever the
+ * member's size): blocks of comp [comp_bytes] are decoded from bit cand[c] until one ends at a bit position that is in the list, a block
+ * with BFINAL = 1 has ended (final = 1) or an error (status != 0: a VS_INFLATE_* code; VS_INFLATE_CAP for a span not over after
+ * VS_INFLATE_BLOCKS_MAX_IN bytes of input).  The output is not capped.  words int64 [n, VS_INFLATE_REPORT_WORDS] row c - first receives
+ * status, end (in bits, behind the last block consumed), final, bytes produced, external bytes and the largest reach; cells uint16
+ * [n, VS_INFLATE_WINDOW_BYTES] row c - first receives the LAST min(produced, VS_INFLATE_WINDOW_BYTES) cells in order, from its start: a
+ * byte's value, or 0x8000 | o for a byte whose source is the byte o + 1 before the span's first output byte.  Nothing else in global memory
+ * is written, on any input.  VS_ERR_ARG (and nothing launched) for a null pointer, a negative size, first + n above n_cand, n above
+ * VS_INFLATE_MAX_BATCH or cells off a 2-byte boundary; n == 0 launches nothing.                                                         */
+int vs_inflate_block_probe(const uint8_t* comp, int64_t comp_bytes, const int64_t* cand, int64_t n_cand, int64_t first, int64_t n, uint16_t* cells,
+                           int64_t* words, void* stream);
+/* ONE workgroup walks spans 0 .. n - 1 IN CHAIN ORDER: windows uint8 [n + 1, VS_INFLATE_WINDOW_BYTES], row 0 given (the window before span
+ * 0: byte j is the byte VS_INFLATE_WINDOW_BYTES - j before the span's first output byte; zeros where the stream has not begun), row k + 1
+ * = the window behind span k, from row k and the cells of row slot_index[k] of cells [n_slots, VS_INFLATE_WINDOW_BYTES] as
+ * vs_inflate_block_probe left them for a span of produced[k] bytes: a value stays, a mark o reads byte VS_INFLATE_WINDOW_BYTES - 1 - o of
+ * row k, a span shorter than the window keeps the rest of row k in front of its own bytes.  A span whose slot is outside 0 .. n_slots - 1
+ * or whose size is negative passes its window on unchanged.  VS_ERR_ARG for a null pointer, a negative size, n or n_slots above
+ * VS_INFLATE_MAX_BATCH, cells off a 2-byte or windows off a 16-byte boundary; n == 0 launches nothing.                                  */
+int vs_inflate_block_windows(const uint16_t* cells, int64_t n_slots, const int64_t* slot_index, const int64_t* produced, int64_t n, uint8_t* windows,
+                             void* stream);
+/* One wave per span k < n of the chain: a plain inflate of comp [comp_bytes] from bit start_bits[k] until a block ends at or behind bit
+ * end_bits[k] (or a final block ends), with the min(offsets[k], VS_INFLATE_WINDOW_BYTES) bytes before it taken from row k of windows uint8
+ * [n, VS_INFLATE_WINDOW_BYTES], written to out + offsets[k] .. + sizes[k] and nowhere else (more output is VS_INFLATE_OUT_LONG, a distance
+ * before the window VS_INFLATE_DISTANCE).  words int64 [n, VS_INFLATE_DECODE_WORDS] receives status, end (bits) and bytes produced, which
+ * the caller compares with the probe's.  A span with a negative offset or size or with offsets[k] + sizes[k] above out_bytes writes nothing
+ * and reports VS_INFLATE_OUT_LONG.  VS_ERR_ARG for a null pointer, a negative size, n above VS_INFLATE_MAX_BATCH or windows off a 16-byte
+ * boundary; n == 0 launches nothing.                                                                                                   */
+int vs_inflate_block_decode(const uint8_t* comp, int64_t comp_bytes, const int64_t* start_bits, const int64_t* end_bits, const int64_t* offsets,
+                            const int64_t* sizes, int64_t n, const uint8_t* windows, uint8_t* out, int64_t out_bytes, int64_t* words, void* stream);
+
 /* PNG encoding on the device (csrc/vs_png_encode.hip; the logic is csrc/vs_png_encode_core.h on top of the two DEFLATE cores): a batch of
  * images in HBM becomes one complete PNG file per image in three launches -- the forward row filters, one DEFLATE stream per image, the
  * framing -- so that only compressed bytes are copied to the host.  S = H * (1 + W * C) is the filtered size of one image.             */

@@ -16,7 +16,7 @@ _CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(_HERE, 'libvarsep_hip.so')
 SOURCES = ['vs_gemm.hip', 'vs_eltwise.hip', 'vs_conv.hip', 'vs_rollout.hip', 'vs_norm.hip', 'vs_optim.hip', 'vs_data.hip', 'vs_conv_tap.hip', 'vs_metrics.hip', 'vs_conv_img.hip', 'vs_conv_k4s2.hip',
            'vs_conv_thin.hip', 'vs_conv_band2.hip', 'vs_conv_wgrad2.hip', 'vs_eval.hip', 'vs_wave_sim.hip', 'vs_resample.hip', 'vs_png.hip', 'vs_deflate.hip',
-           'vs_mt19937.hip', 'vs_mmnist_walk.hip', 'vs_png_encode.hip', 'vs_inflate_chunks.hip']
+           'vs_mt19937.hip', 'vs_mmnist_walk.hip', 'vs_png_encode.hip', 'vs_inflate_chunks.hip', 'vs_inflate_blocks.hip']
 
 F32, BF16, F16 = 0, 1, 2
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -162,6 +162,10 @@ SIGNATURES = {
     'vs_inflate_segments': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'vs_inflate_place': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     'vs_inflate_resolve': (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'vs_inflate_block_scan': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    'vs_inflate_block_probe': (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    'vs_inflate_block_windows': (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    'vs_inflate_block_decode': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     'vs_u8_tn_to_f32_nt': (_i32, [_vp, _i64, _i64, _i64, _vp, _vp]),
     'vs_png_filter': (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     'vs_deflate_streams': (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),

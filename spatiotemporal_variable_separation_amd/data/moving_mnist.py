@@ -280,19 +280,24 @@ class MovingMNIST:
         return cond[0], target[0]
 
     @classmethod
-    def make_dataset(cls, data_dir, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device='cuda', seed=None, load=None, report=None):
+    def make_dataset(cls, data_dir, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device='cuda', seed=None, load=None, report=None,
+                     foreign=None):
         """load: who decompresses the test-set file (utils/loadz.npz_loader: the keyword, then VARSEP_NPZ_LOAD, then 'host').  'host' is
         np.load and the host conversion, as before; 'device' inflates `sequences` in HBM (utils/loadz.load), where it stays uint8 until the
         [T, N, ...] -> fp32 [N, T, ...] step, also done there.  `.data` is the same bit for bit.  report: optional dict for
-        utils/loadz.load's record of the route `sequences` took."""
+        utils/loadz.load's record of the route `sequences` took.  foreign: with 'device', who decompresses a file that is not cut at sync
+        markers, as np.savez_compressed writes it (utils/loadz.npz_foreign: the keyword, then VARSEP_NPZ_FOREIGN, then 'host'), read here
+        with the first rule and handed on when it is not the default."""
         if train:
             data = synthetic_digits(seed=seed or 1234) if data_dir == 'synthetic_digits' else read_mnist_images(data_dir, train=True)
         else:
             from ..utils import loadz
             prefix = '' if deterministic else 's'
             path = os.path.join(data_dir, f'{prefix}mmnist_test_{num_digits}digits_{nx}.npz')
-            if loadz.npz_loader(load) == 'device':
-                sequences = loadz.load(path, device, keys=('sequences',), load='device', report=report)['sequences']
+            how, who = loadz.npz_loader(load), loadz.npz_foreign(foreign)
+            if how == 'device':
+                extra = {} if foreign is None and who == 'host' else {'foreign': who}
+                sequences = loadz.load(path, device, keys=('sequences',), load='device', report=report, **extra)['sequences']
                 if sequences.dtype == torch.uint8:
                     from .. import ops
                     data = ops.u8_tn_to_f32_nt(sequences)

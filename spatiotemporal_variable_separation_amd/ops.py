@@ -2824,6 +2824,146 @@ def inflate_raw(comp, out_bytes, crc=None, batch=None, trace=None):
     return out
 
 
+# ---- block-parallel DEFLATE decoding on the device (csrc/vs_inflate_blocks.hip) ------------------------------------------------------
+INFLATE_WINDOW_BYTES = 32768      # VS_INFLATE_WINDOW_BYTES: cells a probe leaves per candidate, bytes of a window
+INFLATE_BLOCKS_MAX_IN = 1 << 20   # VS_INFLATE_BLOCKS_MAX_IN: bytes of input one span may read
+INFLATE_CAP = 12                  # VS_INFLATE_CAP
+INFLATE_DECODE_WORDS = 3          # VS_INFLATE_DECODE_WORDS: status, end, produced
+
+
+def inflate_block_scan(comp):
+    """The candidate span starts of a raw DEFLATE stream without sync markers: int64 [n] BIT positions on the device, sorted -- bit 0 and
+    every bit from which a non-final dynamic block header reads (vs_inflate_block_scan, once to count and once to list; the sort of the
+    short list is torch's)."""
+    require_cuda(comp)
+    if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous():
+        raise _lib.VarsepHipError('inflate_block_scan: a contiguous uint8 [bytes] tensor expected')
+    lib, device, n = _lib.load_library(), comp.device, comp.numel()
+    with torch.cuda.device(device):
+        count = torch.zeros((2,), dtype=torch.int64, device=device)
+        keep = comp if n else torch.zeros((1,), dtype=torch.uint8, device=device)
+        e0 = _pb()
+        check(lib.vs_inflate_block_scan(keep.data_ptr(), n, None, 0, count.data_ptr(), stream_ptr()), 'vs_inflate_block_scan')
+        _pe(e0, 'vs_inflate_block_scan', nbytes=float(n))
+        found = int(count[0].item())
+        cand = torch.empty((found,), dtype=torch.int64, device=device)
+        e0 = _pb()
+        check(lib.vs_inflate_block_scan(keep.data_ptr(), n, cand.data_ptr(), found, count[1:].data_ptr(), stream_ptr()), 'vs_inflate_block_scan')
+        _pe(e0, 'vs_inflate_block_scan', nbytes=float(n))
+        return torch.sort(cand).values
+
+
+def inflate_blocks(comp, out_bytes, crc=None, batch=None, trace=None):
+    """The `out_bytes` bytes of the raw DEFLATE stream `comp` (uint8 [bytes] on the device) that has NO sync markers -- one unbroken stream
+    of zlib, what np.savez_compressed stores -- decoded in parallel at its block headers: uint8 [out_bytes] on the device, or an
+    InflateNotChunked when the spans do not chain (the caller then decodes the stream another way).
+    Every candidate (inflate_block_scan) is probed by one wave that does not know what came before it (vs_inflate_block_probe), `batch`
+    candidates per launch (default INFLATE_BATCH: 96 KiB of workspace each) with one download of the report words per batch.  The chain is
+    walked here: from candidate 0 the next span is the candidate at the bit where the last one ended; every step needs status 0, an end
+    that is a candidate (or a final block that ends in the stream's last byte) and no reference further back than the bytes produced so
+    far, and the chain must total out_bytes.  A block end that is a candidate is a true block start, so false candidates are decoded and
+    ignored.  Per batch the chain's spans get their true windows in chain order (vs_inflate_block_windows, one workgroup) and are decoded a
+    second time straight into the output (vs_inflate_block_decode), whose status, end and size must be the probe's.  A span that reads more
+    than INFLATE_BLOCKS_MAX_IN bytes of input (long runs of stored or fixed blocks) does not chain.  crc: the CRC-32 the result must have
+    (ops.crc32); a mismatch after a valid chain raises zipfile.BadZipFile.  trace: optional list that receives per decoded batch a dict
+    (first: first candidate index, cand: the sorted candidates as a host array, words int64 [n, 6], chain: rows of the batch on the chain,
+    windows uint8 [chain + 1, 32768] and words2 int64 [chain, 3], both None where the batch has no span of the chain or the chain broke in
+    it), and after a walk to the end a dict(candidates, chain, workspace_bytes)."""
+    import numpy as np
+    require_cuda(comp)
+    out_bytes = int(out_bytes)
+    batch = INFLATE_BATCH if batch is None else int(batch)
+    if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous() or out_bytes < 0 or batch < 1 or batch > INFLATE_MAX_BATCH:
+        raise _lib.VarsepHipError('inflate_blocks: comp uint8 [bytes] contiguous, out_bytes >= 0 and batch in 1 .. %d expected' % INFLATE_MAX_BATCH)
+    lib, device, n = _lib.load_library(), comp.device, comp.numel()
+    W, RW, DW = INFLATE_WINDOW_BYTES, INFLATE_REPORT_WORDS, INFLATE_DECODE_WORDS
+    with torch.cuda.device(device):
+        cand = inflate_block_scan(comp)
+        starts = cand.cpu().numpy()
+        n_cand = starts.size
+        rows = min(batch, n_cand)
+        keep = comp if n else torch.zeros((1,), dtype=torch.uint8, device=device)
+        out = torch.empty((max(out_bytes, 1),), dtype=torch.uint8, device=device)[:out_bytes]
+        cells = torch.empty((rows, W), dtype=torch.int16, device=device)
+        words = torch.empty((rows, RW), dtype=torch.int64, device=device)
+        windows = torch.zeros((rows + 1, W), dtype=torch.uint8, device=device)   # row 0: the window before the batch's first span of the chain
+        words2 = torch.empty((rows, DW), dtype=torch.int64, device=device)
+        total, nxt, final, chain_len = 0, 0, False, 0                       # bytes produced, the candidate the chain is at, closed
+        for lo in range(0, n_cand, batch):
+            if final:
+                break
+            if nxt >= lo + batch:                                           # a batch of off-chain candidates only: nothing of it is needed
+                continue
+            m = min(batch, n_cand - lo)
+            e0 = _pb()
+            check(lib.vs_inflate_block_probe(keep.data_ptr(), n, cand.data_ptr(), n_cand, lo, m, cells.data_ptr(), words.data_ptr(), stream_ptr()),
+                  'vs_inflate_block_probe')
+            _pe(e0, 'vs_inflate_block_probe', nbytes=float(n) / max(1, -(-n_cand // batch)) + 2.0 * m * W)
+            w = words[:m].cpu().numpy()
+            rec = dict(first=lo, cand=starts, words=w.copy(), chain=[], windows=None, words2=None)
+            if trace is not None:
+                trace.append(rec)
+            follow = np.searchsorted(starts, w[:, 1])                       # per candidate: the candidate that starts where it ends, if any
+            is_start = (starts[np.minimum(follow, n_cand - 1)] == w[:, 1]) & (follow < n_cand)
+            rows_w, follow, is_start = w.tolist(), follow.tolist(), is_start.tolist()
+            plan = []                                                       # (row, start bit, end bit, offset, size) of the chain's spans in this batch
+            while not final and lo <= nxt < lo + m:
+                status, end, fin, produced, externals, reach = rows_w[nxt - lo]
+                if status != 0:
+                    why = 'more than %d bytes of input before a block header that can be found' % INFLATE_BLOCKS_MAX_IN if status == INFLATE_CAP \
+                        else INFLATE_STATUS.get(status, 'status %d' % status)
+                    return InflateNotChunked('span at bit %d: %s' % (starts[nxt], why))
+                if reach > total:
+                    return InflateNotChunked('span at bit %d reaches %d bytes back, %d bytes into the stream' % (starts[nxt], reach, total))
+                if total + produced > out_bytes:
+                    return InflateNotChunked('more than the %d bytes of the record' % out_bytes)
+                plan.append((nxt - lo, int(starts[nxt]), end, total, produced))
+                total += produced
+                if fin:
+                    final = True
+                    if (end + 7) // 8 != n:
+                        return InflateNotChunked('the final block ends at bit %d of %d bytes' % (end, n))
+                    break
+                k = follow[nxt - lo]
+                if not is_start[nxt - lo] or k <= nxt:
+                    return InflateNotChunked('span at bit %d ends at bit %d, which is no candidate' % (starts[nxt], end))
+                nxt = k
+            if not plan:
+                continue
+            c = len(plan)
+            chain_len += c
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(plan, dtype=np.int64).T)).to(device)
+            e0 = _pb()
+            check(lib.vs_inflate_block_windows(cells.data_ptr(), m, t[0].data_ptr(), t[4].data_ptr(), c, windows.data_ptr(), stream_ptr()),
+                  'vs_inflate_block_windows')
+            _pe(e0, 'vs_inflate_block_windows', nbytes=3.0 * c * W)
+            e0 = _pb()
+            check(lib.vs_inflate_block_decode(keep.data_ptr(), n, t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(), c, windows.data_ptr(),
+                                              out.data_ptr() if out_bytes else keep.data_ptr(), out_bytes, words2.data_ptr(), stream_ptr()),
+                  'vs_inflate_block_decode')
+            _pe(e0, 'vs_inflate_block_decode', nbytes=float(c) * W + float(sum(r[4] for r in plan)))
+            w2 = words2[:c].cpu().numpy()
+            if trace is not None:
+                rec.update(chain=[r[0] for r in plan], windows=windows[:c + 1].cpu().numpy(), words2=w2.copy())
+            want = np.asarray([(0, r[2], r[4]) for r in plan], dtype=np.int64)
+            if not np.array_equal(w2, want):
+                bad = int(np.nonzero((w2 != want).any(axis=1))[0][0])
+                raise _lib.VarsepHipError('inflate_blocks: the second decode of the span at bit %d reports status, end, size %s where the probe '
+                                          'reported %s' % (plan[bad][1], w2[bad].tolist(), want[bad].tolist()))
+            windows[0].copy_(windows[c])                                    # the window behind this batch's last span, before the next batch's first
+        if trace is not None:
+            trace.append(dict(candidates=int(n_cand), chain=chain_len,
+                              workspace_bytes=sum(x.numel() * x.element_size() for x in (cand, cells, words, windows, words2))))
+        if not final:
+            return InflateNotChunked('the chain leaves the candidates before a final block')
+        if total != out_bytes:
+            return InflateNotChunked('%d bytes where the record says %d' % (total, out_bytes))
+    if crc is not None and crc32(out) != (int(crc) & 0xFFFFFFFF):
+        import zipfile
+        raise zipfile.BadZipFile('inflate_blocks: bad CRC-32 of %d decoded bytes' % out_bytes)
+    return out
+
+
 def u8_tn_to_f32_nt(x):
     """uint8 [T, N, ...] on the device -> fp32 [N, T, ...] (vs_u8_tn_to_f32_nt, csrc/vs_data.hip): what `[x[:, i].astype(np.single) for i ...]` stacks on the host."""
     require_cuda(x)

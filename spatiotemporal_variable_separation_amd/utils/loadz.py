@@ -9,6 +9,12 @@ stream is cut at sync markers at most 32 KiB of data apart -- all that this pack
 members that are one segment.  A member the device route does not cover takes the host route, alone: Fortran-order, object, structured and
 big-endian arrays, dtypes torch does not have, and streams that do not chain (a large np.savez_compressed member is one stream without
 markers).  Stored members (method 0) are uploaded as they are.  The zip directory and the .npy headers are read by utils/npz.py on the host.
+
+Foreign members: VARSEP_NPZ_FOREIGN=host|device (`foreign=` in code; same precedence, default `host`) matters only while the loader is
+`device`.  `host` is the paragraph above.  `device` sends a member that does not chain at sync markers -- every np.savez_compressed member --
+to ops.inflate_blocks (csrc/vs_inflate_blocks.hip: block headers found by validation, one wave per span between two of them, each span
+decoded twice), and only a member that does not chain there either (more than 1 MiB of input between two dynamic block headers: long runs
+of stored or fixed blocks) takes the host route.
 """
 import os
 import zlib
@@ -20,6 +26,7 @@ from .. import ops
 from . import npz
 
 LOAD_ENV = 'VARSEP_NPZ_LOAD'
+FOREIGN_ENV = 'VARSEP_NPZ_FOREIGN'
 _HEAD_BYTES = 1 << 16                # compressed bytes inflated on the host to read a member's .npy header (a header is at most 64 KiB + 10)
 
 
@@ -32,6 +39,18 @@ def npz_loader(load=None):
     if load not in ('host', 'device'):
         raise ValueError("%s=%r: 'host' or 'device' expected" % (source, load))
     return load
+
+
+def npz_foreign(foreign=None):
+    """'host' or 'device': who decompresses a member that is not cut at sync markers while the loader is 'device'.  The keyword wins; None
+    reads the environment variable VARSEP_NPZ_FOREIGN; when that is unset or empty the host does (the behaviour before the block-parallel
+    reader existed).  Any other value raises, naming the two."""
+    source = 'foreign'
+    if foreign is None:
+        foreign, source = os.environ.get('VARSEP_NPZ_FOREIGN', '') or 'host', FOREIGN_ENV
+    if foreign not in ('host', 'device'):
+        raise ValueError("%s=%r: 'host' or 'device' expected" % (source, foreign))
+    return foreign
 
 
 def _key(entry):
@@ -91,12 +110,14 @@ def _as_array(raw, header):
     return data.view(dtype).reshape(header.shape)
 
 
-def load(path, device, keys=None, load=None, report=None):
+def load(path, device, keys=None, load=None, report=None, foreign=None):
     """The arrays of the .npz file `path` as {name: tensor on `device`}, names as np.load gives them; keys: the names wanted (default
     all, in the file's order).  load: 'host' (np.load, then an upload), 'device' (see the module docstring) or None (`npz_loader`).
     report: optional dict that receives name -> (route, why) with route 'host', 'device' or 'stored'.  An array torch cannot hold (object,
-    structured) is returned as the host array.  A damaged member raises what np.load raises for it (zipfile.BadZipFile, zlib.error, ...)."""
+    structured) is returned as the host array.  A damaged member raises what np.load raises for it (zipfile.BadZipFile, zlib.error, ...).
+    foreign: 'host', 'device' or None (`npz_foreign`): with load='device', who decompresses a member that does not chain at sync markers."""
     load = npz_loader(load)
+    foreign = npz_foreign(foreign)
     device = torch.device(device)
     report = {} if report is None else report
     out = {}
@@ -132,6 +153,9 @@ def load(path, device, keys=None, load=None, report=None):
                 else:
                     raw = ops.inflate_raw(comp, e.usize, crc=e.crc32)
                     route = ('device', 'chained at its sync markers')
+                    if isinstance(raw, ops.InflateNotChunked) and foreign == 'device':
+                        raw = ops.inflate_blocks(comp, e.usize, crc=e.crc32)
+                        route = ('device', 'chained at its block headers')
                     if isinstance(raw, ops.InflateNotChunked):
                         why = 'not chunked: ' + raw.reason
                 if why is None:

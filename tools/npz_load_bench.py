@@ -5,7 +5,13 @@ ops.inflate_raw on the `sequences` member by kernel (event times, one warm pass)
 with VARSEP_NPZ_LOAD=device and =host, alternating, every run in a fresh process, with the peak of HBM torch allocated.  The comparison
 is the host route on the same box in the same run.  Writes the note given by --out.
 
-    python tools/npz_load_bench.py [--out FILE] [--videos N] [--pairs K]
+--blocks: the rule VARSEP_NPZ_FOREIGN on the np.savez_compressed file alone (utils/loadz.npz_foreign, csrc/vs_inflate_blocks.hip): the
+launches of ops.inflate_blocks by kernel, the candidates the scan found, the chain's length, the candidates off the chain (each one a false
+positive: a chain that verified passes through every block start that is in the list), the scan's misses on a sample of the stream that a
+block walker reads on the host, the peak of HBM, and `make_dataset` on the three routes `host`, `device` + foreign `host` (what the file
+took before the rule existed) and `device` + foreign `device`, alternating, every run in a fresh process.
+
+    python tools/npz_load_bench.py [--out FILE] [--videos N] [--pairs K] [--blocks] [--sample-mb M]
 """
 import argparse
 import json
@@ -27,6 +33,8 @@ from spatiotemporal_variable_separation_amd.utils import npz, savez  # noqa: E40
 N_IMAGES, T, F, ND, SPEED, SEED = 10000, 100, 64, 2, 4, 42
 NAME = 'mmnist_test_%ddigits_%d.npz' % (ND, F)
 KERNELS = ('vs_inflate_sync_scan', 'vs_inflate_segments', 'vs_inflate_place', 'vs_inflate_resolve', 'vs_crc32')
+BLOCK_KERNELS = ('vs_inflate_block_scan', 'vs_inflate_block_probe', 'vs_inflate_block_windows', 'vs_inflate_block_decode', 'vs_crc32')
+ROUTES = ('host', 'device+host', 'device+device')          # VARSEP_NPZ_LOAD [+ VARSEP_NPZ_FOREIGN]
 
 lines = []
 
@@ -43,8 +51,9 @@ def child(directory, route):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats(dev)
     report = {}
+    load, _, foreign = route.partition('+')
     t0 = time.perf_counter()
-    ds = MovingMNIST.make_dataset(directory, F, 5, 10, SPEED, True, ND, False, device=dev, load=route, report=report)
+    ds = MovingMNIST.make_dataset(directory, F, 5, 10, SPEED, True, ND, False, device=dev, load=load, report=report, foreign=foreign or None)
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     print(json.dumps(dict(seconds=seconds, peak=torch.cuda.max_memory_allocated(dev), shape=list(ds.data.shape),
@@ -102,15 +111,136 @@ def kernel_table(label, path, dev):
     torch.cuda.empty_cache()
 
 
+def blocks_table(label, path, dev, sample_mb):
+    """ops.inflate_blocks on the `sequences` member of `path`: per-kernel event times of one warm pass, candidates, chain, misses, HBM."""
+    import inflate_blocks_inputs as IB
+    entry = {e.name: e for e in npz.read_directory(path)}['sequences.npy']
+    host_bytes = np.fromfile(path, dtype=np.uint8, count=entry.csize, offset=entry.data_offset)
+    t0 = time.perf_counter()
+    comp = torch.from_numpy(host_bytes).to(dev)
+    torch.cuda.synchronize()
+    upload = time.perf_counter() - t0
+    say('## %s: `sequences` is %d compressed bytes (%.1f MB) for %d (%.3f GB)' % (label, entry.csize, entry.csize / 1e6, entry.usize, entry.usize / 1e9))
+    say()
+    first = ops.inflate_raw(comp, entry.usize, crc=entry.crc32)
+    say('* ops.inflate_raw (the sync-marker reader, tried first): %r' % (first,))
+    out = ops.inflate_blocks(comp, entry.usize, crc=entry.crc32)            # warm
+    if not isinstance(out, torch.Tensor):
+        say('* ops.inflate_blocks: %r: the member takes the host route.' % (out,))
+        say()
+        return
+    del out
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    ops.profile_reset(True)
+    trace = []
+    t0 = time.perf_counter()
+    out = ops.inflate_blocks(comp, entry.usize, crc=entry.crc32, trace=trace)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    prof = ops.profile_collect()
+    peak = torch.cuda.max_memory_allocated(dev) - base
+    say()
+    say('| launch | launches | event time, summed | output bytes per second of it |')
+    say('|---|---|---|---|')
+    for k in BLOCK_KERNELS:
+        p = prof.get(k, {'ms': 0.0, 'n': 0})
+        say('| %s | %d | %.3f ms | %s |' % (k, p['n'], p['ms'], '%.1f GB/s' % (entry.usize / p['ms'] / 1e6) if p['ms'] else '-'))
+    total = sum(prof.get(k, {'ms': 0.0})['ms'] for k in BLOCK_KERNELS)
+    say('| all launches | %d | %.3f ms | %.1f GB/s |' % (sum(prof.get(k, {'n': 0})['n'] for k in BLOCK_KERNELS), total, entry.usize / total / 1e6))
+    say()
+    summary = trace[-1]
+    words = np.concatenate([t['words'] for t in trace[:-1]])
+    chain_rows = np.concatenate([np.asarray(t['chain'], dtype=np.int64) + t['first'] for t in trace[:-1]])
+    w = words[chain_rows] if len(words) == summary['candidates'] else None
+    say('* candidates found by the scan: %d; spans on the chain: %d; candidates off the chain (false positives, decoded and ignored): %d.'
+        % (summary['candidates'], summary['chain'], summary['candidates'] - summary['chain']))
+    if w is not None:
+        bad = words[np.setdiff1d(np.arange(len(words)), chain_rows)]
+        say('* spans of the chain: compressed bytes min / median / max %d / %d / %d, bytes produced min / median / max %d / %d / %d; spans with '
+            'external bytes: %d, external bytes in all: %d (%.1f %% of the output).'
+            % tuple([int(x) for x in (np.min(np.diff(np.append(trace[0]['cand'][chain_rows], w[-1, 1]))) // 8,
+                                      np.median(np.diff(np.append(trace[0]['cand'][chain_rows], w[-1, 1]))) // 8,
+                                      np.max(np.diff(np.append(trace[0]['cand'][chain_rows], w[-1, 1]))) // 8, w[:, 3].min(), np.median(w[:, 3]), w[:, 3].max(),
+                                      (w[:, 4] > 0).sum(), w[:, 4].sum())] + [100.0 * w[:, 4].sum() / max(1, entry.usize)]))
+        if len(bad):
+            say('* the off-chain probes ended with status ' + ', '.join('%d (%d)' % (s, int((bad[:, 0] == s).sum())) for s in np.unique(bad[:, 0]))
+                + '; the longest read %d bytes of input.' % int(((bad[:, 1] - trace[0]['cand'][np.setdiff1d(np.arange(len(words)), chain_rows)]) // 8).max()))
+    t0 = time.perf_counter()
+    blocks = IB.walk_blocks(host_bytes.tobytes(), stop_bit=8 * int(sample_mb * 1e6))
+    walked = time.perf_counter() - t0
+    limit = blocks[-1]['end']
+    truth = {b['start'] for b in blocks if b['type'] == 2 and not b['final'] and b['start'] > 0}
+    cand = {int(c) for c in trace[0]['cand'] if 0 < c < limit}
+    kinds = [sum(1 for b in blocks if b['type'] == k) for k in range(3)]
+    say('* the scan against a block walker on the host (tests/inflate_blocks_inputs.walk_blocks, %.1f s) over the first %.2f MB of the stream: %d '
+        'blocks (%d stored, %d fixed, %d dynamic), %d non-final dynamic block starts, of which the scan MISSED %d; candidates in that range that '
+        'are no block start (FALSE POSITIVES): %d.' % (walked, limit / 8e6, len(blocks), kinds[0], kinds[1], kinds[2], len(truth), len(truth - cand),
+                                                       len(cand - truth)))
+    say('* ops.inflate_blocks, wall clock with its downloads of the report words and the chain walk on the host: %.3f s; reading the member from '
+        'the file and uploading it: %.3f s; HBM allocated above the compressed bytes, at the peak: %.2f GB (the output is %.2f GB, the workspace '
+        '%.2f GB for batches of %d candidates).' % (wall, upload, peak / 1e9, entry.usize / 1e9, summary['workspace_bytes'] / 1e9, ops.INFLATE_BATCH))
+    say()
+    del out, comp
+    torch.cuda.empty_cache()
+
+
+def main_blocks(args):
+    import mmnist_testset_inputs as I
+    from spatiotemporal_variable_separation_amd.preprocessing.mnist import make_test_set
+    dev = torch.device('cuda', 0)
+    n_images = args.videos * ND
+    images = synthetic_digits(n_images, seed=SEED)
+    labels = (np.arange(n_images) % 10).astype(np.uint8)
+    say('# Reading a NumPy-written Moving-MNIST test-set file on the device (one MI355X, `tools/npz_load_bench.py --blocks`)')
+    say()
+    say('%d videos x %d frames of %d x %d, written by np.savez_compressed: every member is one zlib stream without sync markers.  Kernel times '
+        'are HIP event times of one warm pass; everything else is wall clock on the same box in the same run, one fresh process per '
+        '`make_dataset`.' % (args.videos, T, F, F))
+    say()
+    with tempfile.TemporaryDirectory() as tmp:
+        I.write_t10k(tmp, images, labels)
+        arrays = make_test_set.generate_device(tmp, T, SEED, ND, F, SPEED, dev)
+        d = os.path.join(tmp, 'numpy')
+        os.makedirs(d)
+        t0 = time.perf_counter()
+        savez.savez_compressed(os.path.join(d, NAME), arrays, compress='host', match=None)
+        say('The file: %.1f MB, written in %.2f s.' % (os.path.getsize(os.path.join(d, NAME)) / 1e6, time.perf_counter() - t0))
+        say()
+        del arrays
+        torch.cuda.empty_cache()
+        blocks_table('np.savez_compressed', os.path.join(d, NAME), dev, args.sample_mb)
+        say('## `MovingMNIST.make_dataset(train=False)`, whole, alternating routes, a fresh process each')
+        say()
+        say('| VARSEP_NPZ_LOAD | VARSEP_NPZ_FOREIGN | seconds | peak HBM | `sequences` took | `.data` checksum |')
+        say('|---|---|---|---|---|---|')
+        for _ in range(args.pairs):
+            for route in ROUTES:
+                r = run_child(d, route)
+                took = r['report'].get('sequences', ['host', 'load=host'])
+                load, _, foreign = route.partition('+')
+                say('| %s | %s | **%.2f s** | %.2f GB | %s (%s) | %.0f |' % (load, foreign or '-', r['seconds'], r['peak'] / 1e9, took[0], took[1], r['checksum']))
+        say()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'npz_load_timing.md'))
+    ap.add_argument('--out', default=None, help='the note to write (default: profiles/npz_load_timing.md, with --blocks profiles/npz_blocks_timing.md)')
+    ap.add_argument('--blocks', action='store_true', help='the rule VARSEP_NPZ_FOREIGN on the np.savez_compressed file (see above)')
+    ap.add_argument('--sample-mb', type=float, default=4.0, help='--blocks: compressed MB a block walker reads on the host to count the misses')
     ap.add_argument('--videos', type=int, default=N_IMAGES // ND, help='videos of the set (the reference: 5 000)')
     ap.add_argument('--pairs', type=int, default=2, help='(device, host) pairs of fresh processes per file')
     ap.add_argument('--child', nargs=2, metavar=('DIR', 'ROUTE'), help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(*args.child)
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'npz_blocks_timing.md' if args.blocks else 'npz_load_timing.md')
+    if args.blocks:
+        return main_blocks(args)
     import mmnist_testset_inputs as I
     from spatiotemporal_variable_separation_amd.preprocessing.mnist import make_test_set
     dev = torch.device('cuda', 0)
