@@ -566,6 +566,16 @@ int vs_inflate_resolve(const uint16_t* marks, int64_t n_slots, const int64_t* sl
  * even where it exceeds cap (entries beyond cap are not written): a call with cand null and cap 0 only counts.  VS_ERR_ARG (and nothing
  * launched) for a null comp or count, a null cand with cap != 0, a negative comp_bytes or cap, or more bytes than a grid covers.          */
 int vs_inflate_block_scan(const uint8_t* comp, int64_t comp_bytes, int64_t* cand, int64_t cap, int64_t* count, void* stream);
+/* The finder of STORED blocks, opt-in (ops.inflate_block_scan(stored=True); the candidates of both scans together are the list the probe
+ * gets).  Byte offset B with B + 4 <= comp_bytes is a stored boundary when LEN (little-endian 16 bits at B) and NLEN (at B + 2) satisfy
+ * (LEN ^ 0xffff) == NLEN and B + 4 + LEN < comp_bytes (a non-final block is followed by another header; LEN = 0, the sync marker
+ * 00 00 ff ff, counts).  For a stored boundary B and k = 0 .. 7 the bit position q = 8 * B - 3 - k is appended when q >= 0 and every bit
+ * from q to 8 * B - 1 is zero (BFINAL = 0, BTYPE = 00 and the padding): zero to eight adjacent positions per boundary, about six of them
+ * false by construction (decoded and ignored, as every false candidate).  Bit 0 is not added and final stored blocks are not looked for.
+ * cand, cap and *count as vs_inflate_block_scan; one pass over the stream, nothing outside comp [comp_bytes] is read.  VS_ERR_ARG (and
+ * nothing launched) for a null comp or count, a null cand with cap != 0, a negative comp_bytes or cap, or more bytes than a grid covers;
+ * fewer than 5 bytes launch nothing.                                                                                                    */
+int vs_inflate_block_scan_stored(const uint8_t* comp, int64_t comp_bytes, int64_t* cand, int64_t cap, int64_t* count, void* stream);
 /* One wave per candidate c in first .. first + n - 1 of the SORTED list cand int64 [n_cand] (a batch: the workspace is n rows whatever the
  * member's size): blocks of comp [comp_bytes] are decoded from bit cand[c] until one ends at a bit position that is in the list, a block
  * with BFINAL = 1 has ended (final = 1) or an error (status != 0: a VS_INFLATE_* code; VS_INFLATE_CAP for a span not over after

@@ -163,6 +163,7 @@ SIGNATURES = {
     'vs_inflate_place': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     'vs_inflate_resolve': (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     'vs_inflate_block_scan': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    'vs_inflate_block_scan_stored': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
     'vs_inflate_block_probe': (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     'vs_inflate_block_windows': (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     'vs_inflate_block_decode': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),

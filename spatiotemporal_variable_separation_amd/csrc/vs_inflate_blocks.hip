@@ -10,6 +10,10 @@
 // own, the lanes of a wave side by side (vsb_block_start: the code-length code in two packed words, the lengths as counts per length, no
 // array indexed at run time).  A wave appends its matches with one atomic; the list is unordered and the count goes on past the capacity.
 //
+// vs_inflate_block_scan_stored (opt-in, ops.inflate_block_scan(stored=True)).  The same split of the stream, one pass at memory rate: a
+// thread tests its four byte boundaries for LEN / NLEN = ~LEN with LEN + 1 bytes behind them and counts the zero bits in front of each
+// (vsb_stored_boundary, vsb_stored_count); a boundary appends up to eight adjacent bit positions.  Bit 0 is not added.
+//
 // vs_inflate_block_probe.  ONE WORKGROUP OF ONE WAVE PER CANDIDATE, control flow wave-uniform as in inflate_segments_kernel.  In LDS (about
 // 67.5 KiB: two workgroups per CU): the code tables and a RING of 32768 cells of 16 bits, so the output of a span is not capped; a match is
 // copied by all lanes, LDS operations of a wave execute in program order and a wave-scope fence keeps the compiler from reordering across
@@ -119,6 +123,61 @@ __global__ __launch_bounds__(SCAN_BLOCK) void block_scan_kernel(const uint8_t* _
         hits &= hits - 1;
         if (cand && at < cap) cand[at] = p0 * 8 + q;
         ++at;
+    }
+}
+
+// The stored finder: a thread owns the byte boundaries p0 .. p0 + 3 and reads bytes p0 - 4 .. p0 + 7 (three aligned words, or byte by byte
+// at either end of the stream and for a stream that is not word-aligned): LEN and NLEN of boundary B in bytes B .. B + 3, the zero bits in
+// front of it in bytes B - 2 and B - 1.  Bytes before the stream count as ones (no candidate has a negative position), bytes behind it
+// are never part of a boundary (vsb_stored_boundary's B + 4 <= n).  No LDS, a handful of registers; the list is appended to as above.
+__global__ __launch_bounds__(SCAN_BLOCK) void block_scan_stored_kernel(const uint8_t* __restrict__ comp, int64_t n, int64_t* __restrict__ cand, int64_t cap,
+                                                                       unsigned long long* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p0 = ((int64_t)blockIdx.x * SCAN_BLOCK + threadIdx.x) * SCAN_BYTES;
+    uint32_t prev = 0xffffffffu, cur = 0, next = 0;                         // bytes p0 - 4 .. p0 - 1, p0 .. p0 + 3, p0 + 4 .. p0 + 7
+    if (p0 >= 4 && p0 + 8 <= n && (((uintptr_t)(comp + p0)) & 3) == 0) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(comp + p0);
+        prev = w[-1];
+        cur = w[0];
+        next = w[1];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (p0 - 4 + k >= 0 && p0 - 4 + k < n) prev = (prev & ~(0xffu << (8 * k))) | ((uint32_t)comp[p0 - 4 + k] << (8 * k));
+            if (p0 + k < n) cur |= (uint32_t)comp[p0 + k] << (8 * k);
+            if (p0 + 4 + k < n) next |= (uint32_t)comp[p0 + 4 + k] << (8 * k);
+        }
+    }
+    const uint64_t before = (uint64_t)prev | ((uint64_t)cur << 32), behind = (uint64_t)cur | ((uint64_t)next << 32);
+    uint32_t counts = 0;                                                    // 4 bits per boundary: how many candidates it gives, 0 .. 8
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_BYTES; ++k) {
+        const int64_t B = p0 + k;
+        const uint32_t hdr = (uint32_t)(behind >> (8 * k));                 // LEN in the low half, NLEN in the high half
+        const bool boundary = B + 4 <= n && ((hdr ^ 0xffffu) & 0xffffu) == (hdr >> 16) && B + 4 + (int64_t)(hdr & 0xffffu) < n;
+        const int c = boundary ? vsb_stored_count((uint32_t)(before >> (8 * (k + 2))) & 0xffffu) : 0;
+        counts |= (uint32_t)c << (4 * k);
+        mine += c;
+    }
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+    }
+    const int total = __shfl(incl, 63, 64);
+    if (total == 0) return;                                                 // wave-uniform
+    unsigned long long base = 0;
+    if (lane == 63) base = atomicAdd(count, (unsigned long long)total);
+    base = (unsigned long long)__shfl((long long)base, 63, 64);
+    int64_t at = (int64_t)base + incl - mine;
+    if (!cand) return;
+#pragma unroll
+    for (int k = 0; k < SCAN_BYTES; ++k) {
+        const int c = (int)((counts >> (4 * k)) & 15u);
+        for (int j = 0; j < c; ++j, ++at)
+            if (at < cap) cand[at] = (p0 + k) * 8 - 3 - j;
     }
 }
 
@@ -277,6 +336,21 @@ extern "C" int vs_inflate_block_scan(const uint8_t* comp, int64_t comp_bytes, in
     hipLaunchKernelGGL(block_scan_kernel, dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, (hipStream_t)stream, comp, comp_bytes, cand, cap,
                        reinterpret_cast<unsigned long long*>(count));
     VS_CHECK_LAUNCH("vs_inflate_block_scan");
+    return VS_OK;
+}
+
+extern "C" int vs_inflate_block_scan_stored(const uint8_t* comp, int64_t comp_bytes, int64_t* cand, int64_t cap, int64_t* count, void* stream) {
+    VS_CHECK_ARG(comp && count, "vs_inflate_block_scan_stored: null pointer");
+    VS_CHECK_ARG(comp_bytes >= 0 && cap >= 0, "vs_inflate_block_scan_stored: comp_bytes %lld and cap %lld must not be negative", (long long)comp_bytes,
+                 (long long)cap);
+    VS_CHECK_ARG(cand || cap == 0, "vs_inflate_block_scan_stored: a null list needs cap 0 (got %lld)", (long long)cap);
+    const int64_t per_block = (int64_t)SCAN_BLOCK * SCAN_BYTES;
+    const int64_t blocks = comp_bytes / per_block + 1;
+    VS_CHECK_ARG(blocks <= 2147483647ll, "vs_inflate_block_scan_stored: %lld bytes exceed the grid limit", (long long)comp_bytes);
+    if (comp_bytes < 5) return VS_OK;                                       // no room for LEN, NLEN and a byte behind them: nothing launched
+    hipLaunchKernelGGL(block_scan_stored_kernel, dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, (hipStream_t)stream, comp, comp_bytes, cand, cap,
+                       reinterpret_cast<unsigned long long*>(count));
+    VS_CHECK_LAUNCH("vs_inflate_block_scan_stored");
     return VS_OK;
 }
 

@@ -12,6 +12,9 @@
 //    that removes all but about one position in 500 before the full validation.  Nothing is stored per position: the code-length code
 //    lives in two packed words, the two sets of lengths only as their counts per length (VsiCounters).  Bit 0 is a candidate always.
 //    A false candidate costs a decode that is thrown away and nothing else: see 3.
+//    THE STORED FINDER (vsb_stored_boundary, vsb_stored_start; opt-in) adds the positions from which a non-final STORED block header reads:
+//    BFINAL = 0, BTYPE = 00 and zero padding up to a byte boundary where LEN and NLEN = ~LEN stand and LEN + 1 more bytes follow.  A
+//    boundary gives up to eight adjacent candidates (the padding cannot be told from the header bits); all but one are false, see 3.
 //
 // 2. A SPAN (vsb_inflate_span) is what one wave decodes: blocks (stored, fixed, dynamic) from a bit offset until
 //      * PROBE (cand != null): a block ends at a bit position that is in the sorted candidate list (binary search), or a final block ends;
@@ -188,6 +191,35 @@ VSI_HD bool vsb_is_candidate(const int64_t* cand, int64_t n_cand, int64_t bit) {
         if (cand[mid] < bit) lo = mid + 1; else hi = mid;
     }
     return lo < n_cand && cand[lo] == bit;
+}
+
+// ---- 1b. the finder of stored blocks (opt-in: vs_inflate_block_scan_stored) ------------------------------------------------------------
+// A stored block's header is BFINAL, BTYPE = 00, zero bits up to the next byte boundary, then LEN and NLEN = ~LEN at that boundary.  Byte
+// offset B is a STORED BOUNDARY when LEN and NLEN read there, complementary, and the LEN bytes behind them are followed by at least one
+// more byte of the stream (a non-final block is followed by another header).  LEN = 0 counts: 00 00 ff ff is an empty stored block.
+VSI_HD bool vsb_stored_boundary(const uint8_t* comp, int64_t n, int64_t B) {
+    if (B < 0 || n < 4 || B > n - 4) return false;
+    const uint32_t len = (uint32_t)comp[B] | ((uint32_t)comp[B + 1] << 8), nlen = (uint32_t)comp[B + 2] | ((uint32_t)comp[B + 3] << 8);
+    return (len ^ 0xffffu) == nlen && B + 4 + (int64_t)len < n;
+}
+
+// How many bit positions in front of the stored boundary at bit 8 * B are candidates, given the 16 bits in front of it (bit 15 of `front`
+// is stream bit 8 * B - 1; bits before the stream's first must be ones): the positions 8 * B - 3 - k, k = 0 .. count - 1, from each of
+// which three header bits and k padding bits read as zeros.  0 .. 8.
+VSI_HD int vsb_stored_count(uint32_t front) {
+    const int zeros = __builtin_clz(((front & 0xffffu) << 16) | (1u << 21));   // zero bits straight in front of the boundary, 10 at most
+    return zeros < 3 ? 0 : zeros - 2;
+}
+
+// Whether bit position `bit` of comp[0 .. n) is a candidate of the stored rule: the header bits BFINAL = 0, BTYPE = 00 read from it, at
+// most seven zero bits pad it to a byte boundary, and that boundary is a stored boundary.  Reads bytes B - 2 .. B + 3 at most.
+VSI_HD bool vsb_stored_start(const uint8_t* comp, int64_t n, int64_t bit) {
+    if (bit < 0 || n < 4) return false;
+    const int64_t B = (bit + 3 + 7) >> 3;                                   // the boundary behind the three header bits
+    if (!vsb_stored_boundary(comp, n, B)) return false;
+    for (int64_t q = bit; q < 8 * B; ++q)                                   // at most 10 bits, all in bytes B - 2 and B - 1
+        if ((comp[q >> 3] >> (q & 7)) & 1u) return false;
+    return true;
 }
 
 // ---- 2. a span -----------------------------------------------------------------------------------------------------------------------

@@ -281,22 +281,25 @@ class MovingMNIST:
 
     @classmethod
     def make_dataset(cls, data_dir, nx, nt_cond, seq_len, max_speed, deterministic, num_digits, train, device='cuda', seed=None, load=None, report=None,
-                     foreign=None):
+                     foreign=None, finder=None):
         """load: who decompresses the test-set file (utils/loadz.npz_loader: the keyword, then VARSEP_NPZ_LOAD, then 'host').  'host' is
         np.load and the host conversion, as before; 'device' inflates `sequences` in HBM (utils/loadz.load), where it stays uint8 until the
         [T, N, ...] -> fp32 [N, T, ...] step, also done there.  `.data` is the same bit for bit.  report: optional dict for
         utils/loadz.load's record of the route `sequences` took.  foreign: with 'device', who decompresses a file that is not cut at sync
         markers, as np.savez_compressed writes it (utils/loadz.npz_foreign: the keyword, then VARSEP_NPZ_FOREIGN, then 'host'), read here
-        with the first rule and handed on when it is not the default."""
+        with the first rule and handed on when it is not the default.  finder: with both 'device', which block headers are found
+        (utils/loadz.npz_finder: the keyword, then VARSEP_NPZ_FINDER, then 'dynamic'), read and handed on in the same way."""
         if train:
             data = synthetic_digits(seed=seed or 1234) if data_dir == 'synthetic_digits' else read_mnist_images(data_dir, train=True)
         else:
             from ..utils import loadz
             prefix = '' if deterministic else 's'
             path = os.path.join(data_dir, f'{prefix}mmnist_test_{num_digits}digits_{nx}.npz')
-            how, who = loadz.npz_loader(load), loadz.npz_foreign(foreign)
+            how, who, which = loadz.npz_loader(load), loadz.npz_foreign(foreign), loadz.npz_finder(finder)
             if how == 'device':
                 extra = {} if foreign is None and who == 'host' else {'foreign': who}
+                if finder is not None or which != 'dynamic':
+                    extra['finder'] = which
                 sequences = loadz.load(path, device, keys=('sequences',), load='device', report=report, **extra)['sequences']
                 if sequences.dtype == torch.uint8:
                     from .. import ops

@@ -2831,29 +2831,40 @@ INFLATE_CAP = 12                  # VS_INFLATE_CAP
 INFLATE_DECODE_WORDS = 3          # VS_INFLATE_DECODE_WORDS: status, end, produced
 
 
-def inflate_block_scan(comp):
+def _block_scan(entry, comp):
+    """One finder (`entry`: vs_inflate_block_scan or vs_inflate_block_scan_stored) on comp: once to count and once to list, then sorted."""
+    lib, device, n = _lib.load_library(), comp.device, comp.numel()
+    scan = getattr(lib, entry)
+    count = torch.zeros((2,), dtype=torch.int64, device=device)
+    keep = comp if n else torch.zeros((1,), dtype=torch.uint8, device=device)
+    e0 = _pb()
+    check(scan(keep.data_ptr(), n, None, 0, count.data_ptr(), stream_ptr()), entry)
+    _pe(e0, entry, nbytes=float(n))
+    found = int(count[0].item())
+    cand = torch.empty((found,), dtype=torch.int64, device=device)
+    e0 = _pb()
+    check(scan(keep.data_ptr(), n, cand.data_ptr(), found, count[1:].data_ptr(), stream_ptr()), entry)
+    _pe(e0, entry, nbytes=float(n))
+    return torch.sort(cand).values
+
+
+def inflate_block_scan(comp, stored=False):
     """The candidate span starts of a raw DEFLATE stream without sync markers: int64 [n] BIT positions on the device, sorted -- bit 0 and
     every bit from which a non-final dynamic block header reads (vs_inflate_block_scan, once to count and once to list; the sort of the
-    short list is torch's)."""
+    short list is torch's).  stored=True: the sorted union of that list and the stored finder's (vs_inflate_block_scan_stored: for every
+    byte boundary B where LEN and NLEN = ~LEN stand with LEN + 1 more bytes behind them, the up to eight bit positions 8 * B - 3 - k from
+    which only zero bits lead to the boundary)."""
     require_cuda(comp)
     if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous():
         raise _lib.VarsepHipError('inflate_block_scan: a contiguous uint8 [bytes] tensor expected')
-    lib, device, n = _lib.load_library(), comp.device, comp.numel()
-    with torch.cuda.device(device):
-        count = torch.zeros((2,), dtype=torch.int64, device=device)
-        keep = comp if n else torch.zeros((1,), dtype=torch.uint8, device=device)
-        e0 = _pb()
-        check(lib.vs_inflate_block_scan(keep.data_ptr(), n, None, 0, count.data_ptr(), stream_ptr()), 'vs_inflate_block_scan')
-        _pe(e0, 'vs_inflate_block_scan', nbytes=float(n))
-        found = int(count[0].item())
-        cand = torch.empty((found,), dtype=torch.int64, device=device)
-        e0 = _pb()
-        check(lib.vs_inflate_block_scan(keep.data_ptr(), n, cand.data_ptr(), found, count[1:].data_ptr(), stream_ptr()), 'vs_inflate_block_scan')
-        _pe(e0, 'vs_inflate_block_scan', nbytes=float(n))
-        return torch.sort(cand).values
+    with torch.cuda.device(comp.device):
+        cand = _block_scan('vs_inflate_block_scan', comp)
+        if not stored:
+            return cand
+        return torch.unique(torch.cat((cand, _block_scan('vs_inflate_block_scan_stored', comp))))     # sorted, and bit 0 once
 
 
-def inflate_blocks(comp, out_bytes, crc=None, batch=None, trace=None):
+def inflate_blocks(comp, out_bytes, crc=None, batch=None, trace=None, stored=False):
     """The `out_bytes` bytes of the raw DEFLATE stream `comp` (uint8 [bytes] on the device) that has NO sync markers -- one unbroken stream
     of zlib, what np.savez_compressed stores -- decoded in parallel at its block headers: uint8 [out_bytes] on the device, or an
     InflateNotChunked when the spans do not chain (the caller then decodes the stream another way).
@@ -2864,11 +2875,14 @@ def inflate_blocks(comp, out_bytes, crc=None, batch=None, trace=None):
     far, and the chain must total out_bytes.  A block end that is a candidate is a true block start, so false candidates are decoded and
     ignored.  Per batch the chain's spans get their true windows in chain order (vs_inflate_block_windows, one workgroup) and are decoded a
     second time straight into the output (vs_inflate_block_decode), whose status, end and size must be the probe's.  A span that reads more
-    than INFLATE_BLOCKS_MAX_IN bytes of input (long runs of stored or fixed blocks) does not chain.  crc: the CRC-32 the result must have
+    than INFLATE_BLOCKS_MAX_IN bytes of input before a candidate does not chain: with the dynamic finder alone long runs of stored or
+    fixed blocks; with stored=True (inflate_block_scan(comp, stored=True): the stored finder's candidates too, about six of them per
+    stored block, false ones probed and ignored like any other) only long runs of fixed blocks.  crc: the CRC-32 the result must have
     (ops.crc32); a mismatch after a valid chain raises zipfile.BadZipFile.  trace: optional list that receives per decoded batch a dict
     (first: first candidate index, cand: the sorted candidates as a host array, words int64 [n, 6], chain: rows of the batch on the chain,
     windows uint8 [chain + 1, 32768] and words2 int64 [chain, 3], both None where the batch has no span of the chain or the chain broke in
-    it), and after a walk to the end a dict(candidates, chain, workspace_bytes)."""
+    it), and after a walk to the end a dict(candidates, chain, workspace_bytes), with stored=True also stored_candidates (how many
+    of the candidates the dynamic finder alone does not give)."""
     import numpy as np
     require_cuda(comp)
     out_bytes = int(out_bytes)
@@ -2878,7 +2892,11 @@ def inflate_blocks(comp, out_bytes, crc=None, batch=None, trace=None):
     lib, device, n = _lib.load_library(), comp.device, comp.numel()
     W, RW, DW = INFLATE_WINDOW_BYTES, INFLATE_REPORT_WORDS, INFLATE_DECODE_WORDS
     with torch.cuda.device(device):
-        cand = inflate_block_scan(comp)
+        if stored:
+            dynamic = inflate_block_scan(comp)
+            cand = torch.unique(torch.cat((dynamic, _block_scan('vs_inflate_block_scan_stored', comp))))
+        else:
+            cand = inflate_block_scan(comp)
         starts = cand.cpu().numpy()
         n_cand = starts.size
         rows = min(batch, n_cand)
@@ -2954,6 +2972,8 @@ def inflate_blocks(comp, out_bytes, crc=None, batch=None, trace=None):
         if trace is not None:
             trace.append(dict(candidates=int(n_cand), chain=chain_len,
                               workspace_bytes=sum(x.numel() * x.element_size() for x in (cand, cells, words, windows, words2))))
+            if stored:
+                trace[-1]['stored_candidates'] = int(n_cand - dynamic.numel())
         if not final:
             return InflateNotChunked('the chain leaves the candidates before a final block')
         if total != out_bytes:

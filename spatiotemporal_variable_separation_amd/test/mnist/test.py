@@ -17,7 +17,9 @@ the same; measurements and the sizes of the device-written files: profiles/eval_
 Who decompresses the test-set file D/[s]mmnist_test_*.npz: VARSEP_NPZ_LOAD=host|device (utils/loadz.py), read once at the same place.
 `host` (the default) is np.load and the host conversion, as before; `device` uploads the compressed bytes and inflates them in HBM.
 With `device`, VARSEP_NPZ_FOREIGN=host|device (read at that same place) says who inflates a file that is not cut at sync markers, as
-np.savez_compressed writes it: the host (the default) or the block-parallel reader of csrc/vs_inflate_blocks.hip.
+np.savez_compressed writes it: the host (the default) or the block-parallel reader of csrc/vs_inflate_blocks.hip.  With both `device`,
+VARSEP_NPZ_FINDER=dynamic|all (read there too) says whether that reader starts at dynamic block headers alone (the default) or at stored
+ones as well.
 """
 import os
 
@@ -37,11 +39,11 @@ def split_data_dir(data_dir):
     return (data_dir[len(GENERATED):], True) if data_dir.startswith(GENERATED) else (data_dir, False)
 
 
-def load_dataset(args, train=False, device='cuda', stochastic=False, load=None, foreign=None):
+def load_dataset(args, train=False, device='cuda', stochastic=False, load=None, foreign=None, finder=None):
     """stochastic: the command line's --mnist_stochastic, never the `mnist_stochastic` that training saved in params.json (`args` is that
     configuration): an existing experiment is evaluated on what it was evaluated on before.  load: who decompresses the test-set file
-    (utils/loadz.npz_loader) and foreign: who decompresses it when it is not cut at sync markers (utils/loadz.npz_foreign), each handed on
-    only when it was given."""
+    (utils/loadz.npz_loader), foreign: who decompresses it when it is not cut at sync markers (utils/loadz.npz_foreign) and finder: which
+    block headers the device then looks for (utils/loadz.npz_finder), each handed on only when it was given."""
     data_dir, generated = split_data_dir(args.data_dir)
     if generated and not train:      # make_test_set.py's defaults: seed 42, 100 frames, frame size 64, speed 4
         return MovingMNIST.generated(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, args.n_object, device,
@@ -49,6 +51,8 @@ def load_dataset(args, train=False, device='cuda', stochastic=False, load=None, 
     extra = {} if load is None or train else {'load': load}
     if foreign is not None and not train:
         extra['foreign'] = foreign
+    if finder is not None and not train:
+        extra['finder'] = finder
     return MovingMNIST.make_dataset(data_dir, 64, args.nt_cond, args.nt_cond + args.nt_pred, 4, not stochastic, args.n_object, train,
                                     device=device, **extra)
 
@@ -78,13 +82,15 @@ def main(args):
     compress = savez.npz_compressor()         # who compresses the six frame files: read once, a bad value is refused before any work
     load = loadz.npz_loader()                 # who decompresses the test-set file (VARSEP_NPZ_LOAD): read once, here
     foreign = loadz.npz_foreign()             # and who does when it has no sync markers (VARSEP_NPZ_FOREIGN)
+    finder = loadz.npz_finder()               # and which block headers the device then finds (VARSEP_NPZ_FINDER)
     device = setup_device(args)
     seed_all(args.test_seed)
     xp_config = load_xp_config(args, device, args.nt_pred)
 
     print('Loading data...')
     stochastic = bool(getattr(args, 'mnist_stochastic', False))
-    test_dataset = load_dataset(xp_config, train=False, device=device, stochastic=stochastic, load=load, foreign=foreign)
+    test_dataset = load_dataset(xp_config, train=False, device=device, stochastic=stochastic, load=load, foreign=foreign,
+                                **({} if finder == 'dynamic' else {'finder': finder}))
     train_dataset = load_dataset(xp_config, train=True, device=device, stochastic=stochastic)
     nc = 1
     size = 64

@@ -13,8 +13,15 @@ markers).  Stored members (method 0) are uploaded as they are.  The zip director
 Foreign members: VARSEP_NPZ_FOREIGN=host|device (`foreign=` in code; same precedence, default `host`) matters only while the loader is
 `device`.  `host` is the paragraph above.  `device` sends a member that does not chain at sync markers -- every np.savez_compressed member --
 to ops.inflate_blocks (csrc/vs_inflate_blocks.hip: block headers found by validation, one wave per span between two of them, each span
-decoded twice), and only a member that does not chain there either (more than 1 MiB of input between two dynamic block headers: long runs
-of stored or fixed blocks) takes the host route.
+decoded twice), and only a member that does not chain there either (more than 1 MiB of input between two block headers the finder knows)
+takes the host route.
+
+Which block headers are found: VARSEP_NPZ_FINDER=dynamic|all (`finder=` in code; same precedence, default `dynamic`) matters only while
+both rules above say `device`.  `dynamic` finds dynamic-Huffman headers alone, so a member with more than 1 MiB of stored or fixed blocks
+between two of them -- random or already-compressed bytes, the noisy parts of float arrays -- goes to the host.  `all` also finds stored
+headers (ops.inflate_blocks(stored=True): LEN and NLEN = ~LEN at a byte boundary with zero bits in front; about six candidates per stored
+block, all but one false and ignored), which leaves only more than 1 MiB of FIXED blocks between two findable headers (zlib's Z_FIXED) to
+the host: the 7-bit fixed header cannot be validated.
 """
 import os
 import zlib
@@ -27,6 +34,7 @@ from . import npz
 
 LOAD_ENV = 'VARSEP_NPZ_LOAD'
 FOREIGN_ENV = 'VARSEP_NPZ_FOREIGN'
+FINDER_ENV = 'VARSEP_NPZ_FINDER'
 _HEAD_BYTES = 1 << 16                # compressed bytes inflated on the host to read a member's .npy header (a header is at most 64 KiB + 10)
 
 
@@ -51,6 +59,18 @@ def npz_foreign(foreign=None):
     if foreign not in ('host', 'device'):
         raise ValueError("%s=%r: 'host' or 'device' expected" % (source, foreign))
     return foreign
+
+
+def npz_finder(finder=None):
+    """'dynamic' or 'all': which block headers the block-parallel reader looks for while the loader and the foreign rule are both 'device'.
+    The keyword wins; None reads the environment variable VARSEP_NPZ_FINDER; when that is unset or empty dynamic-Huffman headers alone are
+    found (the behaviour before the stored finder existed).  Any other value raises, naming the two."""
+    source = 'finder'
+    if finder is None:
+        finder, source = os.environ.get('VARSEP_NPZ_FINDER', '') or 'dynamic', FINDER_ENV
+    if finder not in ('dynamic', 'all'):
+        raise ValueError("%s=%r: 'dynamic' or 'all' expected" % (source, finder))
+    return finder
 
 
 def _key(entry):
@@ -110,14 +130,16 @@ def _as_array(raw, header):
     return data.view(dtype).reshape(header.shape)
 
 
-def load(path, device, keys=None, load=None, report=None, foreign=None):
+def load(path, device, keys=None, load=None, report=None, foreign=None, finder=None):
     """The arrays of the .npz file `path` as {name: tensor on `device`}, names as np.load gives them; keys: the names wanted (default
     all, in the file's order).  load: 'host' (np.load, then an upload), 'device' (see the module docstring) or None (`npz_loader`).
     report: optional dict that receives name -> (route, why) with route 'host', 'device' or 'stored'.  An array torch cannot hold (object,
     structured) is returned as the host array.  A damaged member raises what np.load raises for it (zipfile.BadZipFile, zlib.error, ...).
-    foreign: 'host', 'device' or None (`npz_foreign`): with load='device', who decompresses a member that does not chain at sync markers."""
+    foreign: 'host', 'device' or None (`npz_foreign`): with load='device', who decompresses a member that does not chain at sync markers.
+    finder: 'dynamic', 'all' or None (`npz_finder`): with both 'device', whether stored block headers are found too."""
     load = npz_loader(load)
     foreign = npz_foreign(foreign)
+    finder = npz_finder(finder)
     device = torch.device(device)
     report = {} if report is None else report
     out = {}
@@ -154,7 +176,8 @@ def load(path, device, keys=None, load=None, report=None, foreign=None):
                     raw = ops.inflate_raw(comp, e.usize, crc=e.crc32)
                     route = ('device', 'chained at its sync markers')
                     if isinstance(raw, ops.InflateNotChunked) and foreign == 'device':
-                        raw = ops.inflate_blocks(comp, e.usize, crc=e.crc32)
+                        raw = ops.inflate_blocks(comp, e.usize, crc=e.crc32, stored=True) if finder == 'all' \
+                            else ops.inflate_blocks(comp, e.usize, crc=e.crc32)
                         route = ('device', 'chained at its block headers')
                     if isinstance(raw, ops.InflateNotChunked):
                         why = 'not chunked: ' + raw.reason
